@@ -12,6 +12,15 @@ One step = encode(2^20 payloads -> codewords)            [rs255 encode kernel]
          + decode(codewords -> payloads, status, in-place write-back)   [rs255 decode kernel]
 value = algorithmic bytes of all ranks (encode k+n B + decode n+k B per block) / step time.
 
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps once, checks the
+last step's result on the device and prints the headline line (value, ms_per_step, ...).  `--full`
+adds every other leg after the timed region: three repeat regions, in-step / standalone kernel times
+and the roofline, the device copy ceiling, the host-inclusive path and host link, the other BASELINE
+configs, cfg1 and the CPU baselines (the --no-* switches drop single legs of a --full run).
+`--dump-outputs DIR` writes what the last timed step computed -- codewords after write-back,
+payloads, statuses of a fixed seeded sample of the blocks -- as DIR/<name>.npy (float32); the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
+
 Multi-GPU: one process per GPU.  `python bench.py --gpus N` (N > 1, no torchrun env) starts
 `torch.distributed.run` with N ranks as a child process before anything touches a GPU and exits
 with its code; under torchrun (WORLD_SIZE set) each rank runs its own shard.  Blocks are
@@ -46,6 +55,13 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=None, help="GPUs (ranks); default: WORLD_SIZE or 1")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (repeat regions, in-step / standalone "
+                         "kernel times and roofline, device copy, host-inclusive, per-config kernels, cfg1, CPU "
+                         "baseline); a plain run sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed (codewords after write-back, "
+                         "payloads, statuses; a fixed seeded sample of the blocks) as DIR/<name>.npy, float32")
     ap.add_argument("--launch", choices=("eager", "graph"), default="eager",
                     help="eager launches (default) or one hipGraph per --graph-steps steps")
     ap.add_argument("--graph-steps", type=int, default=10, help="steps captured per hipGraph (--launch graph)")
@@ -293,6 +309,27 @@ def timed_steps(step, steps, world, sync, device=None, pre=None, bar_group=None)
     return elapsed
 
 
+DUMP_SAMPLE_BLOCKS = 1 << 14  # --dump-outputs: 2^14 blocks x (n + k) <= 510 values x 4 B = 33 MB
+DUMP_STATUS_MAX = 1 << 22  # every block's status up to 2^22 blocks (16 MB as float32), else the sample's
+
+
+def dump_sample(nb):
+    """The blocks --dump-outputs writes: all of them up to DUMP_SAMPLE_BLOCKS, else a fixed seeded
+    choice (sorted block indices; the same for every run and build with the same --blocks)."""
+    if nb <= DUMP_SAMPLE_BLOCKS:
+        return np.arange(nb, dtype=np.int64)
+    return np.sort(np.random.default_rng(0x44554D50).choice(nb, DUMP_SAMPLE_BLOCKS, replace=False)).astype(np.int64)
+
+
+def write_dump(dirname, rank, arrays):
+    """DIR/<name>.npy (rank 0; the other ranks' shards as <name>_rank<r>.npy): bytes as float32,
+    block indices (int64) as float64."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}{'' if rank == 0 else f'_rank{rank}'}.npy"),
+                np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.int64 else np.float32))
+
+
 def lib_sha256():
     from paritypartyfs_amd import _native
 
@@ -501,6 +538,8 @@ def dry_run(args, world, rank):
     for _ in range(args.warmup):
         step()
     elapsed = timed_steps(step, args.steps, world, lambda: None, None)
+    if args.dump_outputs:
+        write_dump(args.dump_outputs, rank, {"buffer": buf})
     mine = {"rank": rank, "block_size": args.block_size, "t": args.t, "blocks": args.blocks,
             "encode": float(np.mean(part_s["encode"])) * 1e3, "decode": float(np.mean(part_s["decode"])) * 1e3}
     gathered = [mine]
@@ -662,21 +701,92 @@ def main(argv=None):
     # to back).  The self-check runs after the region.
     elapsed = timed_steps(lambda: run_steps(args.steps), 1, world, torch.cuda.synchronize, red_dev,
                           pre=lambda: run_steps(args.warmup), bar_group=bar_group)
-    # the same timed region again, 3 times (reported beside the measurement, never as `value`):
-    # shows whether the measured region was representative of back-to-back regions
+    # --full: the same timed region again, 3 times (reported beside the measurement, never as
+    # `value`): shows whether the measured region was representative of back-to-back regions
     repeats = [timed_steps(lambda: run_steps(args.steps), 1, world, torch.cuda.synchronize, red_dev,
                            pre=lambda: run_steps(max(2, args.warmup)), bar_group=bar_group) / args.steps * 1e3
-               for _ in range(3)]
+               for _ in range(3 if args.full else 0)]
     # device-side self-check of the last timed step: every block corrected, payload restored
     ok = bool(torch.equal(out, data)) and int(status.min()) == 1 and int(status.max()) == 1
     if not ok:
         print(json.dumps({"error": "verification failed"}), file=sys.stderr)
         return 3
+    if args.dump_outputs:
+        # what a caller of the last step holds: the codewords after the decode's write-back, the
+        # payloads and the statuses (every step computes the same: the inputs never change)
+        idx = dump_sample(nb)
+        sel = torch.from_numpy(idx).to(dev)
+        st_all = nb <= DUMP_STATUS_MAX
+        write_dump(args.dump_outputs, rank, {
+            "sample_blocks": idx,
+            "codewords": cw.view(nb, n).index_select(0, sel).cpu().numpy(),
+            "payload": out.view(nb, k).index_select(0, sel).cpu().numpy(),
+            "status": (status if st_all else status.index_select(0, sel)).cpu().numpy(),
+        })
 
-    # ---- everything below is outside the timed region ----
+    K = args.steps
+    alg_per_block = k + n  # 504 B for RS(255,249), both for encode and decode
+    alg_launch = alg_per_block * nb
+    if (args.block_size, args.t) == (512, 3):
+        cfg_ref = "BASELINE configs[1]+[2]"
+    elif (args.block_size, args.t) == (4096, 16):
+        cfg_ref = "BASELINE configs[4], one GPU's shard"
+    else:
+        cfg_ref = "not a BASELINE config"
+    total_bytes = 2 * alg_launch * world * K
+    value = total_bytes / elapsed / GIB
+    ms_per_step = elapsed / K * 1e3
+    # the headline fields, complete after the timed region (a plain run prints these and ends)
+    line = {
+        "metric": METRIC,
+        "value": round(value, 3),
+        "unit": "GiB/s",
+        "n_gpus": world,
+        "steps": K,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic",
+        "config": {
+            "workload": f"RS({n},{k}) t={args.t} block_size={args.block_size}: encode + 1-byte-error "
+                        f"inject + decode with write-back, {nb} blocks per GPU ({cfg_ref})",
+            "blocks_per_gpu": nb,
+            "global_blocks": nb * world,
+            "parallelism": f"shard{world}",
+        },
+        **({"rehearsal": f"{world} ranks sharing {torch.cuda.device_count()} GPU(s), barrier / max-reduce "
+                         "over gloo: the multi-rank path on real kernels, not a scaling figure"}
+           if world > 1 and args.share_gpu else {}),
+    }
+    collectives = ("rccl max-reduce, gloo barriers" if dist.is_initialized() and dist.get_backend() == "nccl"
+                   else "gloo" if dist.is_initialized() else "none (single process, no torchrun)")
+    launch_form = f"hipGraph of {group} steps" if graph is not None else "eager"
+    if not args.full:
+        if rank == 0:
+            line.update({
+                "full": False,
+                # the payload rate, and the timed region's algorithmic bytes over
+                # all ranks / (N x 8 TB/s); every other figure takes runs of its own (--full)
+                "aggregate_frac": round(total_bytes / elapsed / 1e9 / (world * HBM_PEAK_GBS), 4),
+                "aggregate_peak_GBps": world * HBM_PEAK_GBS,
+                "aggregate_bytes": total_bytes,
+                "payload_GiBps": round(value * k / alg_per_block, 3),
+                "kernel_path": eng.stream_kernel_name(stream),
+                "collectives": collectives,
+                "launch": launch_form,
+            })
+            print(json.dumps(line), flush=True)
+        eng.close()
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return 0
+
+    # ---- --full: everything below is outside the timed region ----
     # (1) in-step kernel durations (roofline.achieved): eager steps bracketed by fence-free HIP
     # events on the launch stream, all K queued before one synchronize
-    K = args.steps
     # every measurement below starts from the sustained clock again (the self-check idled the GPU)
     rewarm(0.3)
     # Two measures per kernel: (a) events recorded on the stream around each call (they include the
@@ -798,18 +908,6 @@ def main(argv=None):
     hc.close()
     del cp_src, cp_dst, cps
 
-    alg_per_block = k + n  # 504 B for RS(255,249), both for encode and decode
-    alg_launch = alg_per_block * nb
-    if (args.block_size, args.t) == (512, 3):
-        cfg_ref = "BASELINE configs[1]+[2]"
-    elif (args.block_size, args.t) == (4096, 16):
-        cfg_ref = "BASELINE configs[4], one GPU's shard"
-    else:
-        cfg_ref = "not a BASELINE config"
-    total_bytes = 2 * alg_launch * world * K
-    value = total_bytes / elapsed / GIB
-    ms_per_step = elapsed / K * 1e3
-
     def kname(which):
         kn = eng.kernel_name
         if kn.startswith("rs255-wg-tk"):  # 2t <= 8: ticket kernels (rs_wg_tk.hpp); tkenc: encode only
@@ -925,29 +1023,8 @@ def main(argv=None):
                            min(args.cpu_faithful_blocks, nb))
 
     if rank == 0:
-        line = {
-            "metric": METRIC,
-            "value": round(value, 3),
-            "unit": "GiB/s",
-            "n_gpus": world,
-            "steps": K,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic",
-            "config": {
-                "workload": f"RS({n},{k}) t={args.t} block_size={args.block_size}: encode + 1-byte-error "
-                            f"inject + decode with write-back, {nb} blocks per GPU ({cfg_ref})",
-                "blocks_per_gpu": nb,
-                "global_blocks": nb * world,
-                "parallelism": f"shard{world}",
-            },
-            **({"rehearsal": f"{world} ranks sharing {torch.cuda.device_count()} GPU(s), barrier / max-reduce "
-                             "over gloo: the multi-rank path on real kernels, not a scaling figure"}
-               if world > 1 and args.share_gpu else {}),
+        line.update({
+            "full": True,
             "roofline": {
                 "bound": "hbm",
                 "kernel": dom_name,
@@ -1000,13 +1077,12 @@ def main(argv=None):
             "roofline_frac_of_device_copy": round(achieved / copy_gbs, 4) if copy_gbs else None,
             "host_inclusive": host_incl,
             "kernel_path": eng.stream_kernel_name(stream),
-            "collectives": ("rccl max-reduce, gloo barriers" if dist.is_initialized() and dist.get_backend() == "nccl"
-                            else "gloo" if dist.is_initialized() else "none (single process, no torchrun)"),
-            "launch": f"hipGraph of {group} steps" if graph is not None else "eager",
+            "collectives": collectives,
+            "launch": launch_form,
             "host_issue_us_per_eager_step": round(t_issue * 1e6, 1),
             "device_ms_per_step": round(gpu_ms_per_step, 4),
             "repeat_ms_per_step": [round(x, 4) for x in repeats],
-        }
+        })
         print(json.dumps(line), flush=True)
     eng.close()
     if dist.is_initialized():

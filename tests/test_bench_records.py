@@ -81,6 +81,39 @@ def test_config_lines_carry_cold_per_leg_fractions():
     assert abs(st["GiBps"] - 2 * 478 * nb / 0.25e-3 / 2**30) < 1e-2
 
 
+def test_dump_sample_is_fixed_and_within_budget():
+    """--dump-outputs: the sampled blocks are the same for every run (seeded, sorted, distinct), all
+    blocks when few, and codewords + payloads + statuses as float32 stay under 64 MB at 2^20 blocks."""
+    import numpy as np
+
+    assert np.array_equal(bench.dump_sample(1000), np.arange(1000))
+    a, b = bench.dump_sample(1 << 20), bench.dump_sample(1 << 20)
+    assert np.array_equal(a, b) and a.dtype == np.int64 and len(a) == bench.DUMP_SAMPLE_BLOCKS
+    assert np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < 1 << 20
+    # RS codewords are at most 255 B (n + k <= 510 values per block); statuses: one per block
+    total = 4 * (len(a) * 510 + min(1 << 20, bench.DUMP_STATUS_MAX)) + 8 * len(a)
+    assert total <= 64 * 10**6
+    worst = 4 * (bench.DUMP_SAMPLE_BLOCKS * 510 + max(bench.DUMP_STATUS_MAX, bench.DUMP_SAMPLE_BLOCKS)) \
+        + 8 * bench.DUMP_SAMPLE_BLOCKS
+    assert worst <= 64 * 10**6  # any --blocks
+
+
+def test_dump_outputs_and_plain_options_parse(tmp_path, capsys):
+    """The launch / timing path with --dump-outputs (CPU stand-in): DIR/<name>.npy in float32, the
+    line carries ms_per_step and the steps asked for; --full is off unless given."""
+    import numpy as np
+
+    assert bench.parse([]).full is False and bench.parse(["--full"]).full is True
+    assert bench.parse([]).dump_outputs is None
+    d = tmp_path / "dump"
+    assert bench.main(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dry-run-cpu", "--dump-outputs", str(d)]) == 0
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    arr = np.load(d / "buffer.npy")
+    assert arr.dtype == np.float32 and arr.shape == (1 << 16,)
+    assert np.all(arr == 0)  # 3 + 1 XORs with 1: an even count leaves the stand-in's buffer at zero
+
+
 def test_cfg1_leg_parses_the_harness_lines(monkeypatch, tmp_path):
     """bench.py's cfg1 object from tests/cpp/bench_blockdevice's JSON lines (the binary is stood in)."""
     import subprocess

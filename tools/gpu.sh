@@ -10,8 +10,8 @@
 #   rs           the RS parity tests (tests/test_gpu_parity.py -k rs)
 #   parity       every test of tests/test_gpu_parity.py (RS, CRC, Hamming, parity vs the oracle)
 #   smoke        __graft_entry__.smoke()
-#   bench        the default bench line (no CPU column, no host-inclusive leg)
-#   benchfull    the default bench line with every leg (what the driver runs)
+#   bench        the default bench line with its kernel legs (--full; no CPU column, no host-inclusive leg)
+#   benchfull    the default bench line with every leg (bench.py --full)
 #   cfg5         the cfg5 (RS t = 16, 4 KiB) bench line
 #   configs      tools/bench_configs.py (every BASELINE config, kernel-only)
 #   prof         tools/profile_box.sh TAG (rocprofv3 kernel trace + PMC passes)
@@ -45,14 +45,14 @@ for step in "$@"; do
         timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > ${O}_smoke.log 2>&1
         rc=$?; tail -2 ${O}_smoke.log; [ $rc -eq 0 ] || exit $rc ;;
     bench)
-        timeout -k 10 300 python bench.py --no-cpu-baseline --no-host-inclusive --no-configs > ${O}_bench.json 2> ${O}_bench.err \
+        timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-host-inclusive --no-configs > ${O}_bench.json 2> ${O}_bench.err \
             || { tail -5 ${O}_bench.err; exit 1; }
         line ${O}_bench.json bench ;;
     benchfull)
-        timeout -k 10 600 python bench.py > ${O}_benchfull.json 2> ${O}_benchfull.err || { tail -5 ${O}_benchfull.err; exit 1; }
+        timeout -k 10 600 python bench.py --full > ${O}_benchfull.json 2> ${O}_benchfull.err || { tail -5 ${O}_benchfull.err; exit 1; }
         line ${O}_benchfull.json benchfull ;;
     cfg5)
-        timeout -k 10 300 python bench.py --block-size 4096 --t 16 --no-cpu-baseline --no-host-inclusive --no-configs \
+        timeout -k 10 300 python bench.py --full --block-size 4096 --t 16 --no-cpu-baseline --no-host-inclusive --no-configs \
             > ${O}_bench_cfg5.json 2> ${O}_bench_cfg5.err || { tail -5 ${O}_bench_cfg5.err; exit 1; }
         line ${O}_bench_cfg5.json cfg5 ;;
     configs)
@@ -65,7 +65,7 @@ for step in "$@"; do
         IFS=, read -r A B N <<< "${step#ab=}"
         for r in $(seq 1 ${N:-3}); do
             for L in "$A" "$B"; do
-                PPFS_ECC_LIB=$L timeout -k 10 300 python bench.py --no-cpu-baseline --no-host-inclusive --no-configs \
+                PPFS_ECC_LIB=$L timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-host-inclusive --no-configs \
                     > ${O}_ab.tmp 2> ${O}_ab.err || { tail -5 ${O}_ab.err; exit 1; }
                 echo "{\"lib\": \"$L\", \"round\": $r, \"line\": $(tail -1 ${O}_ab.tmp)}" >> ${O}_ab.jsonl
                 line ${O}_ab.tmp "$(basename $L) r$r"

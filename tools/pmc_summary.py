@@ -20,7 +20,7 @@ import sys
 from collections import defaultdict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BENCH_ARGS = "bench.py --steps 50 --warmup 5 --prewarm-s 0.3 --no-cpu-baseline --no-host-inclusive"
+BENCH_ARGS = "bench.py --full --steps 50 --warmup 5 --prewarm-s 0.3 --no-cpu-baseline --no-host-inclusive"
 
 
 def short(name):

@@ -11,7 +11,7 @@ RAW=/tmp/prof_$TAG
 mkdir -p $OUT $RAW
 sha256sum $ROOTDIR/paritypartyfs_amd/_lib/libppfs_ecc.so | cut -d' ' -f1 > $OUT/lib.sha256
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOTDIR/bench.py --steps 50 --warmup 5 --prewarm-s 0.3 --no-cpu-baseline --no-host-inclusive $*"
+B="python3 $ROOTDIR/bench.py --full --steps 50 --warmup 5 --prewarm-s 0.3 --no-cpu-baseline --no-host-inclusive $*"
 # the same bench command untraced first: its line is what the trace's averages must reproduce (the
 # tracer adds ~4 us to every dispatch-packet interval the bench itself measures under it)
 timeout -k 10 300 $B > $OUT/untraced.log 2>&1 || { echo "untraced bench failed"; tail -20 $OUT/untraced.log; exit 1; }
