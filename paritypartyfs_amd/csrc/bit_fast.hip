@@ -5,7 +5,7 @@
 // One wave per block, NP = block_size / 1024 pieces of 16 B per lane, coalesced: lane l of a wave
 // holds raw bytes [16 (64 k + l), +16) for k < NP, i.e. big-endian raw words w = 256 k + 4 l + u.
 // The grid covers the batch (one wave per block, workgroups dispatched in address order); see
-// BF_PREFETCH below.  Smaller blocks use bit_kernels.hip.
+// "Grid and prefetch" (BF_BPW) below.  Smaller blocks use bit_kernels.hip.
 //
 // Reference semantics (lib/blockdevice/src/hamming_block_device.cpp, MSB-first bit numbering of
 // lib/common/include/ppfs/common/bit_helpers.hpp:8-52):
@@ -1120,7 +1120,7 @@ __global__ __launch_bounds__(64 * WV) PPFS_CRC_ATTR void crc_fast_check_kernel(c
 
 using namespace ppfs;
 
-// Full grid: one wave per block, WV blocks per workgroup of WV waves (see BF_PREFETCH above); the
+// Full grid: one wave per block, WV blocks per workgroup of WV waves (see "Grid and prefetch", BF_BPW, above); the
 // entry points refuse batches whose grid would pass 2^30 workgroups.
 template <typename K> static uint32_t bf_grid(K, uint64_t nb, int wv = bf::WAVES)
 {
@@ -1280,7 +1280,7 @@ extern "C" hipError_t ppfs_ham_fast_decode(uint8_t* r, uint8_t* d, uint8_t* st, 
     return hipGetLastError();
 }
 
-// The table blob's layout for the host builder (api.cpp build_crc_fast_tables), in this order:
+// The table blob's layout for the host builder (host_tables.hpp build_crc_fast_tables), in this order:
 // map bytes, maps, lane-map offset, lane maps, 6-bit offset, 6-bit maps, 6-bit map bytes, 8-bit
 // offset, 8-bit maps, 8-bit map bytes, total bytes
 extern "C" int ppfs_crc_fast_layout(int32_t* v, int n)

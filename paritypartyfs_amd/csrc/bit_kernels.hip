@@ -137,7 +137,7 @@ __device__ __forceinline__ uint32_t wave_add32(uint32_t v)
 
 // ------------------------------------------------------------------------------------
 // CRC
-// Tables (built on the host, api.cpp): PT[64 pos][2 nibble][16] u64 =
+// Tables (built on the host, host_tables.hpp): PT[64 pos][2 nibble][16] u64 =
 //   (v << 4h) * x^(8(63-pos) + n - 8z - 1) mod P   (z = 64*G - ds zero bytes appended)
 // and LV[6 level][16 nibble][16] u64 = (v << 4k) * x^(512 * 2^level) mod P.
 // Lane s owns payload bytes [64s, 64s+64) (zero past ds); its contribution is shifted by
@@ -935,7 +935,7 @@ extern "C" hipError_t ppfs_parity_check(const uint8_t* r, uint8_t* d, uint8_t* s
     return hipGetLastError();
 }
 
-// resident small-batch server for CRC / Hamming / parity contexts (api.cpp server_call)
+// resident small-batch server for CRC / Hamming / parity contexts (host_path.cpp server_call)
 extern "C" hipError_t ppfs_bit_server_launch(int ecc_type, uint32_t bs, uint32_t ds, uint32_t crc_n, uint64_t crc_mask,
     uint32_t ham_L, SrvBox* box, uint8_t* zc, uint64_t zc_bytes, const uint8_t* tab, uint32_t gen, uint32_t idle_us,
     hipStream_t s)

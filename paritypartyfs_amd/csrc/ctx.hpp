@@ -1,0 +1,177 @@
+// ctx.hpp -- the engine context and what api.cpp (create / destroy, the device entry points, scrub,
+// vote, groups) and host_path.cpp (the host-memory entry points) share.  Everything declared in
+// namespace ppfs here has hidden visibility: the library exports the C ABI of include/ppfs_ecc.h
+// and the kernel launchers, nothing of this.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+
+#include "../../include/ppfs_ecc.h"
+#include "server_box.hpp"
+
+#pragma GCC visibility push(hidden)
+namespace ppfs {
+
+// the calling thread's last error message (ppfs_ecc_last_error); fail() sets it and returns code
+extern thread_local std::string g_last_error;
+int fail(int code, const char* what, hipError_t e = hipSuccess);
+inline int check_hip(hipError_t e, const char* what) { return e != hipSuccess ? fail(PPFS_ECC_EHIP, what, e) : 0; }
+
+// Runs a scope on a context's device and restores the caller's current device afterwards
+// (the HIP runtime may be shared with the caller's framework, e.g. torch's current device).
+struct DeviceGuard {
+    int prev = -1;
+    hipError_t err = hipSuccess;
+    explicit DeviceGuard(int dev)
+    {
+        if (hipGetDevice(&prev) != hipSuccess)
+            prev = -1;
+        if (prev != dev)
+            err = hipSetDevice(dev);
+    }
+    ~DeviceGuard()
+    {
+        if (prev >= 0)
+            (void)hipSetDevice(prev);
+    }
+};
+
+#define HIP_TRY(expr, what)                                                                                            \
+    do {                                                                                                               \
+        hipError_t _e = (expr);                                                                                        \
+        if (_e != hipSuccess)                                                                                          \
+            return ppfs::fail(PPFS_ECC_EHIP, what, _e);                                                                      \
+    } while (0)
+
+} // namespace ppfs
+#pragma GCC visibility pop
+
+// ---------------------------------------------------------------------------------------
+// Context
+// ---------------------------------------------------------------------------------------
+struct ppfs_ecc_ctx {
+    ppfs_ecc_params p {};
+    int device = 0;
+    // derived
+    uint32_t raw = 0, data = 0;
+    int rs_n = 0, rs_t2 = 0;
+    bool rs_fast = false;
+    int crc_n = 0;
+    uint64_t crc_mask = 0;
+    uint32_t ham_L = 0;
+    const char* kname = "";
+    // device tables
+    uint8_t* d_tables = nullptr;
+    // ticket counters of the dynamic-tile t <= 4 encode and decode (rs_wg_tk.hpp): per stream that
+    // runs them through this context a slot of two 2,560-byte sets (launch parity), each an encode
+    // half then a decode half.  A launch counts on one set and zeroes the other, which the previous
+    // launch of the same kind on the stream used (launches on one stream are ordered; no two streams
+    // share a slot); tk_par = the set the next launch of each kind uses.  Further streams use the
+    // static walk.
+    // Ordering (round 4): a slot remembers the caller-stream event slot (ev[] below) of the stream
+    // that last launched on it; a slot passes to another stream only once that event has completed,
+    // and every device call first waits for the previous call's event on its stream handle, so a
+    // stream created at a destroyed stream's address never runs beside a kernel still counting on
+    // the old stream's set.
+    static constexpr int kTkSlots = 16, kTkSetWords = 1024; // encode 512 words (rs_wq: 32 counters 64 B apart), decode 512
+    uint32_t* d_ctr = nullptr;
+    hipStream_t tk_stream[kTkSlots] = {};
+    uint8_t tk_par[kTkSlots][2] = {};
+    int tk_ev[kTkSlots] = {}; // ev[] slot of the slot's last user
+    int tk_n = 0;
+    // scratch for write_device status when the caller passes none
+    uint8_t* d_scratch = nullptr;
+    size_t scratch_bytes = 0;
+    // host staging (round 5): a stream per link direction, so that chunk i + 1's H2D runs beside
+    // chunk i's D2H (with a stream per slot the slots fell into lockstep: both H2Ds, then both
+    // D2Hs, one link direction idle at a time); an event per slot orders its kernel after its H2D.
+    // hs[0]: H2D copies (SDMA), the small-batch path and decode write-back fix-ups; hs[1]: kernels
+    // and D2H copies (the runtime's D2H into page-locked memory is a blit kernel anyway).  Two, not
+    // one per stage: a process gets few hardware queues (GPU_MAX_HW_QUEUES, 4 by default) and
+    // streams beyond them share queues with torch's -- measured: 4 streams ran slower in bench.py's
+    // process than in a torch-free one
+    static constexpr int kSlots = 3, kHostStreams = 2;
+    hipStream_t hs[kHostStreams] = {};
+    hipEvent_t hev[kSlots][2] = {}; // per slot: inputs landed, outputs landed
+    uint8_t* h_pin[kSlots] = {};
+    uint8_t* d_stage[kSlots] = {};
+    size_t stage_bytes = 0;
+    bool host_eager = false; // the last chunked decode's write-back predictor, where the next one starts
+    // zero-copy staging for small host batches (the per-block IBlockDevice calls): coherent
+    // host memory the kernels read and write in place, no H2D / D2H
+    uint8_t* h_zc = nullptr;
+    uint8_t* d_zc = nullptr;
+    size_t zc_bytes = 0;
+    // resident small-batch server (RS 2t <= 8, server_box.hpp): mailbox, its stream, the current
+    // launch generation, the last request number; srv_ok = -1 undecided, 0 off, 1 on
+    ppfs::SrvBox* h_box = nullptr;
+    ppfs::SrvBox* d_box = nullptr;
+    hipStream_t srv_stream = nullptr;
+    uint32_t srv_gen = 0, srv_seq = 0, flag_seq = 0;
+    bool srv_launched = false;
+    int srv_ok = -1;
+    // a resident launch that did not leave when asked (server_stop): the context is unusable and
+    // destroy leaks what the launch may still read instead of freeing it under it
+    bool srv_stuck = false;
+    // Completion of the work this context queued on CALLER streams (the device entry points):
+    // one fence-free event per stream, re-recorded after every call, so that destroy waits for
+    // exactly that work (it reads the tables, counters and scratch destroy frees) and not for the
+    // whole device -- other contexts' resident servers, unrelated torch streams.  A stream beyond
+    // kEvSlots sets ev_overflow and destroy falls back to a device-wide synchronize.
+    static constexpr int kEvSlots = 32;
+    hipStream_t ev_stream[kEvSlots] = {};
+    hipEvent_t ev[kEvSlots] = {};
+    bool ev_rec[kEvSlots] = {}; // recorded at least once
+    int ev_n = 0;
+    bool ev_overflow = false;
+    // the context's own stream for its stream-ordered device allocations (mem_alloc / mem_free)
+    hipStream_t ms = nullptr;
+    size_t pin_bytes = 0; // bytes of each h_pin[] buffer (pin cache key)
+};
+
+#pragma GCC visibility push(hidden)
+namespace ppfs {
+
+// PPFS_ECC_TRACE=1 (diagnostics): timestamped steps of context creation on stderr (api.cpp)
+void trace_step(const char* what);
+
+// Memory that never synchronizes the device when it is freed (api.cpp): stream-ordered device
+// memory on the context's own stream, page-locked host buffers from a process-wide cache.
+hipError_t mem_alloc(ppfs_ecc_ctx* c, void** p, size_t n);
+void mem_free(ppfs_ecc_ctx* c, void* p); // caller: nothing still queued reads p
+hipError_t pin_alloc(void** p, size_t n, unsigned flags);
+void pin_free(void* p, size_t n, unsigned flags); // caller: nothing still queued reads or writes p
+constexpr unsigned kPinStage = hipHostMallocDefault, kPinMapped = hipHostMallocMapped | hipHostMallocCoherent;
+#ifdef PPFS_ECC_DEBUG
+bool pool_covers(const void* p, size_t n); // [p, p + n) inside one of the engine's pool allocations
+#endif
+
+// every copy the engine queues (checked in PPFS_ECC_DEBUG builds), and the page-locked test of a
+// caller's host range (host_path.cpp)
+hipError_t dma_async(void* dst, const void* src, size_t n, hipMemcpyKind kind, hipStream_t s);
+bool host_pinned(const void* p, size_t bytes);
+
+// Ask the resident server launch to leave and wait for it, at most kSrvStopMs; false = it did not
+// leave (host_path.cpp)
+constexpr int kSrvStopMs = 2000;
+bool server_halt(ppfs_ecc_ctx* c);
+
+// The RS(255, 255 - 2t), 2t <= 8 decodes (rs_wg_tk.hpp / rs_wg.hpp) can put their write-backs
+// somewhere other than the codewords they read: the host path points them at a page-locked caller
+// image mapped into the device, so a chunk's corrections land there with no codeword copy and no
+// patch pass (round 6)
+inline bool rs_wb_direct(const ppfs_ecc_ctx* c)
+{
+    return c->p.ecc_type == PPFS_ECC_REED_SOLOMON && c->rs_fast && c->rs_n == 255 && c->rs_t2 <= 8;
+}
+// ppfs_ecc_decode_device with the write-backs going to wb_dst instead of into d_raw (rs_wb_direct
+// contexts only; nullptr: into d_raw) (api.cpp)
+int decode_device_to(ppfs_ecc_ctx* c, uint8_t* d_raw, uint8_t* d_data, uint8_t* d_status, size_t nblocks, int write_back,
+    uint8_t* d_spill, void* stream, uint8_t* wb_dst);
+
+} // namespace ppfs
+#pragma GCC visibility pop

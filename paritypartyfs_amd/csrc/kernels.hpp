@@ -1,0 +1,52 @@
+// kernels.hpp -- the host-callable launchers of the kernel translation units, declared once:
+// rs_kernels.hip (Reed-Solomon and its servers), bit_kernels.hip (CRC, Hamming, parity and the bit
+// server) and vote.hip (vote, copy, gather, patch list, inject, flag).  The
+// three table-sizing functions are in host_tables.hpp, beside the builders that use them.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "server_box.hpp"
+
+extern "C" {
+int ppfs_rs_fast_supported(int n, int t2);
+hipError_t ppfs_rs_fast_encode(int t2, const uint8_t* d, uint8_t* r, uint64_t nb, const uint8_t* tab, hipStream_t s,
+    uint32_t* ctr, uint32_t* ctr_clear);
+const char* ppfs_rs_fast_path(int t2);
+hipError_t ppfs_flag_launch(uint32_t* flag, uint32_t v, hipStream_t s);
+hipError_t ppfs_rs_generic_server_launch(int n, int t2, ppfs::SrvBox* box, uint8_t* zc, uint64_t zc_bytes,
+    const uint8_t* tab, uint32_t gen, uint32_t idle_us, hipStream_t s);
+hipError_t ppfs_bit_server_launch(int ecc_type, uint32_t bs, uint32_t ds, uint32_t crc_n, uint64_t crc_mask, uint32_t ham_L,
+    ppfs::SrvBox* box, uint8_t* zc, uint64_t zc_bytes, const uint8_t* tab, uint32_t gen, uint32_t idle_us, hipStream_t s);
+hipError_t ppfs_rs_server_launch(int t2, ppfs::SrvBox* box, uint8_t* zc, uint64_t zc_bytes, const uint8_t* tab,
+    uint32_t gen, uint32_t idle_us, hipStream_t s);
+hipError_t ppfs_rs_fast_decode(int t2, uint8_t* r, uint8_t* d, uint8_t* st, uint64_t nb, const uint8_t* tab, int wb,
+    hipStream_t s, uint32_t* ctr, uint32_t* ctr_clear, uint8_t* wb_dst);
+hipError_t ppfs_rs_generic_encode(const uint8_t* d, uint8_t* r, uint64_t nb, int n, int t2, const uint8_t* tab,
+    hipStream_t s);
+hipError_t ppfs_rs_generic_decode(uint8_t* r, uint8_t* d, uint8_t* st, uint8_t* spill, uint64_t nb, int n, int t2,
+    int wb, const uint8_t* tab, hipStream_t s);
+int ppfs_crc_fast_supported(uint32_t bs, uint32_t n);
+int ppfs_bitfast_supported(uint32_t bs);
+hipError_t ppfs_crc_encode(const uint8_t* d, uint8_t* r, const uint8_t* skip, uint64_t nb, uint32_t bs, uint32_t ds,
+    uint32_t n, uint64_t mask, const uint8_t* tab, hipStream_t s);
+hipError_t ppfs_crc_check(const uint8_t* r, uint8_t* d, uint8_t* st, uint64_t nb, uint32_t bs, uint32_t ds, uint32_t n,
+    uint64_t mask, const uint8_t* tab, hipStream_t s);
+hipError_t ppfs_ham_encode(const uint8_t* d, uint8_t* r, const uint8_t* skip, uint64_t nb, uint32_t bs, uint32_t ds,
+    uint32_t L, hipStream_t s);
+hipError_t ppfs_ham_decode(uint8_t* r, uint8_t* d, uint8_t* st, uint64_t nb, int wb, uint32_t bs, uint32_t ds,
+    uint32_t L, hipStream_t s);
+hipError_t ppfs_parity_encode(const uint8_t* d, uint8_t* r, const uint8_t* skip, uint64_t nb, uint32_t bs,
+    hipStream_t s);
+hipError_t ppfs_parity_check(const uint8_t* r, uint8_t* d, uint8_t* st, uint64_t nb, uint32_t bs, hipStream_t s);
+hipError_t ppfs_gather_rows_launch(const uint8_t* src, uint64_t src_rows, uint8_t* dst, const uint32_t* idx, uint32_t nrows,
+    uint32_t row_bytes, hipStream_t s);
+hipError_t ppfs_vote3_launch(const uint8_t* a, const uint8_t* b, const uint8_t* c, uint8_t* out, uint64_t rec_bytes,
+    uint64_t nrec, uint32_t* damaged, hipStream_t s);
+hipError_t ppfs_copy_launch(uint8_t* dst, const uint8_t* src, uint64_t bytes, hipStream_t s);
+hipError_t ppfs_patch_list_launch(const uint8_t* cur, const uint8_t* orig, const uint8_t* status, uint32_t n, uint64_t nb,
+    uint32_t S, uint32_t* patch, uint8_t* image, hipStream_t s);
+hipError_t ppfs_inject_launch(uint8_t* raw, uint64_t stride, uint64_t nblocks, const uint8_t* pos, const uint8_t* val,
+    int mode, hipStream_t s);
+}

@@ -115,7 +115,7 @@ extern "C" const char* PPFS_CAT(ppfs_rs_fast_path_t, PPFS_T2)()
 #endif
 }
 
-// wb_dst: where the write-backs go (null: the codewords in place; 2t <= 8 only: api.cpp's host path
+// wb_dst: where the write-backs go (null: the codewords in place; 2t <= 8 only: host_path.cpp's chunk pipeline
 // passes the page-locked caller image, mapped into the device)
 extern "C" hipError_t PPFS_CAT(ppfs_rs_fast_decode_t, PPFS_T2)(uint8_t* r, uint8_t* d, uint8_t* st, uint64_t nb,
     const uint8_t* tab, int wb, hipStream_t s, [[maybe_unused]] uint32_t* ctr, [[maybe_unused]] uint32_t* ctr_clear,
@@ -143,7 +143,7 @@ extern "C" hipError_t PPFS_CAT(ppfs_rs_fast_decode_t, PPFS_T2)(uint8_t* r, uint8
 }
 PPFS_DBG_ACCESSOR(PPFS_CAT(ppfs_dbg_faults_rs_t, PPFS_T2))
 
-// resident small-batch servers (api.cpp server_call): 2t <= 8 rs_wg.hpp rs_wg_server_kernel,
+// resident small-batch servers (host_path.cpp server_call): 2t <= 8 rs_wg.hpp rs_wg_server_kernel,
 // 8 < 2t <= 16 rs_fast.hpp rs255_server_kernel, 2t = 32 rs_pair.hpp rs_pair_server_kernel
 extern "C" hipError_t PPFS_CAT(ppfs_rs_server_launch_t, PPFS_T2)(ppfs::SrvBox* box, uint8_t* zc, uint64_t zc_bytes,
     const uint8_t* tab, uint32_t gen, uint32_t idle_us, hipStream_t s)

@@ -1,6 +1,6 @@
 #pragma once
 // rs_layout.hpp -- table layout of the workgroup-cooperative RS(255, 255-2t) kernels (rs_wg.hpp),
-// shared by the host table builder (api.cpp) and the device code.  2t <= 8 (t <= 4), so a
+// shared by the host table builder (host_tables.hpp) and the device code.  2t <= 8 (t <= 4), so a
 // remainder fits one 8-byte entry, stored top-aligned: coefficient q of x^q at byte 8 - 2t + q.
 //
 // Every table is a set of nibble tables: 16 entries of 8 bytes (one 128-byte table), indexed by

@@ -1,6 +1,6 @@
 #pragma once
 // server_box.hpp -- mailbox of the resident small-batch server (rs_wg.hpp rs_wg_server_kernel,
-// api.cpp server_call).  One per engine context, in host-coherent memory mapped to the device.
+// host_path.cpp server_call).  One per engine context, in host-coherent memory mapped to the device.
 //
 // Protocol.  The host writes the request's input bytes into the context's zero-copy buffer (the
 // srv_layout offsets) and then the whole request as ONE 32-bit word, `cmd` (release store):
@@ -40,7 +40,7 @@ inline constexpr SrvCmd srv_cmd_unpack(uint32_t w)
     return SrvCmd { w & 0x7Fu, (w >> 12) & 3u, ((w >> 14) & 1u) != 0, ((w >> 15) & 1u) != 0 };
 }
 
-// offsets of a request's buffers in the zero-copy buffer (api.cpp layout_for: same 256-byte rounding)
+// offsets of a request's buffers in the zero-copy buffer (host_plan.hpp layout_for: same 256-byte rounding)
 struct SrvLayout {
     uint32_t data, raw, status;
 };
@@ -57,7 +57,7 @@ struct alignas(64) SrvBox {
     uint32_t done;   // device -> host: the last cmd served
     uint32_t alive;  // device -> host: generation (| SRV_EXITED after return)
     uint64_t served; // requests served by this launch (diagnostics)
-    uint32_t flag;   // device -> host: completion of the launch path (api.cpp wait_flag)
+    uint32_t flag;   // device -> host: completion of the launch path (host_path.cpp wait_flag)
     uint32_t pad1[11];
 };
 static_assert(sizeof(SrvBox) == 128, "mailbox layout: one request line, one reply line");

@@ -47,7 +47,7 @@ extern "C" hipError_t ppfs_vote3_launch(const uint8_t* a, const uint8_t* b, cons
     return hipGetLastError();
 }
 
-// ---- gather of the rows a host decode has to return (api.cpp host_run) ----
+// ---- gather of the rows a host decode has to return (host_path.cpp gather_rows_back) ----
 // dst row i = src row idx[i] (row_bytes each): the codewords a decode with write-back changed
 // (status 1), packed for one D2H copy when they are few.  One workgroup per row, 16-byte pieces
 // where source and destination are 16-byte aligned, else bytes.
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const uint8_t* __restr
 }
 } // namespace ppfs
 
-// ---- patch list of a decode's write-back (api.cpp host_run_chunks) ----
+// ---- patch list of a decode's write-back (host_path.cpp ChunkPipeline) ----
 // The bytes a decode with write-back changed, for the host to patch into its image instead of
 // copying every changed codeword back: block b with status[b] == 1 gets (pos << 8 | byte) for each
 // byte where cur differs from orig (the codeword before the decode) in patch[b S .. b S + S - 1],
@@ -230,7 +230,7 @@ extern "C" hipError_t ppfs_inject_launch(uint8_t* raw, uint64_t stride, uint64_t
     return hipGetLastError();
 }
 
-// Completion flag of the small-batch launch path (api.cpp wait_flag): queued after a call's
+// Completion flag of the small-batch launch path (host_path.cpp wait_flag): queued after a call's
 // kernels on the same stream, it makes their outputs visible system-wide and stores `v` (release)
 // into host-coherent memory, where the host spins on it.  Cheaper than hipStreamSynchronize's
 // completion signal (measured 6.4 vs 10.3 us for one empty kernel, tools/probes/latency_probe.cpp).

@@ -3,7 +3,7 @@
 - the Python mirror rejects buffers shorter than a call touches, and buffers of the wrong kind,
   before anything reaches the C ABI (an undersized host array would overflow the heap, an
   undersized tensor would be written out of bounds in HBM);
-- a host buffer that is only partly page-locked is not DMA'd directly (api.cpp host_pinned checks
+- a host buffer that is only partly page-locked is not DMA'd directly (host_path.cpp host_pinned checks
   the whole range) and still gives the oracle's results;
 - destroying a context right after queueing device work on the caller's stream is safe: the
   context's tables stay alive until that work is done (ppfs_ecc_destroy drains first);

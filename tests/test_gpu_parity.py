@@ -6,6 +6,7 @@ shortened codes).  Edge cases follow the reference tests: 0..t+3 byte errors for
 (miscorrection included), 0..3 bit flips for Hamming (parity, data and unused tail bits),
 CRC flips including the undetected last payload bit, ragged batch sizes.
 """
+import contextlib
 import zlib
 
 import numpy as np
@@ -496,11 +497,25 @@ def test_write_rmw_matches_oracle(oracle, codec):
 # ------------------------------------------------------------------------------------
 # host-memory path (pinned staging, several chunks)
 # ------------------------------------------------------------------------------------
-@pytest.mark.parametrize("chunks", [4, 8], ids=["5chunks", "ramp"])
-def test_host_path_multichunk(oracle, chunks):
+def _locked(kind, *arrays):
+    """The arrays page-locked for the block (kind "pinned"), or left pageable."""
+    from paritypartyfs_amd import pinned
+
+    return pinned(*arrays) if kind == "pinned" else contextlib.nullcontext()
+
+
+@pytest.mark.parametrize("codec,chunks,kind", [("rs512", 4, "pageable"), ("rs512", 8, "pageable"), ("rs512", 4, "pinned"),
+                                               ("rs512", 8, "pinned"), ("ham4096", 8, "pageable"), ("ham4096", 8, "pinned")],
+                         ids=["5chunks", "ramp", "5chunks-pinned", "ramp-pinned", "ham4096-ramp", "ham4096-ramp-pinned"])
+def test_host_path_multichunk(oracle, codec, chunks, kind):
     # 4 chunks of ppfs_ecc_host_chunk_blocks (64 Ki RS(255,249) blocks) and a ragged one: every
-    # staging slot is reused at least once; 8+ chunks: the ramped chunk sizes (api.cpp ramp_chunk:
-    # 8 Ki, 16 Ki, 32 Ki, 64 Ki ... halving tail).  The 1-error decode returns patch lists.
+    # staging slot is reused at least once; 8+ chunks: the ramped chunk sizes (host_plan.hpp
+    # ramp_chunk: 8 Ki, 16 Ki, 32 Ki, 64 Ki ... halving tail; 8 chunks is the shortest call that
+    # ramps).  The 1-error decode returns patch lists; with page-locked caller buffers every ramped
+    # offset goes by direct DMA and the write-back straight into the caller's image (RS: from the
+    # decode kernel, Hamming: from the patch kernel).
+    if codec == "ham4096":
+        return _multichunk_hamming(oracle, chunks, kind)
     bs, t = 512, 3
     n, k, _ = oracle.rs_sizes(bs, t)
     eng = EccEngine(ECC_REED_SOLOMON, bs, t)
@@ -509,7 +524,8 @@ def test_host_path_multichunk(oracle, chunks):
     rng = rng_for("host")
     data = rng.integers(0, 256, nb * k, dtype=np.uint8)
     raw = np.zeros(nb * n, np.uint8)
-    eng.encode_host(data, raw)
+    with _locked(kind, data, raw):
+        eng.encode_host(data, raw)
     sample = rng.choice(nb, 2000, replace=False)
     ref = oracle.rs_encode(bs, t, data.reshape(nb, k)[sample].reshape(-1)).reshape(-1, n)
     assert np.array_equal(raw.reshape(nb, n)[sample], ref)
@@ -518,10 +534,51 @@ def test_host_path_multichunk(oracle, chunks):
     bad = bad.reshape(-1)
     out = np.zeros(nb * k, np.uint8)
     st = np.zeros(nb, np.uint8)
-    eng.decode_host(bad, out, st, write_back=True)
+    with _locked(kind, bad, out, st):
+        eng.decode_host(bad, out, st, write_back=True)
     assert (st == 1).all()
     assert np.array_equal(out, data)
     assert np.array_equal(bad, raw)
+
+
+def _multichunk_hamming(oracle, chunks, kind):
+    # Hamming, 4 KiB blocks: 4 Ki blocks a chunk.  Single-bit flips in every block of the second
+    # chunk's range (the predictor turns eager), in 100 blocks elsewhere and in 9 of the tail; the
+    # oracle decodes every block that was hit, the others must come back clean and untouched.
+    bs = 4096
+    eng = EccEngine(ECC_HAMMING, bs, 0)
+    ch = eng.host_chunk_blocks()
+    assert ch == 4096
+    nb = chunks * ch + 777
+    n, k = eng.raw_block_size, eng.data_size
+    rng = rng_for("host", "ham")
+    data = rng.integers(0, 256, nb * k, dtype=np.uint8)
+    raw = np.zeros(nb * n, np.uint8)
+    with _locked(kind, data, raw):
+        eng.encode_host(data, raw)
+    sample = rng.choice(nb, 300, replace=False)
+    ref = oracle.ham_encode(bs, data.reshape(nb, k)[sample].reshape(-1)).reshape(-1, n)
+    assert np.array_equal(raw.reshape(nb, n)[sample], ref)
+    hit = np.unique(np.concatenate([ch + np.arange(ch), rng.choice(nb - 777, 100, replace=False),
+                                    nb - 777 + rng.choice(777, 9, replace=False)]))
+    bad = raw.reshape(nb, n).copy()
+    pos = rng.integers(0, 8 * n, hit.size)
+    bad[hit, pos // 8] ^= (0x80 >> (pos % 8)).astype(np.uint8)
+    h_data, h_st, h_fixed, _ = oracle.ham_decode(bs, bad[hit].reshape(-1))
+    o_st = np.zeros(nb, np.uint8)
+    o_st[hit] = h_st
+    o_fixed = bad.copy()
+    o_fixed[hit] = h_fixed.reshape(-1, n)
+    o_data = data.reshape(nb, k).copy()
+    o_data[hit] = h_data.reshape(-1, k)
+    img = bad.reshape(-1)
+    out = np.zeros(nb * k, np.uint8)
+    st = np.full(nb, 77, np.uint8)
+    with _locked(kind, img, out, st):
+        eng.decode_host(img, out, st, write_back=True)
+    assert np.array_equal(st, o_st)
+    assert np.array_equal(img, o_fixed.reshape(-1))
+    assert np.array_equal(out, o_data.reshape(-1))
 
 
 @pytest.mark.parametrize("typ,bs,t,poly", [(ECC_REED_SOLOMON, 512, 3, 0), (ECC_REED_SOLOMON, 64, 3, 0),
@@ -529,9 +586,10 @@ def test_host_path_multichunk(oracle, chunks):
                          ids=["rs512", "rs64", "ham4096", "crc4096"])
 def test_host_path_pinned_equals_pageable(typ, bs, t, poly):
     """Page-locked caller buffers (ppfs_ecc_host_register) take the direct-DMA path of the host
-    calls; results must be byte-identical to the staged (pageable) path, across chunks."""
-    from paritypartyfs_amd import pinned
-
+    calls; results must be byte-identical to the staged (pageable) path, across chunks -- the spill
+    records too: a shortened RS code's, zeros from RS(255, k) (also where the decode kernel writes
+    straight into the page-locked image), and for the codecs that write none the same untouched
+    staging bytes."""
     eng = EccEngine(typ, bs, t, crc_polynomial_explicit=poly)
     n, k = eng.raw_block_size, eng.data_size
     nb = 70001 if bs <= 512 else 3001
@@ -543,20 +601,16 @@ def test_host_path_pinned_equals_pageable(typ, bs, t, poly):
         d = data.copy()
         out = np.zeros(nb * k, np.uint8)
         st = np.full(nb, 77, np.uint8)
-        sp = np.zeros(nb * eng.spill_bytes_per_block(), np.uint8)
-        ctx = pinned(d, raw, out, st, sp) if kind == "pinned" else None
-        if ctx:
-            ctx.__enter__()
-        try:
+        sp = np.full(nb * eng.spill_bytes_per_block(), 0xAA, np.uint8)
+        with _locked(kind, d, raw, out, st, sp):
             eng.encode_host(d, raw)
             r2 = np.random.default_rng(5)
             pos = r2.integers(0, n, nb) + np.arange(nb) * n
             raw[pos] ^= r2.integers(1, 256, nb, dtype=np.uint8)
-            eng.decode_host(raw, out, st, write_back=True, spill=sp if bs < 255 else None)
-        finally:
-            if ctx:
-                ctx.__exit__(None, None, None)
-        outs.append((raw, out, st))
+            eng.decode_host(raw, out, st, write_back=True, spill=sp)
+        if typ == ECC_REED_SOLOMON and n == 255:
+            assert not sp.any()
+        outs.append((raw, out, st, sp))
     for a, b in zip(*outs):
         assert np.array_equal(a, b)
 
@@ -571,7 +625,7 @@ def test_host_decode_returns_only_changed_codewords(oracle, kind, codec, prior):
     (ppfs_ecc_host_chunk_blocks): clean / 100 errors / every block / 5,000 blocks / a short tail;
     every path must leave the caller's image equal to the oracle's write-back.  prior="eager": the
     context's previous call ended on a chunk where every block changed, so this call's first chunks
-    (queued before any has landed: api.cpp host_run_chunks, three staging slots) fetch their
+    (queued before any has landed: host_path.cpp ChunkPipeline, three staging slots) fetch their
     codewords eagerly."""
     from paritypartyfs_amd import pinned
 

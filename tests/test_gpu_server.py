@@ -1,4 +1,4 @@
-"""GPU tests of the resident small-batch server (api.cpp server_call, rs_wg.hpp rs_wg_server_kernel):
+"""GPU tests of the resident small-batch server (host_path.cpp server_call, rs_wg.hpp rs_wg_server_kernel):
 the per-block readBlock / writeBlock calls of every codec (batches of <= 64 blocks through
 the host entry points) are served by one resident workgroup polling a mailbox in host-coherent
 memory.  Every result is compared with the oracle (rs_block_device.cpp semantics: payload,

@@ -3,7 +3,7 @@
 // variant's payload output is checked against the original data.
 // hipcc --offload-arch=gfx950 -O3 -std=c++17 -I paritypartyfs_amd/csrc -I include \
 //     tools/probes/rs_ablate_dec.hip -o tools/rs_ablate_dec.bin
-#include "../paritypartyfs_amd/csrc/api.cpp" // host table builders (same TU: anonymous namespace)
+#include "host_tables.hpp" // host table builders; their sizing functions come from the engine library
 #include "rs_fast.hpp"
 
 #include <algorithm>
@@ -11,23 +11,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-
-// the rs_fast launchers api.cpp declares are not linked here; provide what api.cpp references
-extern "C" {
-int ppfs_rs_fast_supported(int, int) { return 0; }
-int ppfs_rs_fast_tables_bytes(int t2) { return t2 <= 16 ? 4096 : 8192; }
-hipError_t ppfs_rs_fast_encode(int, const uint8_t*, uint8_t*, uint64_t, const uint8_t*, hipStream_t) { return hipErrorInvalidValue; }
-hipError_t ppfs_rs_fast_decode(int, uint8_t*, uint8_t*, uint8_t*, uint64_t, const uint8_t*, int, hipStream_t) { return hipErrorInvalidValue; }
-hipError_t ppfs_rs_generic_encode(const uint8_t*, uint8_t*, uint64_t, int, int, const uint8_t*, hipStream_t) { return hipErrorInvalidValue; }
-hipError_t ppfs_rs_generic_decode(uint8_t*, uint8_t*, uint8_t*, uint8_t*, uint64_t, int, int, int, const uint8_t*, hipStream_t) { return hipErrorInvalidValue; }
-int ppfs_crc_tables_bytes(void) { return 0; }
-hipError_t ppfs_crc_encode(const uint8_t*, uint8_t*, const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint64_t, const uint8_t*, hipStream_t) { return hipErrorInvalidValue; }
-hipError_t ppfs_crc_check(const uint8_t*, uint8_t*, uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint64_t, const uint8_t*, hipStream_t) { return hipErrorInvalidValue; }
-hipError_t ppfs_ham_encode(const uint8_t*, uint8_t*, const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, hipStream_t) { return hipErrorInvalidValue; }
-hipError_t ppfs_ham_decode(uint8_t*, uint8_t*, uint8_t*, uint64_t, int, uint32_t, uint32_t, uint32_t, hipStream_t) { return hipErrorInvalidValue; }
-hipError_t ppfs_parity_encode(const uint8_t*, uint8_t*, const uint8_t*, uint64_t, uint32_t, hipStream_t) { return hipErrorInvalidValue; }
-hipError_t ppfs_parity_check(const uint8_t*, uint8_t*, uint8_t*, uint64_t, uint32_t, hipStream_t) { return hipErrorInvalidValue; }
-}
 
 using namespace ppfs;
 

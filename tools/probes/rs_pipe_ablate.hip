@@ -2,7 +2,7 @@
 // per block -> decode with write-back, 2^20 RS(255,249) blocks) with the kernels' phases switched
 // off (MODE 0 = same bytes moved, no compute), to see what the memory system allows in THIS
 // sequence (each kernel inherits the previous one's dirty lines and cache state).
-#include "../paritypartyfs_amd/csrc/api.cpp" // host table builders (same TU)
+#include "host_tables.hpp" // host table builders
 #include "rs_wg.hpp"
 
 #include <algorithm>

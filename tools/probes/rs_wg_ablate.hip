@@ -1,7 +1,7 @@
 // rs_wg_ablate.hip -- diagnostic build (not shipped): the workgroup RS(255,249) kernels with phases
 // switched off (MODE bits) and at several grid sizes, 2^20 blocks, 1 byte error per block for
 // decode.  Median of 5 rounds of 10 back-to-back launches.
-#include "../paritypartyfs_amd/csrc/api.cpp" // host table builders (same TU)
+#include "host_tables.hpp" // host table builders
 #include "rs_wg.hpp"
 
 #include <algorithm>
