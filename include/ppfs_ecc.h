@@ -29,7 +29,8 @@
  *     H2D / kernel / D2H, and return after the results are in host memory.
  *   - Per-block status bytes use FsError values (lib/common/include/ppfs/common/types.hpp):
  *       PPFS_ECC_OK (0), PPFS_ECC_CORRECTED (1: the reference writes the block back and logs
- *       an ErrorCorrectionEvent), PPFS_ECC_CORRECTION_ERROR (5 = BlockDevice_CorrectionError).
+ *       an ErrorCorrectionEvent), PPFS_ECC_CORRECTION_ERROR (5 = BlockDevice_CorrectionError),
+ *       PPFS_ECC_OUT_OF_BOUNDS (9 = Disk_OutOfBounds, block-list calls only).
  *   - One context per (host thread, GPU); a context is not internally locked.
  */
 #ifndef PPFS_ECC_H
@@ -54,7 +55,8 @@ enum ppfs_ecc_type {
 enum ppfs_ecc_status {
     PPFS_ECC_OK = 0,
     PPFS_ECC_CORRECTED = 1,
-    PPFS_ECC_CORRECTION_ERROR = 5
+    PPFS_ECC_CORRECTION_ERROR = 5,
+    PPFS_ECC_OUT_OF_BOUNDS = 9 /* FsError::Disk_OutOfBounds: a block-list entry past the image */
 };
 
 /* Error codes returned by the entry points. */
@@ -141,6 +143,58 @@ int ppfs_ecc_write_host(ppfs_ecc_ctx* ctx, const uint8_t* data, uint8_t* raw, ui
  * patch list that the host writes into raw; other codecs return the changed codewords whole.
  * Engine extension, no reference counterpart. */
 size_t ppfs_ecc_host_chunk_blocks(ppfs_ecc_ctx* ctx);
+
+/*
+ * Block lists: "these nblocks block indices of this image, in this order" -- what FileIO::readFile /
+ * writeFile get from their BlockIndexIterator (lib/file_io/src/file_io.cpp:27-35, 53-69) for a file
+ * whose blocks lie wherever the bitmap allocator put them.  Engine extension of readBlocks /
+ * writeBlocks; one call instead of one per contiguous run.
+ *   d_image / image   packed raw blocks from block 0, image_blocks of them
+ *   d_index / index   nblocks unsigned 32-bit block indices
+ * Entry i gets exactly what the contiguous call gives block index[i]; payload i (data + i*dataSize()),
+ * status i and spill record i are in LIST order.
+ *   decode  the listed blocks are decoded; with write_back != 0 the blocks with status 1 are written
+ *           back into the image (RS, Hamming).  With write_back == 0, and for CRC / parity / none, the
+ *           image is not written at all.  d_data, d_status, d_spill may be NULL as in
+ *           ppfs_ecc_decode_device; a shortened RS code's spill (n < 255) is reported per entry and
+ *           never applied.
+ *   encode  block index[i] = encode(payload i); the bits the codec leaves undefined (and the parity
+ *           byte's bits above bit 0) keep the image's contents, as in ppfs_ecc_encode_device.
+ *   write   writeBlock(payload i, {index[i], 0}): status 0 / 1 / 5 as ppfs_ecc_write_device; a block
+ *           with status 5 stays untouched.
+ * An entry with index[i] >= image_blocks is not an error of the call: it gets status
+ * PPFS_ECC_OUT_OF_BOUNDS (9) and a zero payload, and touches nothing of the image.
+ * Repeated indices:
+ *   - encode and write: the indices of one call must be distinct (device forms).  With a repeated
+ *     index the call stays memory-safe, but which payload ends up in the block is unspecified.
+ *   - decode may repeat an index: every copy gets the same payload.  With write_back, a repeated
+ *     entry's status is that of a read either before or after another copy's write-back (1 or 0).
+ *   - the host forms process the list in runs without a repeated index, so their result equals the
+ *     per-block calls made in list order: the first entry of a corrupted block reports 1, a later
+ *     one reads the written-back block; for encode / write the last payload listed wins.
+ * Device forms: the rows are gathered into staging memory the context owns (made at the first list
+ * call, ppfs_ecc_host_chunk_blocks(ctx) blocks rounded down to a multiple of 1 Ki; longer lists run
+ * in pieces of that many blocks on `stream`), the codec runs on the copy, and the changed rows are
+ * scattered back.  d_data / d_status / d_spill keep the alignment rules of the contiguous calls
+ * (16 bytes for RS and Hamming).  The staging is shared by all streams of the context: each list
+ * call waits for the previous list call of that context, whichever stream it ran on.  A stream that
+ * is capturing a hipGraph gets PPFS_ECC_ENOTSUP.  Null ctx or required pointer: -EINVAL, checked
+ * before anything touches the GPU; nblocks == 0 returns 0.
+ * Host forms: same arguments with host pointers and no stream; they return when the results are in
+ * host memory.
+ */
+int ppfs_ecc_decode_list_device(ppfs_ecc_ctx* ctx, uint8_t* d_image, size_t image_blocks, const uint32_t* d_index,
+    size_t nblocks, uint8_t* d_data, uint8_t* d_status, int write_back, uint8_t* d_spill, void* stream);
+int ppfs_ecc_encode_list_device(ppfs_ecc_ctx* ctx, const uint8_t* d_data, uint8_t* d_image, size_t image_blocks,
+    const uint32_t* d_index, size_t nblocks, void* stream);
+int ppfs_ecc_write_list_device(ppfs_ecc_ctx* ctx, const uint8_t* d_data, uint8_t* d_image, size_t image_blocks,
+    const uint32_t* d_index, uint8_t* d_status, size_t nblocks, void* stream);
+int ppfs_ecc_decode_list_host(ppfs_ecc_ctx* ctx, uint8_t* image, size_t image_blocks, const uint32_t* index,
+    size_t nblocks, uint8_t* data, uint8_t* status, int write_back, uint8_t* spill);
+int ppfs_ecc_encode_list_host(ppfs_ecc_ctx* ctx, const uint8_t* data, uint8_t* image, size_t image_blocks,
+    const uint32_t* index, size_t nblocks);
+int ppfs_ecc_write_list_host(ppfs_ecc_ctx* ctx, const uint8_t* data, uint8_t* image, size_t image_blocks,
+    const uint32_t* index, uint8_t* status, size_t nblocks);
 
 /*
  * Whole-image scrub: the disk-image effect of readBlock(i, 0, dataSize()) for

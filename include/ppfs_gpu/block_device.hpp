@@ -32,6 +32,8 @@
  *
  * Extension: readBlocks / writeBlocks run a contiguous range of whole blocks
  * through ONE engine call; results, disk contents and log are those of the per-block loop.
+ * readBlockList / writeBlockList do the same for a list of block indices in any order (the blocks
+ * of a fragmented file, as FileIO's BlockIndexIterator yields them).
  */
 #include <algorithm>
 #include <cstddef>
@@ -43,6 +45,7 @@
 #include <memory>
 #include <string>
 #include <type_traits>
+#include <unordered_set>
 #include <utility>
 #include <vector>
 
@@ -493,6 +496,36 @@ public:
     virtual expected<void> writeBlocks(block_index_t first, size_t count, const uint8_t* payloads, uint8_t* err)
         = 0;
 
+    // List extension: whole blocks idx[0 .. count), in any order -- what FileIO's BlockIndexIterator
+    // loop (file_io.cpp:27-35, 53-69) collects for a fragmented file.  Equal to the per-block calls
+    // made in list order (a block listed twice is seen the second time as the first left it); out,
+    // payloads and err are in list order, err (may be null) as readBlocks.  The default is that
+    // per-block loop; the codecs run one engine call per list.
+    virtual expected<void> readBlockList(const block_index_t* idx, size_t count, uint8_t* out, uint8_t* err)
+    {
+        const size_t ds = dataSize();
+        for (size_t i = 0; i < count; ++i) {
+            static_vector<uint8_t> v(out + i * ds, ds, 0);
+            auto r = readBlock(DataLocation((int)idx[i], 0), ds, v);
+            if (!r)
+                std::memset(out + i * ds, 0, ds);
+            if (err)
+                err[i] = r ? 0 : (uint8_t)r.error();
+        }
+        return {};
+    }
+    virtual expected<void> writeBlockList(const block_index_t* idx, size_t count, const uint8_t* payloads, uint8_t* err)
+    {
+        const size_t ds = dataSize();
+        for (size_t i = 0; i < count; ++i) {
+            static_vector<uint8_t> v(const_cast<uint8_t*>(payloads + i * ds), ds, ds);
+            auto r = writeBlock(v, DataLocation((int)idx[i], 0));
+            if (err)
+                err[i] = r ? 0 : (uint8_t)r.error();
+        }
+        return {};
+    }
+
     // Whole-image scrub extension: the disk and log effect of
     // readBlock({i, 0}, dataSize()) for i in [first, first + count), in order, without the
     // payloads.  counts (may be null): blocks ok / corrected / failed; err as readBlocks.
@@ -566,6 +599,27 @@ public:
         auto r = detail::disk_write(_disk, (size_t)first * _bs, payloads, count * _bs);
         if (!r)
             return unexpected(r.error());
+        return {};
+    }
+    // lists: one plain copy per entry
+    expected<void> readBlockList(const block_index_t* idx, size_t count, uint8_t* out, uint8_t* err) override
+    {
+        for (size_t i = 0; i < count; ++i) {
+            auto r = detail::disk_read(_disk, (size_t)idx[i] * _bs, _bs, out + i * _bs);
+            if (!r)
+                std::memset(out + i * _bs, 0, _bs);
+            if (err)
+                err[i] = r ? 0 : (uint8_t)r.error();
+        }
+        return {};
+    }
+    expected<void> writeBlockList(const block_index_t* idx, size_t count, const uint8_t* payloads, uint8_t* err) override
+    {
+        for (size_t i = 0; i < count; ++i) {
+            auto r = detail::disk_write(_disk, (size_t)idx[i] * _bs, payloads + i * _bs, _bs);
+            if (err)
+                err[i] = r ? 0 : (uint8_t)r.error();
+        }
         return {};
     }
 
@@ -763,6 +817,155 @@ public:
         return {};
     }
 
+    // Lists.  With a mapped disk image (and no shortened RS code, whose write-back may run into
+    // the next block): one ppfs_ecc_*_list_host call on the image, which gathers the listed rows,
+    // cuts the list where an index repeats and copies the changed rows back.  Otherwise the rows are
+    // read from the disk entry by entry, each stretch of the list without a repeated index goes
+    // through one contiguous engine call, and the write-backs go to the disk in list order.
+    expected<void> readBlockList(const block_index_t* idx, size_t count, uint8_t* out, uint8_t* err) override
+    {
+        if (has_spill() || !_raw)
+            return IBlockDevice::readBlockList(idx, count, out, err);
+        if (err)
+            std::memset(err, 0, count);
+        if (uint8_t* img = _disk.mapped()) {
+            std::vector<uint8_t> status(count);
+            if (!EccEngine::ok(ppfs_ecc_decode_list_host(_eng.ctx(), img, _disk.size() / _raw, idx, count, out,
+                                   status.data(), 1, nullptr),
+                    "decode list"))
+                return unexpected(FsError::Disk_IOError);
+            for (size_t i = 0; i < count; ++i) {
+                if (status[i] == PPFS_ECC_OUT_OF_BOUNDS || status[i] == PPFS_ECC_CORRECTION_ERROR) {
+                    if (err)
+                        err[i] = (uint8_t)(status[i] == PPFS_ECC_OUT_OF_BOUNDS ? FsError::Disk_OutOfBounds
+                                                                               : FsError::BlockDevice_CorrectionError);
+                    std::memset(out + i * _ds, 0, _ds);
+                } else if (status[i] == PPFS_ECC_CORRECTED) {
+                    log(idx[i]);
+                }
+            }
+            return {};
+        }
+        std::vector<uint8_t> raw, fixed, status, dec;
+        std::vector<size_t> pos;
+        for (size_t s = 0; s < count;) {
+            const size_t e = list_run_end(idx, count, s);
+            if (!list_rows(idx, s, e, pos, raw)) { // a row could not be read: block by block
+                auto r = IBlockDevice::readBlockList(idx + s, e - s, out + s * _ds, err ? err + s : nullptr);
+                if (!r)
+                    return r;
+                s = e;
+                continue;
+            }
+            for (size_t i = s, j = 0; i < e; ++i) { // off the disk: the per-block call's error
+                if (j < pos.size() && pos[j] == i) {
+                    ++j;
+                    continue;
+                }
+                auto r = IBlockDevice::readBlockList(idx + i, 1, out + i * _ds, err ? err + i : nullptr);
+                if (!r)
+                    return r;
+            }
+            const size_t m = pos.size();
+            if (m) {
+                fixed = raw;
+                status.assign(m, 0);
+                dec.assign(m * _ds, 0);
+                const int wb = (_type == PPFS_ECC_REED_SOLOMON || _type == PPFS_ECC_HAMMING) ? 1 : 0;
+                if (!EccEngine::ok(ppfs_ecc_decode_host(_eng.ctx(), fixed.data(), dec.data(), status.data(), m, wb, nullptr),
+                        "decode"))
+                    return unexpected(FsError::Disk_IOError);
+            }
+            for (size_t j = 0; j < m; ++j) {
+                const size_t i = pos[j];
+                if (status[j] == PPFS_ECC_CORRECTION_ERROR) {
+                    if (err)
+                        err[i] = (uint8_t)FsError::BlockDevice_CorrectionError;
+                    std::memset(out + i * _ds, 0, _ds);
+                    continue;
+                }
+                std::memcpy(out + i * _ds, dec.data() + j * _ds, _ds);
+                if (status[j] == PPFS_ECC_CORRECTED) {
+                    auto wb = write_back(idx[i], raw.data() + j * _raw, fixed.data() + j * _raw, nullptr);
+                    if (!wb && err)
+                        err[i] = (uint8_t)wb.error();
+                }
+            }
+            s = e;
+        }
+        return {};
+    }
+
+    expected<void> writeBlockList(const block_index_t* idx, size_t count, const uint8_t* payloads, uint8_t* err) override
+    {
+        if (has_spill() || !_raw)
+            return IBlockDevice::writeBlockList(idx, count, payloads, err);
+        if (err)
+            std::memset(err, 0, count);
+        if (uint8_t* img = _disk.mapped()) {
+            std::vector<uint8_t> status(count);
+            if (!EccEngine::ok(ppfs_ecc_write_list_host(_eng.ctx(), payloads, img, _disk.size() / _raw, idx,
+                                   status.data(), count),
+                    "write list"))
+                return unexpected(FsError::Disk_IOError);
+            for (size_t i = 0; i < count; ++i) {
+                if (status[i] == PPFS_ECC_OUT_OF_BOUNDS || status[i] == PPFS_ECC_CORRECTION_ERROR) {
+                    if (err)
+                        err[i] = (uint8_t)(status[i] == PPFS_ECC_OUT_OF_BOUNDS ? FsError::Disk_OutOfBounds
+                                                                               : FsError::BlockDevice_CorrectionError);
+                } else if (status[i] == PPFS_ECC_CORRECTED) {
+                    log(idx[i]); // the old block's write-back was overwritten by the new block
+                }
+            }
+            return {};
+        }
+        std::vector<uint8_t> raw, status, pay;
+        std::vector<size_t> pos;
+        for (size_t s = 0; s < count;) {
+            const size_t e = list_run_end(idx, count, s);
+            if (!list_rows(idx, s, e, pos, raw)) {
+                auto r = IBlockDevice::writeBlockList(idx + s, e - s, payloads + s * _ds, err ? err + s : nullptr);
+                if (!r)
+                    return r;
+                s = e;
+                continue;
+            }
+            for (size_t i = s, j = 0; i < e; ++i) {
+                if (j < pos.size() && pos[j] == i) {
+                    ++j;
+                    continue;
+                }
+                auto r = IBlockDevice::writeBlockList(idx + i, 1, payloads + i * _ds, err ? err + i : nullptr);
+                if (!r)
+                    return r;
+            }
+            const size_t m = pos.size();
+            if (m) {
+                status.assign(m, 0);
+                pay.resize(m * _ds);
+                for (size_t j = 0; j < m; ++j)
+                    std::memcpy(pay.data() + j * _ds, payloads + pos[j] * _ds, _ds);
+                if (!EccEngine::ok(ppfs_ecc_write_host(_eng.ctx(), pay.data(), raw.data(), status.data(), m), "write"))
+                    return unexpected(FsError::Disk_IOError);
+            }
+            for (size_t j = 0; j < m; ++j) {
+                const size_t i = pos[j];
+                if (status[j] == PPFS_ECC_CORRECTION_ERROR) {
+                    if (err)
+                        err[i] = (uint8_t)FsError::BlockDevice_CorrectionError; // block left untouched
+                    continue;
+                }
+                if (status[j] == PPFS_ECC_CORRECTED)
+                    log(idx[i]);
+                auto w = detail::disk_write(_disk, (size_t)idx[i] * _raw, raw.data() + j * _raw, _raw);
+                if (!w && err)
+                    err[i] = (uint8_t)w.error();
+            }
+            s = e;
+        }
+        return {};
+    }
+
     // One engine call (ppfs_ecc_scrub_host) over the disk image from block `first` to the disk
     // end: the write-back of every corrected block is applied in index order, including RS
     // bytes a shortened code writes past a block end; corrected blocks are logged in order.
@@ -833,6 +1036,30 @@ protected:
 
     bool has_spill() const { return _type == PPFS_ECC_REED_SOLOMON && _raw > 0 && _raw < 255; }
     size_t spill_stride() const { return 256 - std::min<size_t>(_raw, 255); }
+
+    // the end of the stretch of a list from `start` in which no index repeats
+    static size_t list_run_end(const block_index_t* idx, size_t count, size_t start)
+    {
+        std::unordered_set<block_index_t> seen;
+        size_t e = start;
+        while (e < count && seen.insert(idx[e]).second)
+            ++e;
+        return e;
+    }
+    // The rows of the entries [s, e) that lie on the disk, packed in list order, and their list
+    // positions; false when a row on the disk could not be read.
+    bool list_rows(const block_index_t* idx, size_t s, size_t e, std::vector<size_t>& pos, std::vector<uint8_t>& rows)
+    {
+        pos.clear();
+        for (size_t i = s; i < e; ++i)
+            if (((size_t)idx[i] + 1) * _raw <= _disk.size())
+                pos.push_back(i);
+        rows.assign(pos.size() * _raw, 0);
+        for (size_t j = 0; j < pos.size(); ++j)
+            if (!detail::disk_read(_disk, (size_t)idx[pos[j]] * _raw, _raw, rows.data() + j * _raw))
+                return false;
+        return true;
+    }
 
     void log(block_index_t b)
     {

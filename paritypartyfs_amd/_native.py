@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("PPFS_ECC_LIB") or os.path.join(_HERE, "_lib", "libppf
 ECC_NONE, ECC_CRC, ECC_HAMMING, ECC_PARITY, ECC_REED_SOLOMON = 0, 1, 2, 3, 4
 
 STATUS_OK, STATUS_CORRECTED, STATUS_CORRECTION_ERROR = 0, 1, 5
+STATUS_OUT_OF_BOUNDS = 9  # a block-list entry past the image (FsError::Disk_OutOfBounds)
 
 # every symbol include/ppfs_ecc.h declares
 EXPORTED_SYMBOLS = (
@@ -35,6 +36,12 @@ EXPORTED_SYMBOLS = (
     "ppfs_ecc_decode_host",
     "ppfs_ecc_write_host",
     "ppfs_ecc_host_chunk_blocks",
+    "ppfs_ecc_decode_list_device",
+    "ppfs_ecc_encode_list_device",
+    "ppfs_ecc_write_list_device",
+    "ppfs_ecc_decode_list_host",
+    "ppfs_ecc_encode_list_host",
+    "ppfs_ecc_write_list_host",
     "ppfs_ecc_scrub_host",
     "ppfs_ecc_scrub_device",
     "ppfs_vote3_device",
@@ -136,6 +143,22 @@ def lib() -> ctypes.CDLL:
     L.ppfs_ecc_decode_host.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
     L.ppfs_ecc_write_host.restype = c_int
     L.ppfs_ecc_write_host.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]
+    # block lists: (ctx, image, image_blocks, index, nblocks, data, status, write_back, spill[, stream])
+    L.ppfs_ecc_decode_list_device.restype = c_int
+    L.ppfs_ecc_decode_list_device.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_int,
+                                              c_void_p, c_void_p]
+    L.ppfs_ecc_encode_list_device.restype = c_int
+    L.ppfs_ecc_encode_list_device.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]
+    L.ppfs_ecc_write_list_device.restype = c_int
+    L.ppfs_ecc_write_list_device.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t,
+                                             c_void_p]
+    L.ppfs_ecc_decode_list_host.restype = c_int
+    L.ppfs_ecc_decode_list_host.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_int,
+                                            c_void_p]
+    L.ppfs_ecc_encode_list_host.restype = c_int
+    L.ppfs_ecc_encode_list_host.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]
+    L.ppfs_ecc_write_list_host.restype = c_int
+    L.ppfs_ecc_write_list_host.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t]
     L.ppfs_ecc_scrub_host.restype = c_int
     L.ppfs_ecc_scrub_host.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, POINTER(c_size_t)]
     L.ppfs_ecc_scrub_device.restype = c_int

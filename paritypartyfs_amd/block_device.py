@@ -213,6 +213,46 @@ class IBlockDevice:
         return err
 
 
+    # list API: whole blocks, any order -- what FileIO's BlockIndexIterator loop collects for a
+    # fragmented file (file_io.cpp:27-35, 53-69).  The per-block loop; the codecs override it.
+    def readBlockList(self, indices) -> Tuple[np.ndarray, np.ndarray]:
+        """== readBlock(DataLocation(i, 0), dataSize()) for i in indices, in list order; returns
+        (payloads [len(indices), dataSize], FsError-or-0 per entry)."""
+        indices = [int(i) for i in indices]
+        out = np.zeros((len(indices), self.dataSize()), dtype=np.uint8)
+        err = np.zeros(len(indices), dtype=np.uint8)
+        for k, i in enumerate(indices):
+            r = self.readBlock(DataLocation(i, 0), self.dataSize())
+            if r:
+                out[k] = np.frombuffer(r.value(), dtype=np.uint8)
+            else:
+                err[k] = int(r.error())
+        return out, err
+
+    def writeBlockList(self, indices, payloads: np.ndarray) -> np.ndarray:
+        """== writeBlock(payload_k, DataLocation(indices[k], 0)) in list order (full-block writes)."""
+        indices = [int(i) for i in indices]
+        payloads = np.ascontiguousarray(payloads, dtype=np.uint8).reshape(len(indices), -1)
+        err = np.zeros(len(indices), dtype=np.uint8)
+        for k, i in enumerate(indices):
+            r = self.writeBlock(bytes(payloads[k]), DataLocation(i, 0))
+            if not r:
+                err[k] = int(r.error())
+        return err
+
+
+def _list_runs(indices: List[int]):
+    """[start, end) of the maximal stretches of a list in which no index repeats."""
+    start, seen = 0, set()
+    for k, i in enumerate(indices):
+        if i in seen:
+            yield start, k
+            start, seen = k, set()
+        seen.add(i)
+    if start < len(indices):
+        yield start, len(indices)
+
+
 class RawBlockDevice(IBlockDevice):  # raw_block_device.cpp
     def __init__(self, block_size: int, disk: IDisk):
         self._bs, self._disk = int(block_size), disk
@@ -395,6 +435,93 @@ class _EngineDevice(IBlockDevice):
         w = self._disk.write(first * self._raw, raw.tobytes())
         if not w:
             err[:] = int(w.error())
+        return err
+
+    # ---- block lists: one engine call per stretch of the list without a repeated index ----
+    def _on_disk(self, block_index: int) -> bool:
+        return 0 <= block_index and (block_index + 1) * self._raw <= self._disk.size()
+
+    def _list_rows(self, indices: List[int]):
+        """(list positions of the entries that lie on the disk, their rows packed); None for the
+        rows when a disk read failed (the caller then goes block by block)."""
+        pos = [k for k, i in enumerate(indices) if self._on_disk(i)]
+        rows = np.zeros(len(pos) * self._raw, dtype=np.uint8)
+        for j, k in enumerate(pos):
+            r = self._disk.read(indices[k] * self._raw, self._raw)
+            if not r:
+                return pos, None
+            rows[j * self._raw:(j + 1) * self._raw] = np.frombuffer(r.value(), dtype=np.uint8)
+        return pos, rows
+
+    def readBlockList(self, indices) -> Tuple[np.ndarray, np.ndarray]:
+        """== readBlock(DataLocation(i, 0), dataSize()) for i in indices, in list order: same
+        payloads, per-entry errors, disk contents and correction log.  A block listed again is read
+        as its earlier entry's write-back left it."""
+        indices = [int(i) for i in indices]
+        if self._has_spill():
+            return super().readBlockList(indices)  # a write-back may run into the next block
+        out = np.zeros((len(indices), self._ds), dtype=np.uint8)
+        err = np.zeros(len(indices), dtype=np.uint8)
+        e = self._engine
+        wb = e.ecc_type in (ECC_REED_SOLOMON, ECC_HAMMING)
+        for s, t in _list_runs(indices):
+            run = indices[s:t]
+            pos, raw = self._list_rows(run)
+            if raw is None:
+                out[s:t], err[s:t] = super().readBlockList(run)
+                continue
+            for k in set(range(len(run))) - set(pos):  # off the disk: the per-block call's error
+                r = self.readBlock(DataLocation(run[k], 0), self._ds)
+                err[s + k] = int(r.error()) if not r else 0
+            if not pos:
+                continue
+            fixed = raw.copy()
+            status = np.zeros(len(pos), dtype=np.uint8)
+            data = np.zeros(len(pos) * self._ds, dtype=np.uint8)
+            e.decode_host(fixed, data, status, write_back=wb)
+            data = data.reshape(len(pos), self._ds)
+            for j, k in enumerate(pos):
+                st = int(status[j])
+                if st == STATUS_CORRECTION_ERROR:
+                    err[s + k] = int(FsError.BlockDevice_CorrectionError)
+                    continue
+                out[s + k] = data[j]
+                if st == STATUS_CORRECTED and wb:
+                    fe = self._write_back(run[k], raw[j * self._raw:(j + 1) * self._raw],
+                                          fixed[j * self._raw:(j + 1) * self._raw], None)
+                    if fe is not None:
+                        err[s + k] = int(fe)
+        return out, err
+
+    def writeBlockList(self, indices, payloads: np.ndarray) -> np.ndarray:
+        """== writeBlock(payload_k, DataLocation(indices[k], 0)) in list order (full-block writes)."""
+        indices = [int(i) for i in indices]
+        payloads = np.ascontiguousarray(payloads, dtype=np.uint8).reshape(len(indices), self._ds)
+        if self._has_spill():
+            return super().writeBlockList(indices, payloads)
+        err = np.zeros(len(indices), dtype=np.uint8)
+        for s, t in _list_runs(indices):
+            run = indices[s:t]
+            pos, raw = self._list_rows(run)
+            if raw is None:
+                err[s:t] = super().writeBlockList(run, payloads[s:t])
+                continue
+            for k in set(range(len(run))) - set(pos):
+                r = self.writeBlock(bytes(payloads[s + k]), DataLocation(run[k], 0))
+                err[s + k] = int(r.error()) if not r else 0
+            if not pos:
+                continue
+            status = np.zeros(len(pos), dtype=np.uint8)
+            self._engine.write_host(np.ascontiguousarray(payloads[s:t][pos]).reshape(-1), raw, status)
+            for j, k in enumerate(pos):
+                if status[j] == STATUS_CORRECTION_ERROR:
+                    err[s + k] = int(FsError.BlockDevice_CorrectionError)  # block left untouched
+                    continue
+                if status[j] == STATUS_CORRECTED:
+                    self._log(run[k])  # the old block's write-back is overwritten below
+                w = self._disk.write(run[k] * self._raw, raw[j * self._raw:(j + 1) * self._raw].tobytes())
+                if not w:
+                    err[s + k] = int(w.error())
         return err
 
     def readBlock(self, loc: DataLocation, bytes_to_read: int, capacity: Optional[int] = None) -> Expected[bytes]:

@@ -1,6 +1,6 @@
 // api.cpp -- host implementation of the ppfs_ecc C ABI (include/ppfs_ecc.h): context create /
 // destroy, the device-memory entry points, scrub, vote and groups.  The host-memory entry points
-// are in host_path.cpp; the two share ctx.hpp.
+// are in host_path.cpp and the block-list entry points in list_path.cpp; the three share ctx.hpp.
 //
 // Builds the per-context codec tables (host_tables.hpp: GF(2^8) log/antilog, RS slicing tables, CRC
 // shift tables), uploads them once, and dispatches batches to the HIP kernels in rs_kernels.hip and
@@ -505,7 +505,7 @@ extern "C" void ppfs_ecc_destroy(ppfs_ecc_ctx* c)
         (void)hipEventSynchronize(c->ev[i]);
         (void)hipEventDestroy(c->ev[i]);
     }
-    if (c->ev_overflow && (c->d_tables || c->d_scratch || c->d_ctr))
+    if (c->ev_overflow && (c->d_tables || c->d_scratch || c->d_ctr || c->d_list))
         (void)hipDeviceSynchronize();
     (void)hipGetLastError();
     if (!srv_gone) {
@@ -531,6 +531,9 @@ extern "C" void ppfs_ecc_destroy(ppfs_ecc_ctx* c)
     mem_free(c, c->d_tables);
     mem_free(c, c->d_ctr);
     mem_free(c, c->d_scratch);
+    mem_free(c, c->d_list); // list calls ran on caller streams: waited for above
+    if (c->list_ev)
+        (void)hipEventDestroy(c->list_ev);
     pin_free(c->h_zc, c->zc_bytes, kPinMapped);
     pin_free(c->h_box, sizeof(ppfs::SrvBox), kPinMapped); // after the streams drained: flag kernels write it
     if (c->ms)
@@ -790,6 +793,13 @@ extern "C" int ppfs_ecc_write_device(ppfs_ecc_ctx* c, const uint8_t* d_data, uin
 {
     return queued(c, ppfs_ecc_write_device_impl(c, d_data, d_raw, d_status, nblocks, ordered(c, nblocks, stream)),
         nblocks, stream, "write (async)");
+}
+
+bool ppfs::stream_capturing(hipStream_t s) { return capturing(s); }
+void* ppfs::call_ordered(ppfs_ecc_ctx* c, size_t nblocks, void* stream) { return ordered(c, nblocks, stream); }
+int ppfs::call_queued(ppfs_ecc_ctx* c, int r, size_t nblocks, void* stream, const char* what)
+{
+    return queued(c, r, nblocks, stream, what);
 }
 
 namespace ppfs {

@@ -1,5 +1,6 @@
 // ctx.hpp -- the engine context and what api.cpp (create / destroy, the device entry points, scrub,
-// vote, groups) and host_path.cpp (the host-memory entry points) share.  Everything declared in
+// vote, groups), host_path.cpp (the host-memory entry points) and list_path.cpp (the block-list
+// entry points) share.  Everything declared in
 // namespace ppfs here has hidden visibility: the library exports the C ABI of include/ppfs_ecc.h
 // and the kernel launchers, nothing of this.
 #pragma once
@@ -131,6 +132,13 @@ struct ppfs_ecc_ctx {
     // the context's own stream for its stream-ordered device allocations (mem_alloc / mem_free)
     hipStream_t ms = nullptr;
     size_t pin_bytes = 0; // bytes of each h_pin[] buffer (pin cache key)
+    // block-list calls (list_path.cpp): the gathered rows of one piece and a status array, made at
+    // the first list call and shared by every stream of the context -- a list call waits for
+    // list_ev, recorded after the previous list call's last kernel, before it touches them
+    uint8_t* d_list = nullptr;
+    size_t list_bytes = 0, list_status_off = 0;
+    hipEvent_t list_ev = nullptr;
+    bool list_ev_rec = false;
 };
 
 #pragma GCC visibility push(hidden)
@@ -172,6 +180,14 @@ inline bool rs_wb_direct(const ppfs_ecc_ctx* c)
 // contexts only; nullptr: into d_raw) (api.cpp)
 int decode_device_to(ppfs_ecc_ctx* c, uint8_t* d_raw, uint8_t* d_data, uint8_t* d_status, size_t nblocks, int write_back,
     uint8_t* d_spill, void* stream, uint8_t* wb_dst);
+
+// What every device entry point does around the work it queues on a caller's stream (api.cpp), for
+// the entry points outside api.cpp: call_ordered before the first launch (after the last call on the
+// same stream handle), call_queued after the last (the stream's completion event destroy waits on,
+// then PPFS_ECC_SYNC_CHECK); stream_capturing: is s capturing a hipGraph?
+bool stream_capturing(hipStream_t s);
+void* call_ordered(ppfs_ecc_ctx* c, size_t nblocks, void* stream);
+int call_queued(ppfs_ecc_ctx* c, int r, size_t nblocks, void* stream, const char* what);
 
 } // namespace ppfs
 #pragma GCC visibility pop

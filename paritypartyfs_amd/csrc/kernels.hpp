@@ -1,6 +1,6 @@
 // kernels.hpp -- the host-callable launchers of the kernel translation units, declared once:
 // rs_kernels.hip (Reed-Solomon and its servers), bit_kernels.hip (CRC, Hamming, parity and the bit
-// server) and vote.hip (vote, copy, gather, patch list, inject, flag).  The
+// server) and vote.hip (vote, copy, gather, patch list, inject, flag, block lists).  The
 // three table-sizing functions are in host_tables.hpp, beside the builders that use them.
 #pragma once
 
@@ -49,4 +49,12 @@ hipError_t ppfs_patch_list_launch(const uint8_t* cur, const uint8_t* orig, const
     uint32_t S, uint32_t* patch, uint8_t* image, hipStream_t s);
 hipError_t ppfs_inject_launch(uint8_t* raw, uint64_t stride, uint64_t nblocks, const uint8_t* pos, const uint8_t* val,
     int mode, hipStream_t s);
+// block lists (list_path.cpp): stage is 16-byte aligned with a capacity of nb * raw rounded up to 16;
+// scatter mode 0 = every in-range entry, 1 = status 1, 2 = status other than 5
+hipError_t ppfs_gather_blocks_launch(const uint8_t* img, uint64_t image_blocks, const uint32_t* index, uint32_t nb,
+    uint32_t raw, uint8_t* stage, hipStream_t s);
+hipError_t ppfs_scatter_blocks_launch(const uint8_t* stage, uint8_t* img, uint64_t image_blocks, const uint32_t* index,
+    const uint8_t* status, int mode, uint32_t nb, uint32_t raw, hipStream_t s);
+hipError_t ppfs_list_oob_launch(const uint32_t* index, uint32_t nb, uint64_t image_blocks, uint8_t* status, uint8_t* data,
+    uint32_t data_bytes, hipStream_t s);
 }

@@ -260,6 +260,190 @@ extern "C" hipError_t ppfs_gather_rows_launch(const uint8_t* src, uint64_t src_r
     return hipGetLastError();
 }
 
+// ---- block lists (list_path.cpp): image rows <-> a dense staging copy ----
+// A list call names nb rows of an image of image_blocks rows of `raw` bytes, in any order: entry i is
+// image row index[i].  With raw = 255 (every RS case) an image row has every byte alignment and a
+// staging row has another, so neither kernel can copy 16-byte pieces from equal offsets as
+// gather_rows_kernel does.  Both work in 16-byte windows ALIGNED ON THE SIDE THEY STORE TO, read the
+// other side as the aligned dwords that cover the window (five, or four when the two sides happen to
+// agree mod 4) and bring them into place with v_alignbyte; only the windows that hold a row's head
+// or tail fall back to bytes.  Positions are 32-bit: the launchers refuse nb * raw >= 2^32.
+namespace ppfs {
+
+// the 16 bytes at p (any alignment) from aligned dword loads; the caller guarantees that the
+// aligned dwords covering [p, p + 16) may be read
+__device__ inline uint4 load16_funnel(const uint8_t* p)
+{
+    const uint32_t sh = (uint32_t)((uintptr_t)p & 3u);
+    const uint32_t* a = (const uint32_t*)((uintptr_t)p & ~(uintptr_t)3);
+    const uint32_t w0 = a[0], w1 = a[1], w2 = a[2], w3 = a[3];
+    if (sh == 0)
+        return make_uint4(w0, w1, w2, w3);
+    const uint32_t w4 = a[4];
+    return make_uint4(__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh),
+        __builtin_amdgcn_alignbyte(w3, w2, sh), __builtin_amdgcn_alignbyte(w4, w3, sh));
+}
+
+// stage row i = image row index[i] for i < nb; an entry with index[i] >= image_blocks is never
+// dereferenced and its row becomes zeros.  One lane per 16-byte window of the staging copy
+// (16-byte aligned, capacity nb * raw rounded up to 16: the last window is stored whole, its excess
+// zero).  A window inside one row takes the aligned-dword path unless those dwords would reach
+// outside the image (only next to the image's two ends); a window over a row boundary is put
+// together from byte loads.  Every store is one aligned 16 bytes.
+__global__ __launch_bounds__(256) void gather_blocks_kernel(const uint8_t* __restrict__ img, uint64_t image_blocks,
+    const uint32_t* __restrict__ index, uint32_t nb, uint32_t raw, uint8_t* __restrict__ stage)
+{
+    const uint32_t total = nb * raw, nwin = (total + 15u) / 16u;
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= nwin)
+        return;
+    const uint8_t* img_end = img + image_blocks * raw;
+    const uint32_t P = 16u * c;
+    uint32_t row = P / raw, col = P - row * raw;
+    uint32_t idx = PPFS_DBG_OK(index + row, 4, index, (uint64_t)nb * 4) ? index[row] : 0xFFFFFFFFu;
+    uint4 v = make_uint4(0, 0, 0, 0);
+    bool done = false;
+    if (col + 16u <= raw) {
+        if (idx >= image_blocks) {
+            done = true;
+        } else {
+            const uint8_t* p = img + (uint64_t)idx * raw + col;
+            const uint8_t* a = (const uint8_t*)((uintptr_t)p & ~(uintptr_t)3);
+            const uint32_t span = ((uintptr_t)p & 3u) ? 20u : 16u;
+            if (a >= img && a + span <= img_end && PPFS_DBG_OK(a, span, img, image_blocks * raw)) {
+                v = load16_funnel(p);
+                done = true;
+            }
+        }
+    }
+    if (!done) {
+        uint32_t w[4] = { 0, 0, 0, 0 };
+#pragma unroll
+        for (uint32_t j = 0; j < 16; ++j) {
+            uint32_t b = 0;
+            if (row < nb && idx < image_blocks) {
+                const uint8_t* p = img + (uint64_t)idx * raw + col;
+                if (PPFS_DBG_OK(p, 1, img, image_blocks * raw))
+                    b = *p;
+            }
+            w[j >> 2] |= b << (8u * (j & 3u));
+            if (++col == raw) {
+                col = 0;
+                ++row;
+                idx = row < nb && PPFS_DBG_OK(index + row, 4, index, (uint64_t)nb * 4) ? index[row] : 0xFFFFFFFFu;
+            }
+        }
+        v = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    if (PPFS_DBG_OK(stage + P, 16, stage, (uint64_t)nwin * 16))
+        *(uint4*)(stage + P) = v;
+}
+
+// image row index[i] = stage row i for the entries that are in range and that `mode` selects:
+// 0 every entry, 1 status[i] == 1 (a decode's write-back), 2 status[i] != 5 (a write whose old
+// block passed its check).  Row i's destination is cut into the 16-byte ALIGNED windows of the image
+// that it touches (at most K = (raw + 15) / 16 + 1), one lane each: a window wholly inside the row
+// is one aligned 16-byte store of funnel-shifted staging dwords, the head and tail windows store
+// their bytes of the row one by one.  So every destination byte has exactly one writer, nothing
+// outside a selected row is written and nothing of the image is read.  The staging copy is read
+// as aligned dwords up to its capacity (nb * raw rounded up to 16).
+__global__ __launch_bounds__(256) void scatter_blocks_kernel(const uint8_t* __restrict__ stage, uint8_t* __restrict__ img,
+    uint64_t image_blocks, const uint32_t* __restrict__ index, const uint8_t* __restrict__ status, int mode, uint32_t nb,
+    uint32_t raw, uint32_t K)
+{
+    const uint64_t item = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (item >= (uint64_t)nb * K)
+        return;
+    const uint32_t i = (uint32_t)(item / K), k = (uint32_t)(item - (uint64_t)i * K);
+    if (!PPFS_DBG_OK(index + i, 4, index, (uint64_t)nb * 4))
+        return;
+    const uint32_t idx = index[i];
+    if (idx >= image_blocks)
+        return;
+    if (mode != 0) {
+        if (!PPFS_DBG_OK(status + i, 1, status, nb))
+            return;
+        const uint32_t st = status[i];
+        if (mode == 1 ? st != 1u : st == 5u)
+            return;
+    }
+    uint8_t* d = img + (uint64_t)idx * raw;
+    const uint8_t* s = stage + (uint64_t)i * raw;
+    const uintptr_t win = ((uintptr_t)d & ~(uintptr_t)15) + 16u * (uintptr_t)k;
+    const uintptr_t lo = win > (uintptr_t)d ? win : (uintptr_t)d;
+    const uintptr_t hi = win + 16u < (uintptr_t)d + raw ? win + 16u : (uintptr_t)d + raw;
+    if (lo >= hi)
+        return;
+    const uint32_t off = (uint32_t)(lo - (uintptr_t)d), len = (uint32_t)(hi - lo);
+    if (!PPFS_DBG_OK(d + off, len, img, image_blocks * raw)
+        || !PPFS_DBG_OK(s + off, len, stage, (((uint64_t)nb * raw + 15u) / 16u) * 16u))
+        return;
+    if (len == 16u) {
+        *(uint4*)(d + off) = load16_funnel(s + off);
+    } else {
+        for (uint32_t b = 0; b < len; ++b)
+            d[off + b] = s[off + b];
+    }
+}
+
+// the out-of-range entries of a list: status PPFS_ECC_OUT_OF_BOUNDS (9) and a zero payload, after
+// the codec ran over their zero staging rows.  One thread per entry; such entries are a caller's
+// mistake, not a path to tune.
+__global__ __launch_bounds__(256) void list_oob_kernel(const uint32_t* __restrict__ index, uint32_t nb, uint64_t image_blocks,
+    uint8_t* __restrict__ status, uint8_t* __restrict__ data, uint32_t data_bytes)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nb || !PPFS_DBG_OK(index + i, 4, index, (uint64_t)nb * 4) || index[i] < image_blocks)
+        return;
+    if (status && PPFS_DBG_OK(status + i, 1, status, nb))
+        status[i] = 9;
+    if (data && PPFS_DBG_OK(data + (uint64_t)i * data_bytes, data_bytes, data, (uint64_t)nb * data_bytes))
+        for (uint32_t b = 0; b < data_bytes; ++b)
+            data[(uint64_t)i * data_bytes + b] = 0;
+}
+} // namespace ppfs
+
+// stage: 16-byte aligned, capacity nb * raw rounded up to 16
+extern "C" hipError_t ppfs_gather_blocks_launch(const uint8_t* img, uint64_t image_blocks, const uint32_t* index, uint32_t nb,
+    uint32_t raw, uint8_t* stage, hipStream_t s)
+{
+    if (nb == 0 || raw == 0)
+        return hipSuccess;
+    if ((uint64_t)nb * raw >= (1ull << 32) || ((uintptr_t)stage & 15u))
+        return hipErrorInvalidValue;
+    const uint32_t nwin = (nb * raw + 15u) / 16u;
+    hipLaunchKernelGGL(ppfs::gather_blocks_kernel, dim3((nwin + 255u) / 256u), dim3(256), 0, s, img, image_blocks, index, nb,
+        raw, stage);
+    return hipGetLastError();
+}
+
+// mode: 0 every in-range entry, 1 those with status 1, 2 those with status other than 5
+extern "C" hipError_t ppfs_scatter_blocks_launch(const uint8_t* stage, uint8_t* img, uint64_t image_blocks,
+    const uint32_t* index, const uint8_t* status, int mode, uint32_t nb, uint32_t raw, hipStream_t s)
+{
+    if (nb == 0 || raw == 0)
+        return hipSuccess;
+    if ((uint64_t)nb * raw >= (1ull << 32) || ((uintptr_t)stage & 15u) || mode < 0 || mode > 2 || (mode && !status))
+        return hipErrorInvalidValue;
+    const uint32_t K = (raw + 15u) / 16u + 1u;
+    const uint64_t grid = ((uint64_t)nb * K + 255u) / 256u;
+    if (grid > 0x7FFFFFFFull)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ppfs::scatter_blocks_kernel, dim3((uint32_t)grid), dim3(256), 0, s, stage, img, image_blocks, index,
+        status, mode, nb, raw, K);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t ppfs_list_oob_launch(const uint32_t* index, uint32_t nb, uint64_t image_blocks, uint8_t* status,
+    uint8_t* data, uint32_t data_bytes, hipStream_t s)
+{
+    if (nb == 0 || (!status && !(data && data_bytes)))
+        return hipSuccess;
+    hipLaunchKernelGGL(ppfs::list_oob_kernel, dim3((nb + 255u) / 256u), dim3(256), 0, s, index, nb, image_blocks, status,
+        data_bytes ? data : nullptr, data_bytes);
+    return hipGetLastError();
+}
+
 PPFS_DBG_ACCESSOR(ppfs_dbg_faults_vote)
 
 // Positive control of the PPFS_ECC_DEBUG checks (tests/test_gpu_hygiene.py): a gather of row 5

@@ -156,6 +156,79 @@ class EccEngine:
     def spill_bytes_per_block(self) -> int:
         return 256 - min(self.raw_block_size, 255)
 
+    # ---------------- block lists (include/ppfs_ecc.h ppfs_ecc_*_list_*) ----------------
+    # "these block indices of this image, in this order": entry i is block index[i] of the image;
+    # payloads, statuses and spill records are in list order.  An index past the image gets status 9
+    # (STATUS_OUT_OF_BOUNDS) and a zero payload.  The image's block count is taken from its size.
+    def _list_check(self, kind, image, index, data=None, status=None, spill=None):
+        """(entries, image blocks) of a list call after the buffer checks of the contiguous calls."""
+        if kind == "device":
+            import torch
+
+            if isinstance(index, np.ndarray) or not getattr(index, "is_cuda", False):
+                raise ValueError("index: device entry points take CUDA tensors")
+            if index.dtype != torch.int32 or not index.is_contiguous() or index.dim() != 1:
+                raise ValueError("index: a contiguous 1-D torch.int32 tensor (read as unsigned)")
+            n = int(index.numel())
+        else:
+            if not isinstance(index, np.ndarray):
+                raise ValueError("index: host entry points take numpy arrays")
+            if index.dtype != np.uint32 or not index.flags["C_CONTIGUOUS"] or index.ndim != 1:
+                raise ValueError("index: a C-contiguous 1-D numpy uint32 array")
+            n = int(index.size)
+        if image is None:
+            raise ValueError("image: required")
+        _need("image", image, 0, kind)
+        _ptr(image)  # contiguous uint8
+        self._check(kind, n, data=data, status=status, spill=spill)
+        return n, _size(image) // self.raw_block_size
+
+    @staticmethod
+    def _index_ptr(index) -> int:
+        return index.ctypes.data if isinstance(index, np.ndarray) else index.data_ptr()
+
+    def _list_payload(self, kind, data, n) -> None:
+        if data is None and self.data_size and n:
+            raise ValueError("data: required")
+        _need("data", data, n * self.data_size, kind)
+
+    def decode_list(self, image, index, data=None, status=None, write_back: bool = True, spill=None, stream=None) -> None:
+        n, blocks = self._list_check("device", image, index, data, status, spill)
+        check(lib().ppfs_ecc_decode_list_device(self._h, _ptr(image), blocks, self._index_ptr(index), n, _ptr(data),
+                                                _ptr(status), int(bool(write_back)), _ptr(spill),
+                                                _stream_handle(stream)))
+
+    def encode_list(self, data, image, index, stream=None) -> None:
+        n, blocks = self._list_check("device", image, index, data)
+        self._list_payload("device", data, n)
+        check(lib().ppfs_ecc_encode_list_device(self._h, _ptr(data), _ptr(image), blocks, self._index_ptr(index), n,
+                                                _stream_handle(stream)))
+
+    def write_list(self, data, image, index, status=None, stream=None) -> None:
+        n, blocks = self._list_check("device", image, index, data, status)
+        self._list_payload("device", data, n)
+        check(lib().ppfs_ecc_write_list_device(self._h, _ptr(data), _ptr(image), blocks, self._index_ptr(index),
+                                               _ptr(status), n, _stream_handle(stream)))
+
+    def decode_list_host(self, image: np.ndarray, index: np.ndarray, data: Optional[np.ndarray] = None,
+                         status: Optional[np.ndarray] = None, write_back: bool = True,
+                         spill: Optional[np.ndarray] = None) -> None:
+        n, blocks = self._list_check("host", image, index, data, status, spill)
+        check(lib().ppfs_ecc_decode_list_host(self._h, _ptr(image), blocks, self._index_ptr(index), n, _ptr(data),
+                                              _ptr(status), int(bool(write_back)), _ptr(spill)))
+
+    def encode_list_host(self, data: np.ndarray, image: np.ndarray, index: np.ndarray) -> None:
+        n, blocks = self._list_check("host", image, index, data)
+        self._list_payload("host", data, n)
+        check(lib().ppfs_ecc_encode_list_host(self._h, _ptr(data), _ptr(image), blocks, self._index_ptr(index), n))
+
+    def write_list_host(self, data: np.ndarray, image: np.ndarray, index: np.ndarray,
+                        status: Optional[np.ndarray] = None) -> None:
+        n, blocks = self._list_check("host", image, index, data, status)
+        self._list_payload("host", data, n)
+        check(lib().ppfs_ecc_write_list_host(self._h, _ptr(data), _ptr(image), blocks, self._index_ptr(index),
+                                             _ptr(status), n))
+
     # ---------------- whole-image scrub (SURVEY 8f-3) ----------------
     def scrub_host(self, image: np.ndarray, nblocks: Optional[int] = None, status: Optional[np.ndarray] = None):
         """readBlock(i) for every block of a host image, in order, for its write-back effect only
