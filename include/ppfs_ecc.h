@@ -197,6 +197,61 @@ int ppfs_ecc_write_list_host(ppfs_ecc_ctx* ctx, const uint8_t* data, uint8_t* im
     const uint32_t* index, uint8_t* status, size_t nblocks);
 
 /*
+ * Byte extents: "these n byte ranges of those blocks" -- a batch of (block, offset, length), the form
+ * in which the callers of IBlockDevice really read and write.  FileIO::readFile / writeFile
+ * (lib/file_io/src/file_io.cpp:24-42, 50-88) start at offset % dataSize() in their first block and stop
+ * mid-block in their last; the inode table, bitmap and directory code write a few bytes at
+ * DataLocation{block, offset}.  Entry i is one readBlock({block, offset}, length) or
+ * writeBlock(bytes, {block, offset}) of the reference (rs_block_device.cpp:25-93,
+ * crc_block_device.cpp:69-122, hamming_block_device.cpp:111-162, parity_block_device.cpp:31-88), the
+ * entries taken in list order.  Engine extension; no reference counterpart as a batch.
+ *   d_ext / ext    n entries (8-byte aligned); entry i's bytes lie at [pos, pos + len) of the packed
+ *                  caller buffer, len = min(length, dataSize() - offset) (the reference's clamp;
+ *                  offset == dataSize() is a valid access of zero bytes)
+ *   d_out / d_in   the packed caller buffer of out_bytes / in_bytes, any alignment
+ *   read   out[pos, pos + len) = payload bytes [offset, offset + len) of the block.  Status 0 / 1 / 5 as
+ *          ppfs_ecc_decode_device; with write_back != 0 the blocks with status 1 are written back into
+ *          the image (RS, Hamming) exactly as by ppfs_ecc_decode_list_*.  An entry with status 5 gets
+ *          len zero bytes.  Bytes of out that no entry covers are not written.
+ *   write  the old block is checked and fixed, payload bytes [offset, offset + len) are replaced by
+ *          in[pos, pos + len) and the block is encoded again; the bits the codec leaves undefined keep
+ *          their contents as in ppfs_ecc_encode_device.  Status 0 / 1 / 5 as ppfs_ecc_write_device; a
+ *          block with status 5 stays untouched.  len == 0 is legal: the block is checked and encoded
+ *          again with its own payload.
+ * An entry is invalid when block >= image_blocks (or block == 0xFFFFFFFF), offset > dataSize(), or
+ * pos + len > out_bytes / in_bytes.  It gets status PPFS_ECC_OUT_OF_BOUNDS (9), reads and writes
+ * nothing, and does not fail the call.  Whatever the entries say, no call touches memory outside the
+ * image and the packed buffer.
+ * Repeats: a read may repeat a block under the rules of decode_list; where two read entries overlap
+ * in out, which bytes win is unspecified.  Device writes need distinct blocks within one call, as
+ * ppfs_ecc_write_list_device does.  The host forms cut the list where a valid block repeats, so their
+ * result equals the per-block calls made in list order: two entries that write different byte ranges
+ * of one block both land.
+ * Device forms: the list calls' pipeline (gather, codec on the staging copy, scatter) in pieces of the
+ * same size on `stream`, plus a second staging allocation for the decoded payloads made at the first
+ * extent call; they wait for and are waited for by the context's list calls.  A capturing stream gets
+ * PPFS_ECC_ENOTSUP.  There is no spill argument: a shortened RS code (n < 255) is decoded as by a list
+ * decode with d_spill == NULL.  PPFS_ECC_NONE: plain byte copies under the same validity rules.
+ * d_status / status may be NULL.  Null ctx or a required pointer missing: -EINVAL before anything
+ * touches the GPU; n == 0 returns 0.
+ */
+typedef struct ppfs_ecc_extent { /* 16 bytes, no padding */
+    uint64_t pos;    /* where this entry's bytes lie in the packed caller buffer */
+    uint32_t block;  /* block index in the image */
+    uint16_t offset; /* DataLocation::offset: first payload byte */
+    uint16_t length; /* bytes asked for */
+} ppfs_ecc_extent;
+
+int ppfs_ecc_read_extents_device(ppfs_ecc_ctx* ctx, uint8_t* d_image, size_t image_blocks, const ppfs_ecc_extent* d_ext,
+    size_t n, uint8_t* d_out, size_t out_bytes, uint8_t* d_status, int write_back, void* stream);
+int ppfs_ecc_write_extents_device(ppfs_ecc_ctx* ctx, const uint8_t* d_in, size_t in_bytes, uint8_t* d_image,
+    size_t image_blocks, const ppfs_ecc_extent* d_ext, size_t n, uint8_t* d_status, void* stream);
+int ppfs_ecc_read_extents_host(ppfs_ecc_ctx* ctx, uint8_t* image, size_t image_blocks, const ppfs_ecc_extent* ext, size_t n,
+    uint8_t* out, size_t out_bytes, uint8_t* status, int write_back);
+int ppfs_ecc_write_extents_host(ppfs_ecc_ctx* ctx, const uint8_t* in, size_t in_bytes, uint8_t* image, size_t image_blocks,
+    const ppfs_ecc_extent* ext, size_t n, uint8_t* status);
+
+/*
  * Whole-image scrub: the disk-image effect of readBlock(i, 0, dataSize()) for
  * i = 0 .. nblocks-1 in index order, without the payloads -- RS writes back the corrected
  * codeword (rs_block_device.cpp:175-180), Hamming the flipped byte (hamming_block_device.cpp:41-51),

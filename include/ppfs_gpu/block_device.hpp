@@ -34,6 +34,9 @@
  * through ONE engine call; results, disk contents and log are those of the per-block loop.
  * readBlockList / writeBlockList do the same for a list of block indices in any order (the blocks
  * of a fragmented file, as FileIO's BlockIndexIterator yields them).
+ * readExtents / writeExtents take byte ranges (block, offset, length) of such blocks -- a file range
+ * that starts and ends mid-block (file_extents), or a few bytes of an inode or bitmap block -- again
+ * in one engine call.
  */
 #include <algorithm>
 #include <cstddef>
@@ -526,6 +529,68 @@ public:
         return {};
     }
 
+    // Extent extension: n byte ranges (block, offset, length) -- the form of FileIO::readFile /
+    // writeFile (file_io.cpp:24-42, 50-88: the first block from offset % dataSize(), the last one up to
+    // where the bytes run out) and of the few bytes the inode table, bitmap and directory code write at
+    // DataLocation{block, offset}.  Entry i is readBlock({block, offset}, length) into
+    // out[pos, pos + len) / writeBlock(in[pos, pos + len), {block, offset}), len = min(length,
+    // dataSize() - offset), the entries taken in list order.  err (may be null): per entry 0 or the
+    // FsError of the per-block call; a failed read's bytes become zeros.  An entry whose offset is past
+    // dataSize(), whose bytes do not fit the packed buffer or whose block index is no int gets
+    // Disk_OutOfBounds and touches nothing.
+    // This per-block loop is the definition; the codecs run one engine call per batch.
+    // DataLocation::block_index is an int: a block index that is none (0xFFFFFFFF, a caller's -1) never
+    // reaches the per-block calls, where it would turn into an address before the disk's first byte.
+    static bool extent_fits(const ppfs_ecc_extent& x, size_t ds, size_t buf_bytes, size_t& len)
+    {
+        if (x.offset > ds || x.block > 0x7FFFFFFFu)
+            return false;
+        len = std::min<size_t>(x.length, ds - x.offset);
+        return x.pos <= buf_bytes && len <= buf_bytes - x.pos;
+    }
+    virtual expected<void> readExtents(const ppfs_ecc_extent* ext, size_t n, uint8_t* out, size_t out_bytes, uint8_t* err)
+    {
+        const size_t ds = dataSize();
+        for (size_t i = 0; i < n; ++i) {
+            size_t len = 0;
+            FsError e = FsError::Disk_OutOfBounds;
+            bool failed = !extent_fits(ext[i], ds, out_bytes, len);
+            if (!failed) {
+                static_vector<uint8_t> v(out + ext[i].pos, len, 0);
+                auto r = readBlock(DataLocation((int)ext[i].block, ext[i].offset), len, v);
+                if (!r) {
+                    failed = true;
+                    e = r.error();
+                    if (e != FsError::Disk_OutOfBounds)
+                        std::memset(out + ext[i].pos, 0, len);
+                }
+            }
+            if (err)
+                err[i] = failed ? (uint8_t)e : 0;
+        }
+        return {};
+    }
+    virtual expected<void> writeExtents(const ppfs_ecc_extent* ext, size_t n, const uint8_t* in, size_t in_bytes, uint8_t* err)
+    {
+        const size_t ds = dataSize();
+        for (size_t i = 0; i < n; ++i) {
+            size_t len = 0;
+            FsError e = FsError::Disk_OutOfBounds;
+            bool failed = !extent_fits(ext[i], ds, in_bytes, len);
+            if (!failed) {
+                static_vector<uint8_t> v(const_cast<uint8_t*>(in + ext[i].pos), len, len);
+                auto r = writeBlock(v, DataLocation((int)ext[i].block, ext[i].offset));
+                if (!r) {
+                    failed = true;
+                    e = r.error();
+                }
+            }
+            if (err)
+                err[i] = failed ? (uint8_t)e : 0;
+        }
+        return {};
+    }
+
     // Whole-image scrub extension: the disk and log effect of
     // readBlock({i, 0}, dataSize()) for i in [first, first + count), in order, without the
     // payloads.  counts (may be null): blocks ok / corrected / failed; err as readBlocks.
@@ -548,6 +613,27 @@ public:
         return {};
     }
 };
+
+// The entries of a FileIO::readFile / writeFile walk (file_io.cpp:24-42, 50-88) over the blocks
+// idx[0 .. count), from the block that holds the first byte on: the first block from
+// offset_in_first_block = offset % dataSize(), whole blocks after it, the last one up to where the
+// nbytes run out; pos is the running sum, so the packed buffer is the file range itself.  One
+// readExtents / writeExtents call then does what the loop's per-block calls do.
+inline std::vector<ppfs_ecc_extent> file_extents(const block_index_t* idx, size_t count, size_t offset_in_first_block,
+    size_t nbytes, size_t data_size)
+{
+    std::vector<ppfs_ecc_extent> out;
+    if (data_size == 0 || offset_in_first_block >= data_size)
+        return out;
+    size_t done = 0;
+    for (size_t k = 0; k < count && done < nbytes; ++k) {
+        const size_t off = k == 0 ? offset_in_first_block : 0;
+        const size_t len = std::min(data_size - off, nbytes - done);
+        out.push_back(ppfs_ecc_extent { (uint64_t)done, idx[k], (uint16_t)off, (uint16_t)len });
+        done += len;
+    }
+    return out;
+}
 
 namespace detail {
     inline expected<void> disk_read(IDisk& d, size_t addr, size_t n, uint8_t* dst)
@@ -619,6 +705,44 @@ public:
             auto r = detail::disk_write(_disk, (size_t)idx[i] * _bs, payloads + i * _bs, _bs);
             if (err)
                 err[i] = r ? 0 : (uint8_t)r.error();
+        }
+        return {};
+    }
+
+    // extents: one plain copy per entry
+    expected<void> readExtents(const ppfs_ecc_extent* ext, size_t n, uint8_t* out, size_t out_bytes, uint8_t* err) override
+    {
+        for (size_t i = 0; i < n; ++i) {
+            size_t len = 0;
+            FsError e = FsError::Disk_OutOfBounds;
+            bool failed = !extent_fits(ext[i], _bs, out_bytes, len);
+            if (!failed) {
+                auto r = detail::disk_read(_disk, (size_t)ext[i].block * _bs + ext[i].offset, len, out + ext[i].pos);
+                if (!r) {
+                    failed = true;
+                    e = r.error();
+                }
+            }
+            if (err)
+                err[i] = failed ? (uint8_t)e : 0;
+        }
+        return {};
+    }
+    expected<void> writeExtents(const ppfs_ecc_extent* ext, size_t n, const uint8_t* in, size_t in_bytes, uint8_t* err) override
+    {
+        for (size_t i = 0; i < n; ++i) {
+            size_t len = 0;
+            FsError e = FsError::Disk_OutOfBounds;
+            bool failed = !extent_fits(ext[i], _bs, in_bytes, len);
+            if (!failed) {
+                auto r = detail::disk_write(_disk, (size_t)ext[i].block * _bs + ext[i].offset, in + ext[i].pos, len);
+                if (!r) {
+                    failed = true;
+                    e = r.error();
+                }
+            }
+            if (err)
+                err[i] = failed ? (uint8_t)e : 0;
         }
         return {};
     }
@@ -966,6 +1090,37 @@ public:
         return {};
     }
 
+    // Extents.  With a mapped disk image and no shortened RS code: one ppfs_ecc_*_extents_host call on
+    // the image, which cuts the batch where a block repeats, so that two entries writing different
+    // bytes of one block both land.  Otherwise the per-block loop.
+    expected<void> readExtents(const ppfs_ecc_extent* ext, size_t n, uint8_t* out, size_t out_bytes, uint8_t* err) override
+    {
+        uint8_t* img = _disk.mapped();
+        if (!img || has_spill() || !_raw || !n)
+            return IBlockDevice::readExtents(ext, n, out, out_bytes, err);
+        std::vector<uint8_t> status(n);
+        const int wb = (_type == PPFS_ECC_REED_SOLOMON || _type == PPFS_ECC_HAMMING) ? 1 : 0;
+        if (!EccEngine::ok(ppfs_ecc_read_extents_host(_eng.ctx(), img, _disk.size() / _raw, ext, n, out, out_bytes,
+                               status.data(), wb),
+                "read extents"))
+            return unexpected(FsError::Disk_IOError);
+        extent_errors(ext, n, status.data(), err);
+        return {};
+    }
+    expected<void> writeExtents(const ppfs_ecc_extent* ext, size_t n, const uint8_t* in, size_t in_bytes, uint8_t* err) override
+    {
+        uint8_t* img = _disk.mapped();
+        if (!img || has_spill() || !_raw || !n)
+            return IBlockDevice::writeExtents(ext, n, in, in_bytes, err);
+        std::vector<uint8_t> status(n);
+        if (!EccEngine::ok(ppfs_ecc_write_extents_host(_eng.ctx(), in, in_bytes, img, _disk.size() / _raw, ext, n,
+                               status.data()),
+                "write extents"))
+            return unexpected(FsError::Disk_IOError);
+        extent_errors(ext, n, status.data(), err);
+        return {};
+    }
+
     // One engine call (ppfs_ecc_scrub_host) over the disk image from block `first` to the disk
     // end: the write-back of every corrected block is applied in index order, including RS
     // bytes a shortened code writes past a block end; corrected blocks are logged in order.
@@ -1034,6 +1189,22 @@ protected:
     {
     }
 
+    // an extent call's statuses as the per-block calls report them: FsError per entry, a correction
+    // event per status 1, in list order
+    void extent_errors(const ppfs_ecc_extent* ext, size_t n, const uint8_t* status, uint8_t* err)
+    {
+        for (size_t i = 0; i < n; ++i) {
+            uint8_t e = 0;
+            if (status[i] == PPFS_ECC_OUT_OF_BOUNDS)
+                e = (uint8_t)FsError::Disk_OutOfBounds;
+            else if (status[i] == PPFS_ECC_CORRECTION_ERROR)
+                e = (uint8_t)FsError::BlockDevice_CorrectionError;
+            else if (status[i] == PPFS_ECC_CORRECTED)
+                log(ext[i].block);
+            if (err)
+                err[i] = e;
+        }
+    }
     bool has_spill() const { return _type == PPFS_ECC_REED_SOLOMON && _raw > 0 && _raw < 255; }
     size_t spill_stride() const { return 256 - std::min<size_t>(_raw, 255); }
 

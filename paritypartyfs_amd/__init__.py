@@ -3,7 +3,7 @@
 Product path: paritypartyfs_amd/csrc (HIP kernels for gfx950 + the C ABI of include/ppfs_ecc.h),
 loaded from the in-tree libppfs_ecc.so.  Python pieces:
   - ecc.EccEngine            batch encode/decode/write/scrub on HBM tensors or host arrays, contiguous
-                             ranges or block lists
+                             ranges, block lists or byte extents (block, offset, length)
   - ecc.EccGroup             the host calls sharded over several GPUs (one thread per device)
   - ecc.vote3 / vote3_host   2-of-3 bitwise voting of replicated records (superblock copies)
   - block_device.*           IBlockDevice mirror (ReedSolomon/Crc/Hamming/Parity/Raw devices)

@@ -9,6 +9,8 @@ import ctypes
 import os
 from ctypes import POINTER, c_char_p, c_int, c_longlong, c_size_t, c_uint8, c_uint32, c_uint64, c_void_p
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PPFS_ECC_LIB: an alternative build of the same library (ablation runs, tools/)
 LIB_PATH = os.environ.get("PPFS_ECC_LIB") or os.path.join(_HERE, "_lib", "libppfs_ecc.so")
@@ -42,6 +44,10 @@ EXPORTED_SYMBOLS = (
     "ppfs_ecc_decode_list_host",
     "ppfs_ecc_encode_list_host",
     "ppfs_ecc_write_list_host",
+    "ppfs_ecc_read_extents_device",
+    "ppfs_ecc_write_extents_device",
+    "ppfs_ecc_read_extents_host",
+    "ppfs_ecc_write_extents_host",
     "ppfs_ecc_scrub_host",
     "ppfs_ecc_scrub_device",
     "ppfs_vote3_device",
@@ -64,6 +70,11 @@ EXPORTED_SYMBOLS = (
     "ppfs_ecc_debug_dma_rejects",
     "ppfs_ecc_debug_dma_selftest",
 )
+
+
+# ppfs_ecc_extent: one (block, offset, length) entry of the byte-extent calls and where its bytes lie
+# in the packed caller buffer
+EXTENT_DTYPE = np.dtype([("pos", "<u8"), ("block", "<u4"), ("offset", "<u2"), ("length", "<u2")])
 
 
 class EccParams(ctypes.Structure):
@@ -159,6 +170,20 @@ def lib() -> ctypes.CDLL:
     L.ppfs_ecc_encode_list_host.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]
     L.ppfs_ecc_write_list_host.restype = c_int
     L.ppfs_ecc_write_list_host.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t]
+    # byte extents: read (ctx, image, image_blocks, ext, n, out, out_bytes, status, write_back[, stream]),
+    # write (ctx, in, in_bytes, image, image_blocks, ext, n, status[, stream])
+    L.ppfs_ecc_read_extents_device.restype = c_int
+    L.ppfs_ecc_read_extents_device.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
+                                               c_void_p, c_int, c_void_p]
+    L.ppfs_ecc_write_extents_device.restype = c_int
+    L.ppfs_ecc_write_extents_device.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
+                                                c_void_p, c_void_p]
+    L.ppfs_ecc_read_extents_host.restype = c_int
+    L.ppfs_ecc_read_extents_host.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
+                                             c_void_p, c_int]
+    L.ppfs_ecc_write_extents_host.restype = c_int
+    L.ppfs_ecc_write_extents_host.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
+                                              c_void_p]
     L.ppfs_ecc_scrub_host.restype = c_int
     L.ppfs_ecc_scrub_host.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, POINTER(c_size_t)]
     L.ppfs_ecc_scrub_device.restype = c_int

@@ -11,7 +11,10 @@ parity tests read like the reference's unit tests:
 All codec arithmetic runs in the HIP kernels (EccEngine host path); this layer only moves
 bytes between the disk and the engine and reproduces the reference's read-modify-write,
 write-back and logging order.  Batched ``readBlocks`` / ``writeBlocks`` run a contiguous
-range of blocks through one engine call (the GPU-worthwhile form).
+range of blocks through one engine call (the GPU-worthwhile form, SURVEY section 8f-1);
+``readBlockList`` / ``writeBlockList`` do so for blocks in any order, ``read_extents`` /
+``write_extents`` for byte ranges (block, offset, length) of them -- a file range built by
+``file_extents``, or a few bytes of an inode or bitmap block.
 """
 from __future__ import annotations
 
@@ -22,8 +25,8 @@ from typing import Generic, List, Optional, Tuple, TypeVar
 
 import numpy as np
 
-from ._native import (ECC_CRC, ECC_HAMMING, ECC_NONE, ECC_PARITY, ECC_REED_SOLOMON, STATUS_CORRECTED,
-                      STATUS_CORRECTION_ERROR)
+from ._native import (ECC_CRC, ECC_HAMMING, ECC_NONE, ECC_PARITY, ECC_REED_SOLOMON, EXTENT_DTYPE, STATUS_CORRECTED,
+                      STATUS_CORRECTION_ERROR, STATUS_OUT_OF_BOUNDS)
 from .ecc import EccEngine
 
 MAX_BLOCK_SIZE = 4096  # iblock_device.hpp:3
@@ -239,6 +242,72 @@ class IBlockDevice:
             if not r:
                 err[k] = int(r.error())
         return err
+
+
+    # byte extents: entry k of `ext` (EXTENT_DTYPE: pos, block, offset, length) is one readBlock /
+    # writeBlock at DataLocation(block, offset); its bytes lie at [pos, pos + len) of the packed buffer,
+    # len = min(length, dataSize() - offset).  The per-block loop is the definition; the codecs
+    # override it with one engine call.  An entry whose offset is past dataSize() or whose bytes do
+    # not fit the buffer gets Disk_OutOfBounds and touches nothing.
+    def _extent_len(self, e, buf_bytes: int) -> Optional[int]:
+        """The clamped length of an entry; None when the entry is invalid before any block is read."""
+        off, ds = int(e["offset"]), self.dataSize()
+        if off > ds:
+            return None
+        n = min(int(e["length"]), ds - off)
+        return n if int(e["pos"]) + n <= buf_bytes else None
+
+    def read_extents(self, ext: np.ndarray, out: np.ndarray) -> np.ndarray:
+        """== readBlock(DataLocation(block, offset), length) per entry, in list order, into
+        out[pos, pos + len); returns FsError-or-0 per entry.  A failed entry's bytes become zeros; bytes
+        of `out` that no entry covers keep their contents."""
+        err = np.zeros(len(ext), dtype=np.uint8)
+        for k, e in enumerate(ext):
+            n = self._extent_len(e, out.size)
+            if n is None:
+                err[k] = int(FsError.Disk_OutOfBounds)
+                continue
+            pos = int(e["pos"])
+            r = self.readBlock(DataLocation(int(e["block"]), int(e["offset"])), n)
+            if r:
+                out[pos:pos + n] = np.frombuffer(r.value(), dtype=np.uint8)
+            else:
+                err[k] = int(r.error())
+                if err[k] != int(FsError.Disk_OutOfBounds):
+                    out[pos:pos + n] = 0
+        return err
+
+    def write_extents(self, ext: np.ndarray, data: np.ndarray) -> np.ndarray:
+        """== writeBlock(data[pos, pos + len), DataLocation(block, offset)) per entry, in list order."""
+        err = np.zeros(len(ext), dtype=np.uint8)
+        for k, e in enumerate(ext):
+            n = self._extent_len(e, data.size)
+            if n is None:
+                err[k] = int(FsError.Disk_OutOfBounds)
+                continue
+            pos = int(e["pos"])
+            r = self.writeBlock(data[pos:pos + n].tobytes(), DataLocation(int(e["block"]), int(e["offset"])))
+            if not r:
+                err[k] = int(r.error())
+        return err
+
+
+def file_extents(indices, offset_in_first_block: int, nbytes: int, data_size: int) -> np.ndarray:
+    """The entries of a FileIO::readFile / writeFile walk (file_io.cpp:24-42, 50-88) over the blocks
+    `indices` (from the block that holds the first byte on): the first block from
+    offset_in_first_block = offset % dataSize(), whole blocks after it, the last one up to where the
+    nbytes run out; pos is the running sum, so the packed buffer is the file range itself."""
+    out = []
+    done = 0
+    if data_size > 0 and 0 <= offset_in_first_block < data_size:
+        for k, i in enumerate(indices):
+            if done >= nbytes:
+                break
+            off = offset_in_first_block if k == 0 else 0
+            n = min(data_size - off, nbytes - done)
+            out.append((done, int(i), off, n))
+            done += n
+    return np.array(out, dtype=EXTENT_DTYPE)
 
 
 def _list_runs(indices: List[int]):
@@ -523,6 +592,41 @@ class _EngineDevice(IBlockDevice):
                 if not w:
                     err[s + k] = int(w.error())
         return err
+
+    # ---- byte extents: one engine call on the disk's image, where the disk is one array in memory ----
+    def _mapped_image(self) -> Optional[np.ndarray]:
+        """The disk as the engine's host calls take it (a HeapDisk's array), unless a write-back may
+        run into the next block (a shortened RS code): then the per-block loop stays."""
+        buf = getattr(self._disk, "buf", None)
+        if self._has_spill() or not isinstance(buf, np.ndarray) or buf.dtype != np.uint8 or not buf.flags["C_CONTIGUOUS"]:
+            return None
+        return buf
+
+    def _extent_errors(self, ext: np.ndarray, status: np.ndarray) -> np.ndarray:
+        """FsError-or-0 per entry from the engine's statuses; a correction event per status 1, in list order."""
+        err = np.zeros(len(ext), dtype=np.uint8)
+        err[status == STATUS_CORRECTION_ERROR] = int(FsError.BlockDevice_CorrectionError)
+        err[status == STATUS_OUT_OF_BOUNDS] = int(FsError.Disk_OutOfBounds)
+        for k in np.nonzero(status == STATUS_CORRECTED)[0]:
+            self._log(int(ext["block"][k]))
+        return err
+
+    def read_extents(self, ext: np.ndarray, out: np.ndarray) -> np.ndarray:
+        image = self._mapped_image()
+        if image is None or not len(ext):
+            return super().read_extents(ext, out)
+        status = np.zeros(len(ext), dtype=np.uint8)
+        wb = self._engine.ecc_type in (ECC_REED_SOLOMON, ECC_HAMMING)
+        self._engine.read_extents_host(image, np.ascontiguousarray(ext), out, status, write_back=wb)
+        return self._extent_errors(ext, status)
+
+    def write_extents(self, ext: np.ndarray, data: np.ndarray) -> np.ndarray:
+        image = self._mapped_image()
+        if image is None or not len(ext):
+            return super().write_extents(ext, data)
+        status = np.zeros(len(ext), dtype=np.uint8)
+        self._engine.write_extents_host(data, image, np.ascontiguousarray(ext), status)
+        return self._extent_errors(ext, status)
 
     def readBlock(self, loc: DataLocation, bytes_to_read: int, capacity: Optional[int] = None) -> Expected[bytes]:
         if capacity is not None and capacity < bytes_to_read:

@@ -532,6 +532,7 @@ extern "C" void ppfs_ecc_destroy(ppfs_ecc_ctx* c)
     mem_free(c, c->d_ctr);
     mem_free(c, c->d_scratch);
     mem_free(c, c->d_list); // list calls ran on caller streams: waited for above
+    mem_free(c, c->d_ext);  // ... and so did the extent calls
     if (c->list_ev)
         (void)hipEventDestroy(c->list_ev);
     pin_free(c->h_zc, c->zc_bytes, kPinMapped);

@@ -1,6 +1,6 @@
 // ctx.hpp -- the engine context and what api.cpp (create / destroy, the device entry points, scrub,
-// vote, groups), host_path.cpp (the host-memory entry points) and list_path.cpp (the block-list
-// entry points) share.  Everything declared in
+// vote, groups), host_path.cpp (the host-memory entry points), list_path.cpp (the block-list entry
+// points) and extent_path.cpp (the byte-extent entry points) share.  Everything declared in
 // namespace ppfs here has hidden visibility: the library exports the C ABI of include/ppfs_ecc.h
 // and the kernel launchers, nothing of this.
 #pragma once
@@ -139,6 +139,10 @@ struct ppfs_ecc_ctx {
     size_t list_bytes = 0, list_status_off = 0;
     hipEvent_t list_ev = nullptr;
     bool list_ev_rec = false;
+    // byte-extent calls (extent_path.cpp): the decoded payloads of one piece and the staged index of
+    // its entries, made at the first extent call; ordered by list_ev like the rows they go with
+    uint8_t* d_ext = nullptr;
+    size_t ext_bytes = 0, ext_index_off = 0;
 };
 
 #pragma GCC visibility push(hidden)

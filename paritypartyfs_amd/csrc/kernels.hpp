@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/ppfs_ecc.h" // ppfs_ecc_extent
 #include "server_box.hpp"
 
 extern "C" {
@@ -57,4 +58,11 @@ hipError_t ppfs_scatter_blocks_launch(const uint8_t* stage, uint8_t* img, uint64
     const uint8_t* status, int mode, uint32_t nb, uint32_t raw, hipStream_t s);
 hipError_t ppfs_list_oob_launch(const uint32_t* index, uint32_t nb, uint64_t image_blocks, uint8_t* status, uint8_t* data,
     uint32_t data_bytes, hipStream_t s);
+// byte extents (extent_path.cpp): index[i] = entry i's block, or 0xFFFFFFFF when the entry is invalid
+// (image_blocks <= 0xFFFFFFFF); copy to_stage 0 = pack payload bytes into buf (zeros for status 5),
+// 1 = overlay buf's bytes onto the payloads.  stage: 16-byte aligned, stage_cap a multiple of 16.
+hipError_t ppfs_extent_index_launch(const ppfs_ecc_extent* ext, uint32_t nb, uint64_t image_blocks, uint32_t ds,
+    uint64_t buf_bytes, uint32_t* index, hipStream_t s);
+hipError_t ppfs_extent_copy_launch(int to_stage, const ppfs_ecc_extent* ext, const uint32_t* index, const uint8_t* status,
+    uint32_t nb, uint32_t ds, uint8_t* stage, uint64_t stage_cap, uint8_t* buf, uint64_t buf_bytes, hipStream_t s);
 }

@@ -17,6 +17,7 @@
 
 #include "ctx.hpp"
 #include "kernels.hpp"
+#include "list_call.hpp"
 #include "list_plan.hpp"
 
 using namespace ppfs;
@@ -34,12 +35,16 @@ bool encode_keeps_old_bits(const ppfs_ecc_ctx* c)
         || (c->p.ecc_type == PPFS_ECC_CRC && c->crc_n % 8 != 0);
 }
 
-bool has_write_back(const ppfs_ecc_ctx* c)
+} // namespace
+
+bool ppfs::has_write_back(const ppfs_ecc_ctx* c)
 {
     return c->p.ecc_type == PPFS_ECC_REED_SOLOMON || c->p.ecc_type == PPFS_ECC_HAMMING;
 }
 
-size_t piece_of(ppfs_ecc_ctx* c) { return piece_blocks(ppfs_ecc_host_chunk_blocks(c), c->raw); }
+size_t ppfs::piece_of(ppfs_ecc_ctx* c) { return piece_blocks(ppfs_ecc_host_chunk_blocks(c), c->raw); }
+
+namespace {
 
 // The staging of the list calls, made once per context (the piece size does not change)
 int ensure_stage(ppfs_ecc_ctx* c)
@@ -55,37 +60,36 @@ int ensure_stage(ppfs_ecc_ctx* c)
     return 0;
 }
 
-// One device list call: the common frame around its pieces.  The staging is shared by every stream
-// of the context, so the call first waits for the event recorded after the previous list call's
-// last kernel and records it again after its own.
-struct ListCall {
-    ppfs_ecc_ctx* c;
-    hipStream_t s;
-    void* stream;
-    size_t nblocks;
-    int begin()
-    {
-        int r = ensure_stage(c);
-        if (r)
-            return r;
-        (void)call_ordered(c, nblocks, stream);
-        if (c->list_ev_rec)
-            HIP_TRY(hipStreamWaitEvent(s, c->list_ev, 0), "list staging wait");
-        return 0;
+} // namespace
+
+// One device list call: the common frame around its pieces (list_call.hpp).  The staging is shared by
+// every stream of the context, so the call first waits for the event recorded after the previous list
+// call's last kernel and records it again after its own.
+int ppfs::ListCall::begin()
+{
+    int r = ensure_stage(c);
+    if (r)
+        return r;
+    (void)call_ordered(c, nblocks, stream);
+    if (c->list_ev_rec)
+        HIP_TRY(hipStreamWaitEvent(s, c->list_ev, 0), "list staging wait");
+    return 0;
+}
+
+int ppfs::ListCall::end(int r, const char* what)
+{
+    // also after a failure: pieces queued before it may still use the staging
+    if (hipEventRecord(c->list_ev, s) == hipSuccess) {
+        c->list_ev_rec = true;
+    } else {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(s); // nothing to order the next call by: drain instead
+        c->list_ev_rec = false;
     }
-    int end(int r, const char* what)
-    {
-        // also after a failure: pieces queued before it may still use the staging
-        if (hipEventRecord(c->list_ev, s) == hipSuccess) {
-            c->list_ev_rec = true;
-        } else {
-            (void)hipGetLastError();
-            (void)hipStreamSynchronize(s); // nothing to order the next call by: drain instead
-            c->list_ev_rec = false;
-        }
-        return call_queued(c, r, nblocks, stream, what);
-    }
-};
+    return call_queued(c, r, nblocks, stream, what);
+}
+
+namespace {
 
 int list_args(ppfs_ecc_ctx* c, const void* d_image, size_t image_blocks, const void* d_index, size_t nblocks,
     const void* d_data, bool data_required, void* stream, const char* what)

@@ -8,6 +8,7 @@
 // bits are set with one atomic OR only where a byte disagrees.
 #include <hip/hip_runtime.h>
 
+#include "../../include/ppfs_ecc.h" // ppfs_ecc_extent
 #include "dbg.hpp"
 #include <stdint.h>
 
@@ -401,6 +402,89 @@ __global__ __launch_bounds__(256) void list_oob_kernel(const uint32_t* __restric
         for (uint32_t b = 0; b < data_bytes; ++b)
             data[(uint64_t)i * data_bytes + b] = 0;
 }
+
+// ---- byte extents (extent_path.cpp): payload staging <-> the caller's packed buffer ----
+// Entry i of a piece names len = min(length, ds - offset) bytes of payload i of the staging P (stride
+// ds) and the same number at buf + pos.  An entry is valid when its block is in the image, its offset
+// is at most ds and [pos, pos + len) lies inside the buf_bytes of the caller's buffer.
+
+// index[i] = valid ? block : 0xFFFFFFFF, the index the gather, scatter and range-mark kernels above
+// and the copy kernel below go by.  One thread per entry.  image_blocks <= 0xFFFFFFFF (the launcher).
+__global__ __launch_bounds__(256) void extent_index_kernel(const ppfs_ecc_extent* __restrict__ ext, uint32_t nb,
+    uint64_t image_blocks, uint32_t ds, uint64_t buf_bytes, uint32_t* __restrict__ index)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nb || !PPFS_DBG_OK(ext + i, 16, ext, (uint64_t)nb * 16) || !PPFS_DBG_OK(index + i, 4, index, (uint64_t)nb * 4))
+        return;
+    const ppfs_ecc_extent e = ext[i];
+    bool ok = e.block < image_blocks && e.offset <= ds;
+    if (ok) {
+        const uint32_t room = ds - e.offset, len = e.length < room ? e.length : room;
+        ok = e.pos <= buf_bytes && len <= buf_bytes - e.pos;
+    }
+    index[i] = ok ? e.block : 0xFFFFFFFFu;
+}
+
+// TO_STAGE = false (pack, a read): buf[pos, pos + len) = P[i*ds + offset ...), zeros where status[i] is 5.
+// TO_STAGE = true (overlay, a write): P[i*ds + offset ...) = buf[pos, pos + len).
+// Neither side is aligned and the two are aligned differently.  The scatter kernel's shape: entry i's
+// destination is cut into the 16-byte ALIGNED windows it touches (at most K = (ds + 15) / 16 + 1), one
+// lane each; a window wholly inside the segment is one aligned 16-byte store of funnel-shifted source
+// dwords, the head and tail windows store their own bytes one by one.  So every destination byte has
+// exactly one writer and nothing outside [dst, dst + len) is written.  The funnel reads the aligned
+// dwords that cover its 16 bytes: where those would reach outside the source ([src_lo, src_hi): the
+// caller's buffer in the overlay direction, the staging's capacity in the pack direction) the window
+// takes the byte path, as the gather does next to the image's ends.  Entries staged as 0xFFFFFFFF are
+// skipped; the validity of the others (extent_index_kernel) bounds every address formed here.
+template <bool TO_STAGE>
+__global__ __launch_bounds__(256) void extent_copy_kernel(const ppfs_ecc_extent* __restrict__ ext,
+    const uint32_t* __restrict__ index, const uint8_t* __restrict__ status, uint32_t nb, uint32_t ds, uint32_t K,
+    uint8_t* stage, uint64_t stage_cap, uint8_t* buf, uint64_t buf_bytes)
+{
+    const uint64_t item = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (item >= (uint64_t)nb * K)
+        return;
+    const uint32_t i = (uint32_t)(item / K), k = (uint32_t)(item - (uint64_t)i * K);
+    if (!PPFS_DBG_OK(index + i, 4, index, (uint64_t)nb * 4) || index[i] == 0xFFFFFFFFu
+        || !PPFS_DBG_OK(ext + i, 16, ext, (uint64_t)nb * 16))
+        return;
+    const ppfs_ecc_extent e = ext[i];
+    if (e.offset >= ds)
+        return;
+    const uint32_t room = ds - e.offset, seg = e.length < room ? e.length : room;
+    uint8_t* in_stage = stage + (uint64_t)i * ds + e.offset;
+    uint8_t* in_buf = buf + e.pos;
+    uint8_t* d = TO_STAGE ? in_stage : in_buf;
+    const uint8_t* s = TO_STAGE ? in_buf : in_stage;
+    const uintptr_t win = ((uintptr_t)d & ~(uintptr_t)15) + 16u * (uintptr_t)k;
+    const uintptr_t lo = win > (uintptr_t)d ? win : (uintptr_t)d;
+    const uintptr_t hi = win + 16u < (uintptr_t)d + seg ? win + 16u : (uintptr_t)d + seg;
+    if (lo >= hi)
+        return;
+    const uint32_t off = (uint32_t)(lo - (uintptr_t)d), len = (uint32_t)(hi - lo);
+    if (!PPFS_DBG_OK(in_stage + off, len, stage, stage_cap) || !PPFS_DBG_OK(in_buf + off, len, buf, buf_bytes))
+        return;
+    bool zero = false;
+    if (!TO_STAGE && status && PPFS_DBG_OK(status + i, 1, status, nb))
+        zero = status[i] == 5u;
+    const uint8_t* src_lo = TO_STAGE ? buf : stage;
+    const uint8_t* src_hi = TO_STAGE ? buf + buf_bytes : stage + stage_cap;
+    if (len == 16u) {
+        if (zero) {
+            *(uint4*)(d + off) = make_uint4(0, 0, 0, 0);
+            return;
+        }
+        const uint8_t* p = s + off;
+        const uint8_t* a = (const uint8_t*)((uintptr_t)p & ~(uintptr_t)3);
+        const uint32_t span = ((uintptr_t)p & 3u) ? 20u : 16u;
+        if (a >= src_lo && a + span <= src_hi) {
+            *(uint4*)(d + off) = load16_funnel(p);
+            return;
+        }
+    }
+    for (uint32_t b = 0; b < len; ++b)
+        d[off + b] = zero ? (uint8_t)0 : s[off + b];
+}
 } // namespace ppfs
 
 // stage: 16-byte aligned, capacity nb * raw rounded up to 16
@@ -441,6 +525,42 @@ extern "C" hipError_t ppfs_list_oob_launch(const uint32_t* index, uint32_t nb, u
         return hipSuccess;
     hipLaunchKernelGGL(ppfs::list_oob_kernel, dim3((nb + 255u) / 256u), dim3(256), 0, s, index, nb, image_blocks, status,
         data_bytes ? data : nullptr, data_bytes);
+    return hipGetLastError();
+}
+
+// ext: 8-byte aligned; image_blocks <= 0xFFFFFFFF, so that 0xFFFFFFFF names no block
+extern "C" hipError_t ppfs_extent_index_launch(const ppfs_ecc_extent* ext, uint32_t nb, uint64_t image_blocks, uint32_t ds,
+    uint64_t buf_bytes, uint32_t* index, hipStream_t s)
+{
+    if (nb == 0)
+        return hipSuccess;
+    if (((uintptr_t)ext & 7u) || ((uintptr_t)index & 3u) || image_blocks > 0xFFFFFFFFull)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ppfs::extent_index_kernel, dim3((nb + 255u) / 256u), dim3(256), 0, s, ext, nb, image_blocks, ds,
+        buf_bytes, index);
+    return hipGetLastError();
+}
+
+// to_stage 0: pack (buf is written, status may be null), 1: overlay (buf is only read).  stage: 16-byte
+// aligned payloads at stride ds with a capacity of stage_cap >= nb * ds bytes, a multiple of 16.
+extern "C" hipError_t ppfs_extent_copy_launch(int to_stage, const ppfs_ecc_extent* ext, const uint32_t* index,
+    const uint8_t* status, uint32_t nb, uint32_t ds, uint8_t* stage, uint64_t stage_cap, uint8_t* buf, uint64_t buf_bytes,
+    hipStream_t s)
+{
+    if (nb == 0 || ds == 0 || buf_bytes == 0)
+        return hipSuccess;
+    if (((uintptr_t)ext & 7u) || ((uintptr_t)stage & 15u) || (stage_cap & 15u) || (uint64_t)nb * ds > stage_cap || !buf)
+        return hipErrorInvalidValue;
+    const uint32_t K = (ds + 15u) / 16u + 1u;
+    const uint64_t grid = ((uint64_t)nb * K + 255u) / 256u;
+    if (grid > 0x7FFFFFFFull)
+        return hipErrorInvalidValue;
+    if (to_stage)
+        hipLaunchKernelGGL(ppfs::extent_copy_kernel<true>, dim3((uint32_t)grid), dim3(256), 0, s, ext, index, status, nb, ds, K,
+            stage, stage_cap, buf, buf_bytes);
+    else
+        hipLaunchKernelGGL(ppfs::extent_copy_kernel<false>, dim3((uint32_t)grid), dim3(256), 0, s, ext, index, status, nb, ds, K,
+            stage, stage_cap, buf, buf_bytes);
     return hipGetLastError();
 }
 

@@ -229,6 +229,64 @@ class EccEngine:
         check(lib().ppfs_ecc_write_list_host(self._h, _ptr(data), _ptr(image), blocks, self._index_ptr(index),
                                              _ptr(status), n))
 
+    # ---------------- byte extents (include/ppfs_ecc.h ppfs_ecc_*_extents_*) ----------------
+    # "these byte ranges of those blocks": entry i (_native.EXTENT_DTYPE: pos, block, offset, length) is
+    # readBlock({block, offset}, length) / writeBlock(bytes, {block, offset}); its bytes lie at
+    # [pos, pos + min(length, data_size - offset)) of the packed buffer.  An invalid entry gets status 9.
+    def _extents(self, kind, ext):
+        """(extents as the call takes them, entries): a numpy EXTENT_DTYPE array (host calls; device
+        calls copy it to the GPU) or, for device calls, a CUDA uint8 tensor of 16 bytes per entry."""
+        if isinstance(ext, np.ndarray):
+            if ext.dtype != _native.EXTENT_DTYPE or ext.ndim != 1 or not ext.flags["C_CONTIGUOUS"]:
+                raise ValueError("extents: a C-contiguous 1-D numpy array of EXTENT_DTYPE")
+            return ext, int(ext.size)
+        if kind != "device":
+            raise ValueError("extents: host entry points take a numpy array of EXTENT_DTYPE")
+        import torch
+
+        if not getattr(ext, "is_cuda", False) or ext.dtype != torch.uint8 or not ext.is_contiguous() or ext.dim() != 1 \
+                or ext.numel() % 16 or ext.data_ptr() % 8:
+            raise ValueError("extents: a contiguous 1-D CUDA uint8 tensor of 16 bytes per entry, 8-byte aligned")
+        return ext, int(ext.numel()) // 16
+
+    def _extent_check(self, kind, image, ext, buf, status):
+        """(extents, entries, image blocks, bytes of the packed buffer) after the buffer checks."""
+        ext, n = self._extents(kind, ext)
+        if image is None:
+            raise ValueError("image: required")
+        _need("image", image, 0, kind)
+        _need("buffer", buf, 0, kind)
+        _need("status", status, n, kind)
+        _ptr(image), _ptr(buf), _ptr(status)  # contiguous uint8
+        if kind == "device" and isinstance(ext, np.ndarray):
+            import torch
+
+            ext = torch.from_numpy(ext.view(np.uint8).copy()).cuda()
+            self._ext_keep = ext  # the queued kernels read it: alive until the next such call
+        return ext, n, _size(image) // self.raw_block_size, 0 if buf is None else _size(buf)
+
+    def read_extents(self, image, ext, out, status=None, write_back: bool = True, stream=None) -> None:
+        ext, n, blocks, nbytes = self._extent_check("device", image, ext, out, status)
+        check(lib().ppfs_ecc_read_extents_device(self._h, _ptr(image), blocks, self._index_ptr(ext), n, _ptr(out), nbytes,
+                                                 _ptr(status), int(bool(write_back)), _stream_handle(stream)))
+
+    def write_extents(self, data, image, ext, status=None, stream=None) -> None:
+        ext, n, blocks, nbytes = self._extent_check("device", image, ext, data, status)
+        check(lib().ppfs_ecc_write_extents_device(self._h, _ptr(data), nbytes, _ptr(image), blocks, self._index_ptr(ext), n,
+                                                  _ptr(status), _stream_handle(stream)))
+
+    def read_extents_host(self, image: np.ndarray, ext: np.ndarray, out: Optional[np.ndarray],
+                          status: Optional[np.ndarray] = None, write_back: bool = True) -> None:
+        ext, n, blocks, nbytes = self._extent_check("host", image, ext, out, status)
+        check(lib().ppfs_ecc_read_extents_host(self._h, _ptr(image), blocks, self._index_ptr(ext), n, _ptr(out), nbytes,
+                                               _ptr(status), int(bool(write_back))))
+
+    def write_extents_host(self, data: Optional[np.ndarray], image: np.ndarray, ext: np.ndarray,
+                           status: Optional[np.ndarray] = None) -> None:
+        ext, n, blocks, nbytes = self._extent_check("host", image, ext, data, status)
+        check(lib().ppfs_ecc_write_extents_host(self._h, _ptr(data), nbytes, _ptr(image), blocks, self._index_ptr(ext), n,
+                                                _ptr(status)))
+
     # ---------------- whole-image scrub (SURVEY 8f-3) ----------------
     def scrub_host(self, image: np.ndarray, nblocks: Optional[int] = None, status: Optional[np.ndarray] = None):
         """readBlock(i) for every block of a host image, in order, for its write-back effect only

@@ -8,10 +8,19 @@ For RS(255,249) and RS(255,223) at 2^20 blocks with one injected byte error per 
 and the two ratios list / contiguous.  Times are medians of --reps runs between stream events, the
 image re-corrupted (untimed) before every run.  Recorded, not gating: DESIGN.md "Block lists".
 
+With --extents, for RS(255,249) only, the two byte-extent legs beside their yardsticks of the same build:
+  read_extents, file shape           file_extents over the permuted list from byte 100 of the first block
+  decode_list, same permutation      the yardstick of the read
+  device copy of the packed bytes    what the pack's traffic costs as a plain copy
+  write_extents, 64 bytes at 32      one 64-byte segment at offset 32 of every permuted block
+  write_list, same permutation       the yardstick of the write
+Recorded, not gating: DESIGN.md "Byte extents".
+
 Every codec is measured in a child process of its own under a time limit; the first child that
 fails ends the run.
 
     python tools/bench_list.py [--blocks 1048576 --reps 7 --out profiles/list_io.json]
+    python tools/bench_list.py --extents [--out profiles/extent_io.json]
 """
 import argparse
 import json
@@ -78,20 +87,102 @@ def worker(bs: int, t: int, blocks: int, reps: int) -> dict:
     return res
 
 
+def worker_extents(bs: int, t: int, blocks: int, reps: int) -> dict:
+    import numpy as np
+    import torch
+
+    from paritypartyfs_amd import ECC_REED_SOLOMON, EccEngine, device_copy, inject_bytes
+    from paritypartyfs_amd._native import EXTENT_DTYPE
+    from paritypartyfs_amd.block_device import file_extents
+
+    torch.cuda.set_device(0)
+    eng = EccEngine(ECC_REED_SOLOMON, bs, t)
+    n, k = eng.raw_block_size, eng.data_size
+    g = torch.Generator(device="cuda").manual_seed(20240611)
+    data = torch.randint(0, 256, (blocks * k,), dtype=torch.uint8, device="cuda", generator=g)
+    image = torch.empty(blocks * n, dtype=torch.uint8, device="cuda")
+    eng.encode(data, image)
+    pos = torch.randint(0, n, (blocks,), dtype=torch.uint8, device="cuda", generator=g)
+    val = torch.randint(1, 256, (blocks,), dtype=torch.uint8, device="cuda", generator=g)
+    st = torch.empty(blocks, dtype=torch.uint8, device="cuda")
+    perm_np = np.random.default_rng(7).permutation(blocks).astype(np.uint32)
+    perm = torch.from_numpy(perm_np.view(np.int32)).cuda()
+
+    def timed(fn, corrupt=True):
+        ms = []
+        for r in range(reps + 2):  # two warm-up runs
+            if corrupt:
+                inject_bytes(image, n, pos, val, xor=True)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if r >= 2:
+                ms.append(a.elapsed_time(b))
+        return statistics.median(ms) * 1e3  # us
+
+    # the read: a file over every block of the list, from byte 100 of its first block to the middle of its last
+    off0 = 100
+    nbytes = (k - off0) + (blocks - 2) * k + k // 2
+    r_ext = file_extents(perm_np, off0, nbytes, k)
+    assert len(r_ext) == blocks
+    r_ext_d = torch.from_numpy(r_ext.view(np.uint8)).cuda()
+    packed = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    payloads = torch.empty_like(data)
+    copy_dst = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    res = {
+        "read_extents_us": timed(lambda: eng.read_extents(image, r_ext_d, packed, st, write_back=True)),
+        "decode_list_us": timed(lambda: eng.decode_list(image, perm, payloads, st, write_back=True)),
+        "pack_copy_us": timed(lambda: device_copy(copy_dst, payloads, nbytes), corrupt=False),
+    }
+    want = data.view(blocks, k)[perm.long()].reshape(-1)
+    assert int(st.max()) <= 1 and torch.equal(payloads, want), "decode_list results differ from the payloads"
+    assert torch.equal(packed, want[off0:off0 + nbytes]), "read_extents results differ from the file range"
+    # the write: 64 bytes at offset 32 of every block of the list
+    seg, at = 64, 32
+    w_ext = np.zeros(blocks, EXTENT_DTYPE)
+    w_ext["pos"], w_ext["block"], w_ext["offset"], w_ext["length"] = np.arange(blocks, dtype=np.uint64) * seg, perm_np, at, seg
+    w_ext_d = torch.from_numpy(w_ext.view(np.uint8)).cuda()
+    fresh = torch.randint(0, 256, (blocks * seg,), dtype=torch.uint8, device="cuda", generator=g)
+    res["write_extents_us"] = timed(lambda: eng.write_extents(fresh, image, w_ext_d, st))
+    assert int(st.max()) <= 1
+    eng.decode_list(image, perm, payloads, st, write_back=False)
+    got = payloads.view(blocks, k)
+    assert int(st.max()) == 0 and torch.equal(got[:, at:at + seg].reshape(-1), fresh), "write_extents: segments differ"
+    keep = torch.ones(k, dtype=torch.bool, device="cuda")
+    keep[at:at + seg] = False
+    assert torch.equal(got[:, keep], want.view(blocks, k)[:, keep]), "write_extents: bytes outside the segments changed"
+    res["write_list_us"] = timed(lambda: eng.write_list(want, image, perm, st))
+    assert int(st.max()) <= 1
+    res["read_over_list"] = res["read_extents_us"] / res["decode_list_us"]
+    res["write_over_list"] = res["write_extents_us"] / res["write_list_us"]
+    # the issue's budget of the read: the list decode, the pack's traffic as a copy, 20 % for the launches
+    res["read_budget_us"] = 1.2 * (res["decode_list_us"] + res["pack_copy_us"])
+    res["read_within_budget"] = res["read_extents_us"] <= res["read_budget_us"]
+    res.update(entries=blocks, raw_block_size=n, data_size=k, reps=reps, image_bytes=blocks * n, read_bytes=nbytes,
+               read_offset_in_first_block=off0, write_segment_bytes=seg, write_segment_offset=at,
+               piece_blocks=eng.host_chunk_blocks() & ~1023, kernel=eng.kernel_name,
+               device=torch.cuda.get_device_name(0))
+    return res
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--blocks", type=int, default=1 << 20)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=None, help="write the records here as one JSON document")
+    ap.add_argument("--extents", action="store_true", help="the byte-extent legs (RS(255,249)) instead of the list legs")
     ap.add_argument("--worker", nargs=2, type=int, metavar=("BLOCK_SIZE", "T"), help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.worker:
-        print(json.dumps(worker(a.worker[0], a.worker[1], a.blocks, a.reps)))
+        run = worker_extents if a.extents else worker
+        print(json.dumps(run(a.worker[0], a.worker[1], a.blocks, a.reps)))
         return 0
     records = []
-    for name, bs, t in CODECS:
+    for name, bs, t in (CODECS[:1] if a.extents else CODECS):
         cmd = ["timeout", "-k", "10", str(STEP_TIMEOUT_S), sys.executable, os.path.abspath(__file__), "--blocks",
-               str(a.blocks), "--reps", str(a.reps), "--worker", str(bs), str(t)]
+               str(a.blocks), "--reps", str(a.reps), "--worker", str(bs), str(t)] + (["--extents"] if a.extents else [])
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
@@ -102,8 +193,10 @@ def main() -> int:
         print(json.dumps(rec))
     if a.out:
         with open(a.out, "w") as f:
-            json.dump({"what": "block-list decode vs contiguous decode, one byte error per block (tools/bench_list.py)",
-                       "records": records}, f, indent=1)
+            what = ("byte-extent read / write vs the list decode / list write of the same build, one byte error per block "
+                    "(tools/bench_list.py --extents)" if a.extents else
+                    "block-list decode vs contiguous decode, one byte error per block (tools/bench_list.py)")
+            json.dump({"what": what, "records": records}, f, indent=1)
             f.write("\n")
     return 0
 
