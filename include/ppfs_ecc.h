@@ -169,6 +169,13 @@ size_t ppfs_ecc_host_chunk_blocks(ppfs_ecc_ctx* ctx);
  *     index the call stays memory-safe, but which payload ends up in the block is unspecified.
  *   - decode may repeat an index: every copy gets the same payload.  With write_back, a repeated
  *     entry's status is that of a read either before or after another copy's write-back (1 or 0).
+ *     On the direct path (below) a copy's read may also see another copy's write-back partly applied.
+ *     For a block within the code's capability (at most t byte errors), and for one whose
+ *     miscorrection lands on a codeword, every such view is within t of the same codeword: every copy
+ *     gets the same payload, each status is 1 or 0, at least one copy reports 1 and the image ends
+ *     corrected.  Only for a block beyond the capability whose fix lands on no codeword, listed more
+ *     than once with write_back, may the copies of one call differ in payload and status (on the
+ *     staged path they already differ across pieces).
  *   - the host forms process the list in runs without a repeated index, so their result equals the
  *     per-block calls made in list order: the first entry of a corrupted block reports 1, a later
  *     one reads the written-back block; for encode / write the last payload listed wins.
@@ -180,9 +187,23 @@ size_t ppfs_ecc_host_chunk_blocks(ppfs_ecc_ctx* ctx);
  * call waits for the previous list call of that context, whichever stream it ran on.  A stream that
  * is capturing a hipGraph gets PPFS_ECC_ENOTSUP.  Null ctx or required pointer: -EINVAL, checked
  * before anything touches the GPU; nblocks == 0 returns 0.
+ * Direct list decode: a context of RS(255, 255 - 2t) with 2t <= 8 (block_size >= 255, t = 1..4) decodes
+ * a list in ONE kernel (ppfs_ecc_list_kernel_name: "rs255-wg-list-lds"): the codec kernel reads each
+ * listed row straight from the image, writes corrected bytes in place at image + index[i] * 255 + pos and
+ * emits payloads and statuses in list order.  No staging copy, no pieces, and no ordering against the
+ * context's other list calls: two such decodes on different streams run side by side like two
+ * contiguous calls (that ordering only ever protected the staging, never results).  The image may have
+ * any alignment; nothing outside [d_image, d_image + image_blocks * 255) is read or written.  Encode
+ * and write lists, every other codec, and a call whose d_data / d_status break the 16-byte rule keep
+ * the staged path above; so does a context created while PPFS_ECC_LIST_DIRECT=0 is in the
+ * environment (A/B measurements).  The extent reads below use the same kernel per piece for such a
+ * context.
  * Host forms: same arguments with host pointers and no stream; they return when the results are in
  * host memory.
  */
+/* How ctx decodes a device list: "rs255-wg-list-lds" (the direct kernel) or "gather-stage-scatter" (the
+ * staged pipeline); "" for a null ctx.  Engine extension, no reference counterpart. */
+const char* ppfs_ecc_list_kernel_name(const ppfs_ecc_ctx* ctx);
 int ppfs_ecc_decode_list_device(ppfs_ecc_ctx* ctx, uint8_t* d_image, size_t image_blocks, const uint32_t* d_index,
     size_t nblocks, uint8_t* d_data, uint8_t* d_status, int write_back, uint8_t* d_spill, void* stream);
 int ppfs_ecc_encode_list_device(ppfs_ecc_ctx* ctx, const uint8_t* d_data, uint8_t* d_image, size_t image_blocks,
@@ -229,7 +250,10 @@ int ppfs_ecc_write_list_host(ppfs_ecc_ctx* ctx, const uint8_t* data, uint8_t* im
  * of one block both land.
  * Device forms: the list calls' pipeline (gather, codec on the staging copy, scatter) in pieces of the
  * same size on `stream`, plus a second staging allocation for the decoded payloads made at the first
- * extent call; they wait for and are waited for by the context's list calls.  A capturing stream gets
+ * extent call; they wait for and are waited for by the context's staged list calls.  A context that
+ * decodes lists directly (ppfs_ecc_list_kernel_name) reads a piece with that one kernel in place of the
+ * gather, decode, scatter and range marks; the payload staging, the pieces and their ordering stay.
+ * A capturing stream gets
  * PPFS_ECC_ENOTSUP.  There is no spill argument: a shortened RS code (n < 255) is decoded as by a list
  * decode with d_spill == NULL.  PPFS_ECC_NONE: plain byte copies under the same validity rules.
  * d_status / status may be NULL.  Null ctx or a required pointer missing: -EINVAL before anything

@@ -139,6 +139,9 @@ struct ppfs_ecc_ctx {
     size_t list_bytes = 0, list_status_off = 0;
     hipEvent_t list_ev = nullptr;
     bool list_ev_rec = false;
+    // list decodes go through the one-kernel direct path (rs_wg_list.hpp): RS(255, 255-2t), 2t <= 8,
+    // unless PPFS_ECC_LIST_DIRECT=0 was set when the context was created (list_path.cpp)
+    bool list_direct = false;
     // byte-extent calls (extent_path.cpp): the decoded payloads of one piece and the staged index of
     // its entries, made at the first extent call; ordered by list_ev like the rows they go with
     uint8_t* d_ext = nullptr;
@@ -184,6 +187,13 @@ inline bool rs_wb_direct(const ppfs_ecc_ctx* c)
 // contexts only; nullptr: into d_raw) (api.cpp)
 int decode_device_to(ppfs_ecc_ctx* c, uint8_t* d_raw, uint8_t* d_data, uint8_t* d_status, size_t nblocks, int write_back,
     uint8_t* d_spill, void* stream, uint8_t* wb_dst);
+
+// The direct list decode (list_path.cpp; c->list_direct contexts): queues one rs_wg_list.hpp launch on s
+// for "entry i = image row index[i]" and the memset of the spill records, nothing else -- the caller
+// frames it (call_ordered / call_queued).  list_direct_args: do d_data / d_status meet its 16-byte rule?
+bool list_direct_args(const ppfs_ecc_ctx* c, const void* d_data, const void* d_status);
+int decode_list_direct(ppfs_ecc_ctx* c, uint8_t* d_image, size_t image_blocks, const uint32_t* d_index, size_t nblocks,
+    uint8_t* d_data, uint8_t* d_status, int write_back, uint8_t* d_spill, hipStream_t s);
 
 // What every device entry point does around the work it queues on a caller's stream (api.cpp), for
 // the entry points outside api.cpp: call_ordered before the first launch (after the last call on the

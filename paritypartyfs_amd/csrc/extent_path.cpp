@@ -14,6 +14,10 @@
 //          the caller's buffer -> range marks
 //   write  index -> gather -> decode(rows -> P) -> overlay the caller's bytes onto P ->
 //          write(P, rows, status) -> scatter (status other than 5) -> range marks
+// A context that decodes lists directly (ctx.hpp list_direct; RS(255, 255-2t), 2t <= 8) reads a piece as
+//   read   index -> list decode(image, index -> P, status, write_back) -> pack P
+// one kernel for the gather, decode, scatter and range marks: the staged index 0xFFFFFFFF of an invalid
+// entry comes out of it as status 9 and a zero payload.  P, the piece size and list_ev stay.
 // Host forms: the list is cut into runs without a repeated valid block, each run is gathered on the
 // CPU, goes through the contiguous host calls and is copied back.  The arithmetic of both is in
 // extent_plan.hpp.
@@ -80,7 +84,8 @@ struct Pieces {
     {
         return d_status && (((uintptr_t)d_status & 15u) == 0) ? d_status + off : own_status;
     }
-    int status_out(uint8_t* st, uint8_t* d_status, size_t off, uint32_t nb, hipStream_t s) const
+    // marks: the range marks are still to be made (the direct list decode made them itself)
+    int status_out(uint8_t* st, uint8_t* d_status, size_t off, uint32_t nb, hipStream_t s, bool marks = true) const
     {
         if (!d_status)
             return 0;
@@ -89,6 +94,8 @@ struct Pieces {
             if (r)
                 return r;
         }
+        if (!marks)
+            return 0;
         return check_hip(ppfs_list_oob_launch(idx, nb, blocks, d_status + off, nullptr, 0, s), "extent range marks");
     }
 };
@@ -115,6 +122,15 @@ extern "C" int ppfs_ecc_read_extents_device(ppfs_ecc_ctx* c, uint8_t* d_image, s
             const ppfs_ecc_extent* ex = d_ext + off;
             uint8_t* st = p.status_for(d_status, off); // the pack selects by status: always one
             r = check_hip(ppfs_extent_index_launch(ex, nb, p.blocks, ds, out_bytes, p.idx, call.s), "extent index");
+            if (!r && c->list_direct) { // P and st are 16-byte aligned (ext_stage_layout, status_for)
+                r = decode_list_direct(c, d_image, p.blocks, p.idx, nb, p.P, st, wb ? 1 : 0, nullptr, call.s);
+                if (!r)
+                    r = check_hip(ppfs_extent_copy_launch(0, ex, p.idx, st, nb, ds, p.P, p.P_cap, d_out, out_bytes, call.s),
+                        "extent pack");
+                if (!r)
+                    r = p.status_out(st, d_status, off, nb, call.s, false);
+                continue;
+            }
             if (!r)
                 r = check_hip(ppfs_gather_blocks_launch(d_image, p.blocks, p.idx, nb, raw, p.rows, call.s), "extent gather");
             if (!r)

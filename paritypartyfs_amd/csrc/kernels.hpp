@@ -24,6 +24,10 @@ hipError_t ppfs_rs_server_launch(int t2, ppfs::SrvBox* box, uint8_t* zc, uint64_
     uint32_t gen, uint32_t idle_us, hipStream_t s);
 hipError_t ppfs_rs_fast_decode(int t2, uint8_t* r, uint8_t* d, uint8_t* st, uint64_t nb, const uint8_t* tab, int wb,
     hipStream_t s, uint32_t* ctr, uint32_t* ctr_clear, uint8_t* wb_dst);
+// RS(255, 255-2t), 2t <= 8: the list decode in one kernel (rs_wg_list.hpp); entry i = image row index[i],
+// d (16-byte aligned or null) and st (or null) in list order
+hipError_t ppfs_rs_list_decode(int t2, uint8_t* image, uint64_t image_blocks, const uint32_t* index, uint8_t* d, uint8_t* st,
+    uint64_t nb, const uint8_t* tab, int wb, hipStream_t s);
 hipError_t ppfs_rs_generic_encode(const uint8_t* d, uint8_t* r, uint64_t nb, int n, int t2, const uint8_t* tab,
     hipStream_t s);
 hipError_t ppfs_rs_generic_decode(uint8_t* r, uint8_t* d, uint8_t* st, uint8_t* spill, uint64_t nb, int n, int t2,

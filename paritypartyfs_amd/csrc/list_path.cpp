@@ -7,6 +7,10 @@
 // (vote.hip gather_blocks_kernel), the unchanged codec kernels run on that copy through the
 // contiguous entry points, and the rows that changed are scattered back (scatter_blocks_kernel).
 // Lists longer than one piece (list_plan.hpp piece_blocks) go piece by piece on the caller's stream.
+// RS(255, 255-2t), 2t <= 8 decodes a list in one kernel instead (rs_wg_list.hpp: the rows are fetched
+// from the image by the codec kernel's loader and corrected in place): no staging, no pieces, no
+// list_ev, framed like a contiguous device call.  PPFS_ECC_LIST_DIRECT=0 at ppfs_ecc_create keeps such
+// a context on the staged path.
 // Host forms: the list is cut into runs without a repeated index, each run is gathered on the CPU
 // and handed to the contiguous host call, and the rows that changed are copied back.
 // The arithmetic of both is in list_plan.hpp.
@@ -89,6 +93,26 @@ int ppfs::ListCall::end(int r, const char* what)
     return call_queued(c, r, nblocks, stream, what);
 }
 
+// ---------------------------------------------------------------------------------------
+// The direct list decode (ctx.hpp)
+// ---------------------------------------------------------------------------------------
+bool ppfs::list_direct_args(const ppfs_ecc_ctx* c, const void* d_data, const void* d_status)
+{
+    // the rule of the contiguous RS decode (ppfs_ecc_decode_device); a call that breaks it takes the
+    // staged path, which refuses it as before
+    return c->list_direct && (((uintptr_t)d_data | (uintptr_t)d_status) & 15u) == 0;
+}
+
+int ppfs::decode_list_direct(ppfs_ecc_ctx* c, uint8_t* d_image, size_t image_blocks, const uint32_t* d_index,
+    size_t nblocks, uint8_t* d_data, uint8_t* d_status, int write_back, uint8_t* d_spill, hipStream_t s)
+{
+    if (d_spill) // n = 255: one count byte per entry, always zero (a write-back never passes the block's end)
+        HIP_TRY(hipMemsetAsync(d_spill, 0, nblocks, s), "list spill");
+    return check_hip(ppfs_rs_list_decode(c->rs_t2, d_image, image_blocks, d_index, d_data, d_status, nblocks, c->d_tables,
+                         write_back ? 1 : 0, s),
+        "rs list decode");
+}
+
 namespace {
 
 int list_args(ppfs_ecc_ctx* c, const void* d_image, size_t image_blocks, const void* d_index, size_t nblocks,
@@ -111,6 +135,12 @@ extern "C" int ppfs_ecc_decode_list_device(ppfs_ecc_ctx* c, uint8_t* d_image, si
     int r = list_args(c, d_image, image_blocks, d_index, nblocks, d_data, false, stream, "decode list: null argument");
     if (r || nblocks == 0)
         return r;
+    if (list_direct_args(c, d_data, d_status)) {
+        (void)call_ordered(c, nblocks, stream);
+        r = decode_list_direct(c, d_image, image_blocks, d_index, nblocks, d_data, d_status, write_back, d_spill,
+            (hipStream_t)stream);
+        return call_queued(c, r, nblocks, stream, "decode list (async)");
+    }
     ListCall call { c, (hipStream_t)stream, stream, nblocks };
     if ((r = call.begin()))
         return r;

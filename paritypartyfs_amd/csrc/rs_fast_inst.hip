@@ -3,12 +3,14 @@
 // (register prefetch, 8-wave and wave-independent encodes, image encodes, deeper rings, the nibble
 // pair kernels) live in tools/ablations/ and are built by tools/build_alt.sh.
 //   2t <= 8      rs_wg_tk.hpp ticket-counter encode / decode (every context hands a counter set
-//                for its first 16 streams, api.cpp ctr_for); rs_wg.hpp static-walk kernels otherwise
+//                for its first 16 streams, api.cpp ctr_for); rs_wg.hpp static-walk kernels otherwise;
+//                rs_wg_list.hpp the block-list decode (rows fetched from the image by the kernel)
 //   8 < 2t <= 16 rs_fast.hpp lane-per-block kernels; 2t = 16 encodes with rs_pair.hpp's solo image kernel
 //   2t = 32      rs_bs.hpp byte-slice kernels (cfg5, RS(255,223))
 #include "rs_fast.hpp"
 #include "rs_wg.hpp"
 #include "rs_wg_tk.hpp"
+#include "rs_wg_list.hpp"
 #include "rs_pair.hpp"
 #include "rs_bs.hpp"
 #include "launch.hpp"
@@ -141,6 +143,17 @@ extern "C" hipError_t PPFS_CAT(ppfs_rs_fast_decode_t, PPFS_T2)(uint8_t* r, uint8
 #endif
     return hipGetLastError();
 }
+#if PPFS_T2 <= 8
+// the block-list decode (rs_wg_list.hpp; list_path.cpp): entry i = image row index[i].  A static
+// walk over the decode's persistent grid, so it takes no ticket-counter set.
+extern "C" hipError_t PPFS_CAT(ppfs_rs_list_decode_t, PPFS_T2)(uint8_t* image, uint64_t image_blocks, const uint32_t* index,
+    uint8_t* d, uint8_t* st, uint64_t nb, const uint8_t* tab, int wb, hipStream_t s)
+{
+    PPFS_LAUNCH((wg::rs_wg_decode_list_kernel<PPFS_T2, DEC_WPC, 1>), dim3(rs_tile_grid(nb, DEC_WPC)), dim3(256), 0, s, image,
+        image_blocks, index, d, st, nb, tab, wb);
+    return hipGetLastError();
+}
+#endif
 PPFS_DBG_ACCESSOR(PPFS_CAT(ppfs_dbg_faults_rs_t, PPFS_T2))
 
 // resident small-batch servers (host_path.cpp server_call): 2t <= 8 rs_wg.hpp rs_wg_server_kernel,

@@ -315,6 +315,27 @@ extern "C" hipError_t ppfs_rs_fast_decode(int t2, uint8_t* r, uint8_t* d, uint8_
     }
 }
 
+// block-list decode in one kernel (rs_wg_list.hpp), 2t <= 8
+#define PPFS_RS_LIST_CASES(X) X(2) X(4) X(6) X(8)
+#define X(T)                                                                                                           \
+    extern "C" hipError_t ppfs_rs_list_decode_t##T(uint8_t*, uint64_t, const uint32_t*, uint8_t*, uint8_t*, uint64_t,  \
+        const uint8_t*, int, hipStream_t);
+PPFS_RS_LIST_CASES(X)
+#undef X
+extern "C" hipError_t ppfs_rs_list_decode(int t2, uint8_t* image, uint64_t image_blocks, const uint32_t* index, uint8_t* d,
+    uint8_t* st, uint64_t nb, const uint8_t* tab, int wb, hipStream_t s)
+{
+    switch (t2) {
+#define X(T)                                                                                                           \
+    case T:                                                                                                            \
+        return ppfs_rs_list_decode_t##T(image, image_blocks, index, d, st, nb, tab, wb, s);
+        PPFS_RS_LIST_CASES(X)
+#undef X
+    default:
+        return hipErrorInvalidValue;
+    }
+}
+
 // resident small-batch servers (2t <= 8: segment-layout tables; 10, 16: lane-per-block; 32: pair layout)
 #define PPFS_RS_SERVER_CASES(X) X(2) X(4) X(6) X(8) X(10) X(16) X(32)
 #define X(T)                                                                                                           \

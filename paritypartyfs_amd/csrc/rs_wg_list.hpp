@@ -1,0 +1,248 @@
+#pragma once
+// rs_wg_list.hpp -- the block-list decode of RS(255, 255-2t), 2t <= 8, in one kernel: entry i of the
+// list is image row index[i], fetched straight from the image into the LDS tile.  No staging copy, no
+// scatter, no range-mark pass (list_path.cpp's staged pipeline, which every other codec keeps).
+//
+// The static-walk decode of rs_wg.hpp with another loader: the LDS tile has the contiguous kernel's
+// layout (64 rows packed at 255 B behind PAD), so the remainder, correction and emission phases
+// are that kernel's, unchanged; the correction takes the image as its write-back target and
+// index[i] as its block, so corrected bytes go in place at image + index[i] * 255 + pos, and
+// payloads and statuses come out in list order.
+//
+// Loader.  LDS-DMA cannot serve: a listed row starts at any byte of the image.  Each thread owns 4 of
+// the tile's 1,020 16-byte windows (as dma_tile does) and reads each by the plan of list_fetch.hpp:
+// the aligned dwords covering the window's bytes of one row, funnel-shifted (funnel.hpp); two such
+// reads merged by a byte mask for the 60 windows that hold a row boundary; single bytes where those
+// dwords would leave the image (next to its two ends only).  The next tile's windows are
+// read into registers (4 x uint4) after barrier A and stored into the other tile buffer after this
+// tile's emission reads.  The tile's 64 indices are one coalesced load of wave 1 and wait in a
+// 256-byte LDS slot from one tile earlier, so a window's address depends on no global load of the
+// same iteration.  The compiler places the vmcnt waits (these are ordinary register loads).
+//
+// An entry index[i] >= image_blocks (0xFFFFFFFF among them) is never dereferenced: its LDS row is
+// zeros -- a valid codeword, so the payload comes out zero by itself -- wave 0 stores status 9
+// (PPFS_ECC_OUT_OF_BOUNDS) for it, and it takes no write-back.
+#include "funnel.hpp"
+#include "list_fetch.hpp"
+#include "rs_wg.hpp"
+
+namespace ppfs {
+namespace wg {
+
+__device__ __forceinline__ uint4 and4(uint4 a, bool keep)
+{
+    const uint32_t m = keep ? ~0u : 0u;
+    return make_uint4(a.x & m, a.y & m, a.z & m, a.w & m);
+}
+
+// window w of the tile, or window 0 for the 4 slots past the tile's 1,020 (k = 3, tid >= 252), which
+// are fetched like any other and never stored
+__device__ __forceinline__ uint32_t list_window(uint32_t tid, int k)
+{
+    const uint32_t w = tid + 256u * k;
+    return k < 3 || w < listfetch::TILE_WINDOWS ? w : 0u;
+}
+
+// The thread's 4 windows of the tile whose 64 entries are slot[0..63] (window tid + 256 k), into
+// registers.  Straight-line on purpose: the plans of all 8 parts (a window's piece of its row, and of
+// the next row where it holds a boundary), then all the loads, then the shifts and merges, so one
+// round trip to memory serves the whole tile.  A part that is not read through the funnel (no block,
+// an interior window's second part, a BYTES part) loads from `safe` instead, the engine's own tables,
+// and the result is dropped.  Returns the windows that hold a BYTES part (bit k): those are not taken
+// from v[k] but written byte by byte by list_fetch_slow.
+__device__ __forceinline__ uint32_t list_fetch_tile(uint4 (&v)[4], const uint8_t* img, uint64_t image_blocks,
+    const uint32_t* slot, uint32_t tid, const uint8_t* safe)
+{
+    const uint64_t base = (uint64_t)(uintptr_t)img;
+    [[maybe_unused]] const uint64_t img_bytes = image_blocks * listfetch::ROW;
+    uint32_t n0[4], sa[4], sb[4], slow = 0;
+    Funnel5 ra[4], rb[4];
+    bool fa[4], fb[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const listfetch::Window x = listfetch::window_of(list_window(tid, k));
+        const listfetch::Part pa = listfetch::part_a(base, image_blocks, x, slot[x.row]);
+        const listfetch::Part pb = listfetch::part_b(base, image_blocks, x, slot[x.row + (x.n0 < 16u ? 1u : 0u)]);
+        // addresses formed from the image pointer, so the loads are global loads
+        const uint8_t* aa = img + (pa.a - base);
+        const uint8_t* ab = img + (pb.a - base);
+        fa[k] = pa.kind == listfetch::FUNNEL && PPFS_DBG_OK(aa, pa.span, img, img_bytes);
+        fb[k] = pb.kind == listfetch::FUNNEL && PPFS_DBG_OK(ab, pb.span, img, img_bytes);
+        ra[k] = funnel_load5((const uint32_t*)(fa[k] ? aa : safe));
+        rb[k] = funnel_load5((const uint32_t*)(fb[k] ? ab : safe));
+        n0[k] = x.n0;
+        sa[k] = (uint32_t)pa.p0 & 3u;
+        sb[k] = (uint32_t)pb.p0 & 3u;
+        if (pa.kind == listfetch::BYTES || pb.kind == listfetch::BYTES)
+            slow |= 1u << k;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint4 a = and4(funnel_shift(ra[k], sa[k]), fa[k]);
+        const uint4 b = and4(funnel_shift(rb[k], sb[k]), fb[k]);
+        const M128 m = range_mask(0, n0[k]);
+        v[k] = make_uint4(bfi((uint32_t)m.lo, a.x, b.x), bfi((uint32_t)(m.lo >> 32), a.y, b.y), bfi((uint32_t)m.hi, a.z, b.z),
+            bfi((uint32_t)(m.hi >> 32), a.w, b.w));
+    }
+    return slow;
+}
+
+// The windows of `slow` (next to the image's two ends only), byte by byte into the tile buffer at
+// dst: the byte loop of gather_blocks_kernel.  Rolled loops: a rare path that must cost the common
+// one no registers.  (img, img_bytes): the image, for the PPFS_ECC_DEBUG bounds checks.
+__device__ __forceinline__ void list_fetch_slow(uint8_t* dst, const uint8_t* img, uint64_t image_blocks, const uint32_t* slot,
+    uint32_t tid, uint32_t slow)
+{
+    const uint64_t base = (uint64_t)(uintptr_t)img;
+    [[maybe_unused]] const uint64_t img_bytes = image_blocks * listfetch::ROW;
+#pragma unroll 1
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t w = tid + 256u * k;
+        if (!((slow >> k) & 1u) || w >= listfetch::TILE_WINDOWS)
+            continue;
+        const listfetch::Window x = listfetch::window_of(w);
+#pragma unroll 1
+        for (int h = 0; h < 2; ++h) {
+            if (h == 1 && x.n0 == 16u)
+                break;
+            const listfetch::Part p = h == 0 ? listfetch::part_a(base, image_blocks, x, slot[x.row])
+                                             : listfetch::part_b(base, image_blocks, x, slot[x.row + 1u]);
+            const uint8_t* s = img + (p.p0 - base);
+#pragma unroll 1
+            for (uint32_t j = p.lo; j < p.hi; ++j) {
+                uint8_t b = 0;
+                if (p.kind != listfetch::SKIP && PPFS_DBG_OK(s + j, 1, img, img_bytes))
+                    b = s[j];
+                dst[16u * w + j] = b;
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ void list_store_tile(uint8_t* dst, const uint4 (&v)[4], uint32_t tid, uint32_t slow)
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t w = tid + 256u * k;
+        if ((k < 3 || w < listfetch::TILE_WINDOWS) && !((slow >> k) & 1u))
+            *(uint4*)(dst + 16u * w) = v[k];
+    }
+}
+
+// entry i of the list; past its end: no block
+__device__ __forceinline__ uint32_t list_entry(const uint32_t* __restrict__ index, uint64_t i, uint64_t nblocks)
+{
+    return i < nblocks && PPFS_DBG_OK(index + i, 4, index, nblocks * 4u) ? index[i] : 0xFFFFFFFFu;
+}
+
+template <int T2, int WPC = 3, int NTST = 1>
+__global__ __launch_bounds__(256, WPC) void rs_wg_decode_list_kernel(uint8_t* image, uint64_t image_blocks,
+    const uint32_t* __restrict__ index, uint8_t* __restrict__ data, uint8_t* __restrict__ status, uint64_t nblocks,
+    const uint8_t* __restrict__ tables, int write_back)
+{
+    using L = RsWgLayout<T2>;
+    using D = Lds<T2, true, 2>;
+    constexpr int OFF_IDX = D::BYTES; // the next tile's 64 entries
+    constexpr int LDS_ALLOC = lds_alloc<D::BYTES + 256, WPC>();
+    static_assert(WPC * LDS_ALLOC <= 163840, "LDS for WPC workgroups per CU");
+    static_assert(OFF_IDX % 16 == 0, "aligned index slot");
+    constexpr int K = L::K;
+    constexpr int OUT_PIECES = TB * K / 16;
+    __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_ALLOC];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = wave_id();
+    const uint32_t row = lane_row(lane);
+    const bool wb = write_back != 0, want = data != nullptr;
+    const uint64_t img_bytes = image_blocks * 255u;
+    uint32_t* const slot = (uint32_t*)(lds + OFF_IDX);
+    for (uint32_t p = tid; p < (uint32_t)D::TBL / 16; p += NTHR)
+        *(uint4*)(lds + 16 * p) = *(const uint4*)(tables + 16 * p);
+    if (tid < 128)
+        *(uint64_t*)(lds + D::OFF_PAR + 8 * tid) = 0;
+    const uint64_t nfull = nblocks / TB, ntiles = (nblocks + TB - 1) / TB;
+    const uint64_t G = gridDim.x;
+    // One loop for every tile of this workgroup, the partial last tile of the list included: an
+    // iteration fetches tile f into registers and runs the phases on tile t = f - G, fetched by the
+    // iteration before (the first iteration only fetches; the last only computes).
+    uint64_t t = 0, f = blockIdx.x;
+    if (f >= ntiles)
+        return;
+    bool first = true;
+    uint32_t cur = 1, pc = 0;
+    uint32_t my_idx = 0xFFFFFFFFu; // wave 0: the entry of this lane's row of tile t
+    if (wave == 1)
+        slot[lane] = list_entry(index, f * TB + lane, nblocks);
+    for (;;) {
+        barrier_lds(); // A: tile t in LDS, the slot holds tile f's entries, last tile's emission reads done
+        const uint32_t buf = D::OFF_BUF + cur * BUF, par = D::OFF_PAR + pc * 512u;
+        const bool have = f < ntiles, far = f + G < ntiles;
+        uint4 v[4];
+        uint32_t next_idx = 0xFFFFFFFFu, far_idx = 0xFFFFFFFFu, slow = 0;
+        uint8_t* const nbuf = lds + D::OFF_BUF + (cur ^ 1u) * BUF + PAD; // held tile t - G: free since barrier A
+        if (have) {
+            // the windows' row / column / mask arithmetic is redone every tile (a few ALU operations):
+            // hoisted out of the loop it would hold some 30 registers through the correction phase
+            uint32_t ftid = tid;
+            asm volatile("" : "+v"(ftid));
+            slow = list_fetch_tile(v, image, image_blocks, slot, ftid, tables);
+            if (slow)
+                list_fetch_slow(nbuf, image, image_blocks, slot, ftid, slow);
+            if (wave == 0)
+                next_idx = slot[row];
+        }
+        if (wave == 1 && far)
+            far_idx = list_entry(index, (f + G) * TB + lane, nblocks);
+        if (!first) {
+            if (wave == 0)
+                *(uint64_t*)(lds + D::OFF_PAR + (pc ^ 1u) * 512u + 8u * lane) = 0;
+            phase_remainder<T2, 255>(lds, buf, par, wave, row);
+        }
+        barrier_lds(); // B: remainders complete; every read of the slot done
+        if (wave == 1 && far)
+            slot[lane] = far_idx;
+        // entries of tile t: 64, or the list's last nblocks % 64 (their rows past the list's end are
+        // zeros, entries that name no block)
+        const uint32_t nb = t < nfull ? (uint32_t)TB : (uint32_t)(nblocks - t * TB);
+        if (!first && wave == 0) {
+            const bool listed = row < nb, valid = listed && my_idx < image_blocks;
+            const uint32_t st = phase_correct<T2>(lds, buf, par, row, valid, image, my_idx, wb, img_bytes);
+            if (status && listed && PPFS_DBG_OK(status + t * TB + row, 1, status, nblocks))
+                status[t * TB + row] = valid ? (uint8_t)st : (uint8_t)9;
+        }
+        barrier_lds(); // C: corrections patched into the LDS rows
+        if (!first && want) {
+            uint8_t* dst = data + t * (TB * K);
+            if (nb == (uint32_t)TB) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const uint32_t p = tid + 256u * k;
+                    const uint4 o = dec_piece<T2>(lds, buf, p);
+                    if ((k < 3 || p < (uint32_t)OUT_PIECES) && PPFS_DBG_OK(dst + 16u * p, 16, data, nblocks * K))
+                        st_nt<NTST>(dst + 16u * p, o);
+                }
+            } else {
+                const uint32_t nout = nb * (uint32_t)K;
+                for (uint32_t p = tid; 16u * p < nout; p += NTHR) {
+                    const uint4 o = dec_piece<T2>(lds, buf, p);
+                    if (!PPFS_DBG_OK(dst + 16u * p, min(16u, nout - 16u * p), data, nblocks * K))
+                        continue;
+                    if (16u * p + 16u <= nout)
+                        *(uint4*)(dst + 16u * p) = o;
+                    else
+                        st_bytes(dst + 16u * p, o, nout - 16u * p);
+                }
+            }
+        }
+        if (!have)
+            break;
+        list_store_tile(nbuf, v, tid, slow);
+        my_idx = next_idx;
+        t = f;
+        f += G;
+        cur ^= 1u;
+        pc ^= 1u;
+        first = false;
+    }
+}
+
+} // namespace wg
+} // namespace ppfs

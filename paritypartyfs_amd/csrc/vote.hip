@@ -10,6 +10,7 @@
 
 #include "../../include/ppfs_ecc.h" // ppfs_ecc_extent
 #include "dbg.hpp"
+#include "funnel.hpp"
 #include <stdint.h>
 
 namespace ppfs {
@@ -271,19 +272,7 @@ extern "C" hipError_t ppfs_gather_rows_launch(const uint8_t* src, uint64_t src_r
 // or tail fall back to bytes.  Positions are 32-bit: the launchers refuse nb * raw >= 2^32.
 namespace ppfs {
 
-// the 16 bytes at p (any alignment) from aligned dword loads; the caller guarantees that the
-// aligned dwords covering [p, p + 16) may be read
-__device__ inline uint4 load16_funnel(const uint8_t* p)
-{
-    const uint32_t sh = (uint32_t)((uintptr_t)p & 3u);
-    const uint32_t* a = (const uint32_t*)((uintptr_t)p & ~(uintptr_t)3);
-    const uint32_t w0 = a[0], w1 = a[1], w2 = a[2], w3 = a[3];
-    if (sh == 0)
-        return make_uint4(w0, w1, w2, w3);
-    const uint32_t w4 = a[4];
-    return make_uint4(__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh),
-        __builtin_amdgcn_alignbyte(w3, w2, sh), __builtin_amdgcn_alignbyte(w4, w3, sh));
-}
+// load16_funnel: funnel.hpp
 
 // stage row i = image row index[i] for i < nb; an entry with index[i] >= image_blocks is never
 // dereferenced and its row becomes zeros.  One lane per 16-byte window of the staging copy

@@ -192,6 +192,11 @@ class EccEngine:
             raise ValueError("data: required")
         _need("data", data, n * self.data_size, kind)
 
+    def list_kernel_name(self) -> str:
+        """How decode_list runs (ppfs_ecc_list_kernel_name): "rs255-wg-list-lds", one kernel that fetches
+        the listed rows itself (RS bs >= 255, t <= 4), or "gather-stage-scatter", the staged pipeline."""
+        return lib().ppfs_ecc_list_kernel_name(self._h).decode()
+
     def decode_list(self, image, index, data=None, status=None, write_back: bool = True, spill=None, stream=None) -> None:
         n, blocks = self._list_check("device", image, index, data, status, spill)
         check(lib().ppfs_ecc_decode_list_device(self._h, _ptr(image), blocks, self._index_ptr(index), n, _ptr(data),
