@@ -23,6 +23,11 @@
 //   - Phase 3, emission: every thread assembles 16-byte pieces of the OUTPUT tile straight from
 //     the LDS input rows (funnel shifts; parity bytes inserted at block starts) and stores them
 //     with 16-byte non-temporal stores.  No output staging in LDS.
+//
+// Where things live: the phases above are written once, in the "Tile phases" section (after
+// phase_correct); the kernels here, in rs_wg_tk.hpp and in rs_wg_list.hpp are a walk, a loader and
+// calls of them.  Two blocks stay written out in the static-walk kernels (see there): their ring
+// walk, and the decode's full-tile emission.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -505,6 +510,155 @@ __device__ __forceinline__ uint32_t phase_correct(uint8_t* lds, uint32_t buf, ui
 }
 
 // ------------------------------------------------------------------------------------
+// Tile phases.  Every kernel of the family (the static walks and the server below, the ticket
+// kernels of rs_wg_tk.hpp, the list decode of rs_wg_list.hpp, the ablation variants) is a walk that
+// picks the next tile, a loader that brings its rows into an LDS tile buffer, and calls of these: a
+// new walk or loader calls the phases, it does not copy them.  NT = the caller's thread stride.
+// (gbase, extent): the global buffer a pointer lies in (PPFS_ECC_DEBUG bounds checks, dbg.hpp).
+// ------------------------------------------------------------------------------------
+// Prologue by plain loads: the first TBL bytes of the table blob to LDS byte 0 (any destination and
+// source for a table that sits elsewhere), and with OFF_PAR >= 0 both parity-slot sets zeroed
+template <int TBL, int OFF_PAR = -1, int NT = NTHR>
+__device__ __forceinline__ void tables_to_lds(uint8_t* lds, const uint8_t* tables, uint32_t tid)
+{
+    for (uint32_t p = tid; p < (uint32_t)TBL / 16; p += NT)
+        *(uint4*)(lds + 16 * p) = *(const uint4*)(tables + 16 * p);
+    if constexpr (OFF_PAR >= 0) {
+        if (tid < 128)
+            *(uint64_t*)(lds + OFF_PAR + 8 * tid) = 0;
+    }
+}
+
+// One assembled piece of a partial tile's nout output bytes: whole, or its bytes below nout
+__device__ __forceinline__ void st_piece_partial(uint8_t* dst, uint4 v, uint32_t p, uint32_t nout,
+    [[maybe_unused]] const uint8_t* gbase, [[maybe_unused]] uint64_t extent)
+{
+    if (!PPFS_DBG_OK(dst + 16u * p, min(16u, nout - 16u * p), gbase, extent))
+        return;
+    if (16u * p + 16u <= nout)
+        *(uint4*)(dst + 16u * p) = v;
+    else
+        st_bytes(dst + 16u * p, v, nout - 16u * p);
+}
+
+// Partial-tile emission: the first nout bytes of the codeword (payload) tile to dst
+template <int T2, int NT = NTHR>
+__device__ __forceinline__ void enc_emit_partial(const uint8_t* lds, uint32_t buf, uint32_t par, uint8_t* dst, uint32_t nout,
+    uint32_t tid, const uint8_t* gbase, uint64_t extent)
+{
+    for (uint32_t p = tid; 16u * p < nout; p += NT)
+        st_piece_partial(dst, enc_piece<T2>(lds, buf, par, p), p, nout, gbase, extent);
+}
+template <int T2, int NT = NTHR>
+__device__ __forceinline__ void dec_emit_partial(const uint8_t* lds, uint32_t buf, uint8_t* dst, uint32_t nout, uint32_t tid,
+    const uint8_t* gbase, uint64_t extent)
+{
+    for (uint32_t p = tid; 16u * p < nout; p += NT)
+        st_piece_partial(dst, dec_piece<T2>(lds, buf, p), p, nout, gbase, extent);
+}
+
+// The one partial tile t (nblocks % 64 blocks) from its first barrier on: rows staged by plain
+// loads, remainder, (decode) correction and status, emission.  Caller: s_waitcnt vmcnt(0) first.
+template <int T2, int NMAP = 3, int XOFF = 0, bool T5 = false>
+__device__ __forceinline__ void enc_partial_tile(uint8_t* lds, uint32_t buf, uint32_t par, const uint8_t* data,
+    uint8_t* raw, uint64_t nblocks, uint64_t t, uint32_t tid, uint32_t wave, uint32_t row)
+{
+    constexpr int K = 255 - T2;
+    barrier_lds();
+    const uint32_t nb = (uint32_t)(nblocks - t * TB);
+    if (PPFS_DBG_OK(data + t * (TB * K), nb * K, data, nblocks * K))
+        stage_bytes(lds + buf + PAD, data + t * (TB * K), nb * K, tid);
+    barrier_lds();
+    phase_remainder<T2, K, NMAP, XOFF, T5>(lds, buf, par, wave, row);
+    barrier_lds();
+    enc_emit_partial<T2>(lds, buf, par, raw + t * (TB * 255), nb * 255u, tid, raw, nblocks * 255u);
+}
+// wbp, wb: the write-back target (the codewords in place, or the caller's image) and its flag;
+// data == nullptr: no payloads wanted
+template <int T2, int NMAP = 3, int XOFF = 0>
+__device__ __forceinline__ void dec_partial_tile(uint8_t* lds, uint32_t buf, uint32_t par, const uint8_t* raw,
+    uint8_t* data, uint8_t* status, uint64_t nblocks, uint64_t t, uint8_t* wbp, bool wb,
+    uint32_t tid, uint32_t wave, uint32_t row)
+{
+    constexpr int K = 255 - T2;
+    barrier_lds();
+    const uint32_t nb = (uint32_t)(nblocks - t * TB);
+    if (PPFS_DBG_OK(raw + t * (TB * 255), nb * 255u, raw, nblocks * 255u))
+        stage_bytes(lds + buf + PAD, raw + t * (TB * 255), nb * 255u, tid);
+    barrier_lds();
+    phase_remainder<T2, 255, NMAP, XOFF>(lds, buf, par, wave, row);
+    barrier_lds();
+    if (wave == 0) {
+        const bool valid = row < nb;
+        const uint32_t st = phase_correct<T2>(lds, buf, par, row, valid, wbp, t * TB + row, wb, nblocks * 255u);
+        if (status && valid && PPFS_DBG_OK(status + t * TB + row, 1, status, nblocks))
+            status[t * TB + row] = (uint8_t)st;
+    }
+    barrier_lds();
+    if (data)
+        dec_emit_partial<T2>(lds, buf, data + t * (TB * K), nb * (uint32_t)K, tid, data, nblocks * K);
+}
+
+// Full-tile emission: this thread's 4 pieces (tid + 256 k) of the output tile, each assembled and
+// stored at once.  The encode's general form keeps the pieces in o[k]: with HOLD nothing is stored
+// and the caller stores them later with store_tile (the single-buffer walk, after the barrier that
+// frees the buffer); ONE_LIVE (the full-grid walk): a piece's index maths starts after the last
+// piece's store, so one piece is live at a time; PIECE = false (ablation builds): a plain 16-byte
+// copy out of the LDS tile, the same bytes moved.
+template <int NPIECE, int NTST>
+__device__ __forceinline__ void store_tile(uint8_t* dst, const uint4 (&o)[4], uint32_t tid, [[maybe_unused]] const uint8_t* gbase,
+    [[maybe_unused]] uint64_t extent)
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t p = tid + 256u * k;
+        if ((k < 3 || p < (uint32_t)NPIECE) && PPFS_DBG_OK(dst + 16u * p, 16, gbase, extent))
+            st_nt<NTST>(dst + 16u * p, o[k]);
+    }
+}
+template <int T2, int NTST, bool HOLD = false, bool ONE_LIVE = false, bool PIECE = true>
+__device__ __forceinline__ void enc_emit_tile(uint4 (&o)[4], const uint8_t* lds, uint32_t buf, uint32_t par, uint8_t* dst,
+    uint32_t tid, [[maybe_unused]] const uint8_t* gbase, [[maybe_unused]] uint64_t extent)
+{
+    constexpr int OUT_PIECES = TB * 255 / 16;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        uint32_t p = tid + 256u * k;
+        if constexpr (ONE_LIVE)
+            asm volatile("" : "+v"(p));
+        if constexpr (PIECE)
+            o[k] = enc_piece<T2>(lds, buf, par, p);
+        else
+            o[k] = *(const uint4*)(lds + buf + PAD + 16u * (p < 996u ? p : p - 64u));
+        if (!HOLD && (k < 3 || p < (uint32_t)OUT_PIECES) && PPFS_DBG_OK(dst + 16u * p, 16, gbase, extent))
+            st_nt<NTST>(dst + 16u * p, o[k]); // store as soon as the piece is assembled
+        if constexpr (ONE_LIVE)
+            asm volatile("" ::: "memory");
+    }
+}
+// the common form: every piece stored at once, none kept
+template <int T2, int NTST>
+__device__ __forceinline__ void enc_emit_tile(const uint8_t* lds, uint32_t buf, uint32_t par, uint8_t* dst, uint32_t tid,
+    const uint8_t* gbase, uint64_t extent)
+{
+    uint4 o[4];
+    enc_emit_tile<T2, NTST>(o, lds, buf, par, dst, tid, gbase, extent);
+}
+template <int T2, int NTST>
+__device__ __forceinline__ void dec_emit_tile(const uint8_t* lds, uint32_t buf, uint8_t* dst, uint32_t tid,
+    [[maybe_unused]] const uint8_t* gbase, [[maybe_unused]] uint64_t extent)
+{
+    constexpr int OUT_PIECES = TB * (255 - T2) / 16;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t p = tid + 256u * k;
+        const uint4 o = dec_piece<T2>(lds, buf, p);
+        if ((k < 3 || p < (uint32_t)OUT_PIECES) && PPFS_DBG_OK(dst + 16u * p, 16, gbase, extent))
+            st_nt<NTST>(dst + 16u * p, o);
+    }
+}
+
+// ------------------------------------------------------------------------------------
 // Kernels: persistent workgroups walk 64-block tiles t = blockIdx.x, += gridDim.x.
 // NBUF = LDS tile buffers: 2 = the next tile's DMA is issued at the top of an iteration (a whole
 // tile of compute ahead); 3, 4 = a ring, the DMA NBUF - 1 tiles ahead (fewer workgroups per CU fit); 1 = it is issued after this tile's emission reads (cross-workgroup
@@ -588,10 +742,7 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_encode_kernel(const uint8_t* _
     __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_ALLOC];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = wave_id();
     const uint32_t row = lane_row(lane);
-    for (uint32_t p = tid; p < (uint32_t)D::TBL / 16; p += NTHR)
-        *(uint4*)(lds + 16 * p) = *(const uint4*)(tables + 16 * p);
-    if (tid < 128)
-        *(uint64_t*)(lds + D::OFF_PAR + 8 * tid) = 0;
+    tables_to_lds<D::TBL, D::OFF_PAR>(lds, tables, tid);
     const uint64_t nfull = nblocks / TB, ntiles = (nblocks + TB - 1) / TB;
     uint64_t t = blockIdx.x;
     uint32_t cur = 0, pc = 0; // tile buffer, parity-slot set
@@ -630,30 +781,12 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_encode_kernel(const uint8_t* _
         barrier_lds(); // B: parity slots complete
         uint8_t* dst = raw + t * (TB * 255);
         uint4 o[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            uint32_t p = tid + 256u * k;
-            if constexpr (NBUF == 0)
-                asm volatile("" : "+v"(p)); // this piece's index maths starts after the last store
-            if constexpr (MODE & 2)
-                o[k] = enc_piece<T2>(lds, buf, par, p);
-            else
-                o[k] = *(const uint4*)(lds + buf + PAD + 16u * (p < 996u ? p : p - 64u));
-            if (NBUF != 1 && (k < 3 || p < (uint32_t)OUT_PIECES) && PPFS_DBG_OK(dst + 16u * p, 16, raw, nblocks * 255u))
-                st_nt<NTST>(dst + 16u * p, o[k]); // store as soon as the piece is assembled
-            if constexpr (NBUF == 0)
-                asm volatile("" ::: "memory"); // one piece live at a time
-        }
+        enc_emit_tile<T2, NTST, NBUF == 1, NBUF == 0, (MODE & 2) != 0>(o, lds, buf, par, dst, tid, raw, nblocks * 255u);
         if (NBUF == 1) {
             barrier_lds(); // every wave's emission reads done: the buffer is free
             if (nx < nfull)
                 dma_tile<IN_PIECES>(lds + D::OFF_BUF + PAD, data + nx * (TB * K), tid, data, nblocks * K);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const uint32_t p = tid + 256u * k;
-                if ((k < 3 || p < (uint32_t)OUT_PIECES) && PPFS_DBG_OK(dst + 16u * p, 16, raw, nblocks * 255u))
-                    st_nt<NTST>(dst + 16u * p, o[k]);
-            }
+            store_tile<OUT_PIECES, NTST>(dst, o, tid, raw, nblocks * 255u);
         }
         // next tile's DMA landed; this tile's stores (NBUF >= 3: and every store and DMA issued
         // after that DMA) may fly
@@ -669,33 +802,18 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_encode_kernel(const uint8_t* _
         pc ^= 1u;
     }
     if (t == nfull && nfull < ntiles) {
-        // the one partial tile (nblocks % 64 blocks)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        barrier_lds();
-        const uint32_t nb = (uint32_t)(nblocks - t * TB);
-        const uint32_t buf = D::OFF_BUF + cur * BUF, par = D::OFF_PAR + pc * 512u;
-        if (PPFS_DBG_OK(data + t * (TB * K), nb * K, data, nblocks * K))
-            stage_bytes(lds + buf + PAD, data + t * (TB * K), nb * K, tid);
-        barrier_lds();
-        phase_remainder<T2, K, D::NMAP>(lds, buf, par, wave, row);
-        barrier_lds();
-        uint8_t* dst = raw + t * (TB * 255);
-        const uint32_t nout = nb * 255u;
-        for (uint32_t p = tid; 16u * p < nout; p += NTHR) {
-            const uint4 v = enc_piece<T2>(lds, buf, par, p);
-            if (!PPFS_DBG_OK(dst + 16u * p, min(16u, nout - 16u * p), raw, nblocks * 255u))
-                continue;
-            if (16u * p + 16u <= nout)
-                *(uint4*)(dst + 16u * p) = v;
-            else
-                st_bytes(dst + 16u * p, v, nout - 16u * p);
-        }
+        enc_partial_tile<T2, D::NMAP>(lds, D::OFF_BUF + cur * BUF, D::OFF_PAR + pc * 512u, data, raw, nblocks, t, tid, wave, row);
     }
 }
 
 
 // MODE (ablation builds only; the engine uses 7): bit 0 = remainder phase, bit 1 = payload
 // emission (else a plain 16-byte copy), bit 2 = correction phase
+// Written out here on purpose: the ring walk (as in the encode above) and the full-tile emission.
+// Through helpers (a ring-walk struct; dec_emit_tile with an output array + store_tile, as the
+// encode has) the shipped instantiations compiled to 2-4 more VGPRs at every 2t, and the list and
+// server kernels, which share this kernel's phase instantiations, moved with them.
 template <int T2, int NBUF = 2, int WPC = 3, int MODE = 7, int NTST = 1>
 __global__ __launch_bounds__(256, WPC) void rs_wg_decode_kernel(uint8_t* __restrict__ raw, uint8_t* __restrict__ data,
     uint8_t* __restrict__ status, uint64_t nblocks, const uint8_t* __restrict__ tables, int write_back,
@@ -713,10 +831,7 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_decode_kernel(uint8_t* __restr
     const uint32_t row = lane_row(lane);
     const bool wb = write_back != 0, want = data != nullptr;
     uint8_t* const wbp = raw_wb ? raw_wb : raw; // write-back target (rs_wg_tk.hpp rs_wg_decode_tk_kernel)
-    for (uint32_t p = tid; p < (uint32_t)D::TBL / 16; p += NTHR)
-        *(uint4*)(lds + 16 * p) = *(const uint4*)(tables + 16 * p);
-    if (tid < 128)
-        *(uint64_t*)(lds + D::OFF_PAR + 8 * tid) = 0;
+    tables_to_lds<D::TBL, D::OFF_PAR>(lds, tables, tid);
     const uint64_t nfull = nblocks / TB, ntiles = (nblocks + TB - 1) / TB;
     uint64_t t = blockIdx.x;
     uint32_t cur = 0, pc = 0;
@@ -808,34 +923,7 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_decode_kernel(uint8_t* __restr
     }
     if (t == nfull && nfull < ntiles) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        barrier_lds();
-        const uint32_t nb = (uint32_t)(nblocks - t * TB);
-        const uint32_t buf = D::OFF_BUF + cur * BUF, par = D::OFF_PAR + pc * 512u;
-        if (PPFS_DBG_OK(raw + t * (TB * 255), nb * 255u, raw, nblocks * 255u))
-            stage_bytes(lds + buf + PAD, raw + t * (TB * 255), nb * 255u, tid);
-        barrier_lds();
-        phase_remainder<T2, 255>(lds, buf, par, wave, row);
-        barrier_lds();
-        if (wave == 0) {
-            const bool valid = row < nb;
-            const uint32_t st = phase_correct<T2>(lds, buf, par, row, valid, wbp, t * TB + row, wb, nblocks * 255u);
-            if (status && valid && PPFS_DBG_OK(status + t * TB + row, 1, status, nblocks))
-                status[t * TB + row] = (uint8_t)st;
-        }
-        barrier_lds();
-        if (want) {
-            uint8_t* dst = data + t * (TB * K);
-            const uint32_t nout = nb * (uint32_t)K;
-            for (uint32_t p = tid; 16u * p < nout; p += NTHR) {
-                const uint4 v = dec_piece<T2>(lds, buf, p);
-                if (!PPFS_DBG_OK(dst + 16u * p, min(16u, nout - 16u * p), data, nblocks * K))
-                    continue;
-                if (16u * p + 16u <= nout)
-                    *(uint4*)(dst + 16u * p) = v;
-                else
-                    st_bytes(dst + 16u * p, v, nout - 16u * p);
-            }
-        }
+        dec_partial_tile<T2>(lds, D::OFF_BUF + cur * BUF, D::OFF_PAR + pc * 512u, raw, data, status, nblocks, t, wbp, wb, tid, wave, row);
     }
 }
 
@@ -858,8 +946,7 @@ __global__ __launch_bounds__(256, 1) void rs_wg_server_kernel(SrvBox* box, uint8
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = wave_id();
     const uint32_t row = lane_row(lane);
     const uint32_t buf = D::OFF_BUF, par = D::OFF_PAR;
-    for (uint32_t p = tid; p < (uint32_t)D::TBL / 16; p += NTHR)
-        *(uint4*)(lds + 16 * p) = *(const uint4*)(tables + 16 * p);
+    tables_to_lds<D::TBL>(lds, tables, tid); // the slots are zeroed per request
     const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
     uint64_t last = t0;
     uint32_t seen = srv::ld_sys(&box->done), served = 0;
@@ -892,16 +979,8 @@ __global__ __launch_bounds__(256, 1) void rs_wg_server_kernel(SrvBox* box, uint8
                     status[row] = (uint8_t)st;
             }
             barrier_lds();
-            if (op == SRV_DECODE && cmd.want_data) {
-                const uint32_t nout = nb * (uint32_t)K;
-                for (uint32_t p = tid; 16u * p < nout; p += NTHR) {
-                    const uint4 v = dec_piece<T2>(lds, buf, p);
-                    if (16u * p + 16u <= nout)
-                        *(uint4*)(data + 16u * p) = v;
-                    else
-                        st_bytes(data + 16u * p, v, nout - 16u * p);
-                }
-            }
+            if (op == SRV_DECODE && cmd.want_data)
+                dec_emit_partial<T2>(lds, buf, data, nb * (uint32_t)K, tid, zc, zc_bytes);
             barrier_lds(); // the buffer and slots are free
         }
         if (ok && (op == SRV_ENCODE || op == SRV_WRITE)) {
@@ -911,14 +990,7 @@ __global__ __launch_bounds__(256, 1) void rs_wg_server_kernel(SrvBox* box, uint8
             barrier_lds();
             phase_remainder<T2, K>(lds, buf, par, wave, row);
             barrier_lds();
-            const uint32_t nout = nb * 255u;
-            for (uint32_t p = tid; 16u * p < nout; p += NTHR) {
-                const uint4 v = enc_piece<T2>(lds, buf, par, p);
-                if (16u * p + 16u <= nout)
-                    *(uint4*)(raw + 16u * p) = v;
-                else
-                    st_bytes(raw + 16u * p, v, nout - 16u * p);
-            }
+            enc_emit_partial<T2>(lds, buf, par, raw, nb * 255u, tid, zc, zc_bytes);
             barrier_lds();
         }
         seen = r;

@@ -5,7 +5,8 @@
 //
 // The static-walk decode of rs_wg.hpp with another loader: the LDS tile has the contiguous kernel's
 // layout (64 rows packed at 255 B behind PAD), so the remainder, correction and emission phases
-// are that kernel's, unchanged; the correction takes the image as its write-back target and
+// are that kernel's, unchanged (rs_wg.hpp's tile phases; this file holds the loader and the walk);
+// the correction takes the image as its write-back target and
 // index[i] as its block, so corrected bytes go in place at image + index[i] * 255 + pos, and
 // payloads and statuses come out in list order.
 //
@@ -147,17 +148,13 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_decode_list_kernel(uint8_t* im
     static_assert(WPC * LDS_ALLOC <= 163840, "LDS for WPC workgroups per CU");
     static_assert(OFF_IDX % 16 == 0, "aligned index slot");
     constexpr int K = L::K;
-    constexpr int OUT_PIECES = TB * K / 16;
     __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_ALLOC];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = wave_id();
     const uint32_t row = lane_row(lane);
     const bool wb = write_back != 0, want = data != nullptr;
     const uint64_t img_bytes = image_blocks * 255u;
     uint32_t* const slot = (uint32_t*)(lds + OFF_IDX);
-    for (uint32_t p = tid; p < (uint32_t)D::TBL / 16; p += NTHR)
-        *(uint4*)(lds + 16 * p) = *(const uint4*)(tables + 16 * p);
-    if (tid < 128)
-        *(uint64_t*)(lds + D::OFF_PAR + 8 * tid) = 0;
+    tables_to_lds<D::TBL, D::OFF_PAR>(lds, tables, tid);
     const uint64_t nfull = nblocks / TB, ntiles = (nblocks + TB - 1) / TB;
     const uint64_t G = gridDim.x;
     // One loop for every tile of this workgroup, the partial last tile of the list included: an
@@ -211,26 +208,10 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_decode_list_kernel(uint8_t* im
         barrier_lds(); // C: corrections patched into the LDS rows
         if (!first && want) {
             uint8_t* dst = data + t * (TB * K);
-            if (nb == (uint32_t)TB) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const uint32_t p = tid + 256u * k;
-                    const uint4 o = dec_piece<T2>(lds, buf, p);
-                    if ((k < 3 || p < (uint32_t)OUT_PIECES) && PPFS_DBG_OK(dst + 16u * p, 16, data, nblocks * K))
-                        st_nt<NTST>(dst + 16u * p, o);
-                }
-            } else {
-                const uint32_t nout = nb * (uint32_t)K;
-                for (uint32_t p = tid; 16u * p < nout; p += NTHR) {
-                    const uint4 o = dec_piece<T2>(lds, buf, p);
-                    if (!PPFS_DBG_OK(dst + 16u * p, min(16u, nout - 16u * p), data, nblocks * K))
-                        continue;
-                    if (16u * p + 16u <= nout)
-                        *(uint4*)(dst + 16u * p) = o;
-                    else
-                        st_bytes(dst + 16u * p, o, nout - 16u * p);
-                }
-            }
+            if (nb == (uint32_t)TB)
+                dec_emit_tile<T2, NTST>(lds, buf, dst, tid, data, nblocks * K);
+            else
+                dec_emit_partial<T2>(lds, buf, dst, nb * (uint32_t)K, tid, data, nblocks * K);
         }
         if (!have)
             break;

@@ -16,6 +16,9 @@
 // right away, before any table byte or ticket arrives; wave 0 brings the tables into LDS by LDS-DMA
 // meanwhile and takes the first dynamic ticket.  Tickets continue after the static tiles of the XCD.
 // A workgroup's tiles increase, so it stops at its first tile past the batch without skipping one.
+//
+// This file holds the ticket walk, its loader (dma_tile192, dma_tables_w0) and the encode's scheduled
+// emission; the partial tile and the decode's emission are rs_wg.hpp's tile phases.
 #include "rs_wg.hpp"
 
 namespace ppfs {
@@ -357,26 +360,8 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_encode_tk_kernel(const uint8_t
     }
     if (q0 == nfull && nfull < ntiles) { // the partial tile
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        barrier_lds();
-        const uint64_t t = nfull;
-        const uint32_t nb = (uint32_t)(nblocks - t * TB);
-        const uint32_t buf = D::OFF_BUF + cur * BUF, par = D::OFF_PAR + pc * 512u;
-        if (PPFS_DBG_OK(data + t * (TB * K), nb * K, data, nblocks * K))
-            stage_bytes(lds + buf + PAD, data + t * (TB * K), nb * K, tid);
-        barrier_lds();
-        phase_remainder<T2, K, D::NMAP, D::OFF_SLX, T5>(lds, buf, par, wave, row);
-        barrier_lds();
-        uint8_t* dst = raw + t * (TB * 255);
-        const uint32_t nout = nb * 255u;
-        for (uint32_t p = tid; 16u * p < nout; p += NTHR) {
-            const uint4 v = enc_piece<T2>(lds, buf, par, p);
-            if (!PPFS_DBG_OK(dst + 16u * p, min(16u, nout - 16u * p), raw, nblocks * 255u))
-                continue;
-            if (16u * p + 16u <= nout)
-                *(uint4*)(dst + 16u * p) = v;
-            else
-                st_bytes(dst + 16u * p, v, nout - 16u * p);
-        }
+        enc_partial_tile<T2, D::NMAP, D::OFF_SLX, T5>(lds, D::OFF_BUF + cur * BUF, D::OFF_PAR + pc * 512u, data, raw, nblocks, nfull,
+            tid, wave, row);
     }
 #ifdef PPFS_TK_TRACE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -411,7 +396,6 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_decode_tk_kernel(uint8_t* __re
     static_assert(WPC * LDS_ALLOC <= 163840, "LDS for WPC workgroups per CU");
     constexpr int K = L::K;
     constexpr int IN_PIECES = TB * 255 / 16;
-    constexpr int OUT_PIECES = TB * K / 16;
     __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_ALLOC];
     uint32_t* const s_tk = (uint32_t*)(lds + OFF_TK);
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = wave_id();
@@ -481,16 +465,8 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_decode_tk_kernel(uint8_t* __re
         }
         barrier_lds(); // C: corrections patched into the LDS rows
         PPFS_TK_MARK(4);
-        if (want) {
-            uint8_t* dst = data + q0 * (TB * K);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const uint32_t p = tid + 256u * k;
-                const uint4 o = dec_piece<T2>(lds, buf, p);
-                if ((k < 3 || p < (uint32_t)OUT_PIECES) && PPFS_DBG_OK(dst + 16u * p, 16, data, nblocks * K))
-                    st_nt<NTST>(dst + 16u * p, o);
-            }
-        }
+        if (want)
+            dec_emit_tile<T2, NTST>(lds, buf, data + q0 * (TB * K), tid, data, nblocks * K);
         ++iter;
         PPFS_TK_MARK(5);
         if (dmaw) { // the next tile's DMA landed; this tile's stores may fly
@@ -508,35 +484,8 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_decode_tk_kernel(uint8_t* __re
     }
     if (q0 == nfull && nfull < ntiles) { // the partial tile
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        barrier_lds();
-        const uint64_t t = nfull;
-        const uint32_t nb = (uint32_t)(nblocks - t * TB);
-        const uint32_t buf = D::OFF_BUF + cur * BUF, par = D::OFF_PAR + pc * 512u;
-        if (PPFS_DBG_OK(raw + t * (TB * 255), nb * 255u, raw, nblocks * 255u))
-            stage_bytes(lds + buf + PAD, raw + t * (TB * 255), nb * 255u, tid);
-        barrier_lds();
-        phase_remainder<T2, 255, D::NMAP, D::OFF_SLX>(lds, buf, par, wave, row);
-        barrier_lds();
-        if (wave == 0) {
-            const bool valid = row < nb;
-            const uint32_t st = phase_correct<T2>(lds, buf, par, row, valid, wbp, t * TB + row, wb, nblocks * 255u);
-            if (status && valid && PPFS_DBG_OK(status + t * TB + row, 1, status, nblocks))
-                status[t * TB + row] = (uint8_t)st;
-        }
-        barrier_lds();
-        if (want) {
-            uint8_t* dst = data + t * (TB * K);
-            const uint32_t nout = nb * (uint32_t)K;
-            for (uint32_t p = tid; 16u * p < nout; p += NTHR) {
-                const uint4 v = dec_piece<T2>(lds, buf, p);
-                if (!PPFS_DBG_OK(dst + 16u * p, min(16u, nout - 16u * p), data, nblocks * K))
-                    continue;
-                if (16u * p + 16u <= nout)
-                    *(uint4*)(dst + 16u * p) = v;
-                else
-                    st_bytes(dst + 16u * p, v, nout - 16u * p);
-            }
-        }
+        dec_partial_tile<T2, D::NMAP, D::OFF_SLX>(lds, D::OFF_BUF + cur * BUF, D::OFF_PAR + pc * 512u, raw, data, status, nblocks,
+            nfull, wbp, wb, tid, wave, row);
     }
 #ifdef PPFS_TK_TRACE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -178,6 +178,42 @@ def test_graph_replays_on_two_streams_at_once(oracle, bs, t, kname, static):
     eng.close()
 
 
+@pytest.mark.parametrize("t", [1, 3, 4])
+@pytest.mark.parametrize("shape", ["101", "3cu+1"])
+def test_static_walk_decode_corrects_its_partial_tile(oracle, t, shape):
+    """The static-walk decode (what a capture launches) on a batch whose partial last tile holds clean,
+    corrected and uncorrectable codewords, with write-back: status, payloads and the written-back
+    image vs the oracle.  101 blocks: one full and one partial tile in different workgroups;
+    (3 CUs + 1) 64 + 37: workgroup 1 reaches the partial tile after a full one, tile buffers and
+    parity-slot set toggled.  One replay: the write-back changes the codewords."""
+    from tests.test_gpu_parity import inject_rs_fast
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    nb = 101 if shape == "101" else (3 * cus + 1) * 64 + 37
+    n, k, _, cw = _rs_batch(oracle, nb, 35 + t, 512, t)
+    bad = inject_rs_fast(np.random.default_rng(135 + t), cw, n, t, nb)
+    o_data, o_st, o_fixed, _, _ = oracle.rs_decode(512, t, bad)
+    assert {0, 1} <= set(o_st[-37:].tolist())  # the partial tile holds clean and erroneous codewords
+    eng = EccEngine(ECC_REED_SOLOMON, 512, t)
+    raw = torch.from_numpy(bad).cuda()
+    data = torch.zeros(nb * k, dtype=torch.uint8, device="cuda")
+    status = torch.full((nb,), 77, dtype=torch.uint8, device="cuda")
+    warm = raw.clone()
+    eng.decode(warm, data, status, write_back=True, nblocks=nb)  # eager first: loads the kernels
+    data.zero_(), status.fill_(77)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        assert eng.stream_kernel_name() == STATIC
+        eng.decode(raw, data, status, write_back=True)
+    g.replay()
+    torch.cuda.synchronize()
+    assert np.array_equal(status.cpu().numpy(), o_st)
+    assert np.array_equal(data.cpu().numpy(), o_data)
+    assert np.array_equal(raw.cpu().numpy(), o_fixed)
+    del g
+    eng.close()
+
+
 def test_stream_slots_are_recycled_past_16_streams(oracle):
     """16 ticket-counter slots: a 17th..20th stream takes a slot whose last user's work has completed
     (round 4; it used to fall back to the static walk for good), and every stream's codewords stay

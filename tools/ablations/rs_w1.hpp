@@ -26,7 +26,6 @@ namespace w1 {
 
 using wg::dma16;
 using wg::lds_addr;
-using wg::st_bytes;
 using wg::st_nt;
 
 constexpr int TB = 64; // blocks per wave tile (lane = block)
@@ -116,8 +115,7 @@ __global__ __launch_bounds__(64 * NW, 1) void rs_w1_encode_kernel(const uint8_t*
     constexpr int KO = (OUT_PIECES + 63) / 64;
     __shared__ __attribute__((aligned(16))) uint8_t lds[D::BYTES];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = wave_id();
-    for (uint32_t p = tid; p < (uint32_t)D::TBL / 16; p += 64u * NW)
-        *(uint4*)(lds + 16 * p) = *(const uint4*)(tables + 16 * p);
+    wg::tables_to_lds<D::TBL, -1, 64 * NW>(lds, tables, tid);
     __syncthreads();
     const uint32_t r = wg::lane_row(lane);
     const uint32_t buf = D::OFF_W + wave * (uint32_t)W::BYTES, par = buf + W::OFF_PAR;
@@ -184,17 +182,7 @@ __global__ __launch_bounds__(64 * NW, 1) void rs_w1_encode_kernel(const uint8_t*
         row_remainder<T2, K>(s, lds, buf + wg::PAD + (uint32_t)K * r);
         *(uint2*)(lds + par + 8u * r) = make_uint2(s[0], s[1]);
         wave_fence();
-        uint8_t* dst = raw + t * (TB * 255);
-        const uint32_t nout = nb * 255u;
-        for (uint32_t p = lane; 16u * p < nout; p += 64u) {
-            const uint4 v = wg::enc_piece<T2>(lds, buf, par, p);
-            if (!PPFS_DBG_OK(dst + 16u * p, min(16u, nout - 16u * p), raw, nblocks * 255u))
-                continue;
-            if (16u * p + 16u <= nout)
-                *(uint4*)(dst + 16u * p) = v;
-            else
-                st_bytes(dst + 16u * p, v, nout - 16u * p);
-        }
+        wg::enc_emit_partial<T2, 64>(lds, buf, par, raw + t * (TB * 255), nb * 255u, lane, raw, nblocks * 255u);
     }
 }
 
@@ -213,8 +201,7 @@ __global__ __launch_bounds__(64 * NW, 1) void rs_w1_decode_kernel(uint8_t* __res
     constexpr int KO = (OUT_PIECES + 63) / 64;
     __shared__ __attribute__((aligned(16))) uint8_t lds[D::BYTES];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = wave_id();
-    for (uint32_t p = tid; p < (uint32_t)D::TBL / 16; p += 64u * NW)
-        *(uint4*)(lds + 16 * p) = *(const uint4*)(tables + 16 * p);
+    wg::tables_to_lds<D::TBL, -1, 64 * NW>(lds, tables, tid);
     __syncthreads();
     const uint32_t r = wg::lane_row(lane);
     const uint32_t buf = D::OFF_W + wave * (uint32_t)W::BYTES, par = buf + W::OFF_PAR;
@@ -285,19 +272,8 @@ __global__ __launch_bounds__(64 * NW, 1) void rs_w1_decode_kernel(uint8_t* __res
         if (status && valid && PPFS_DBG_OK(status + t * TB + r, 1, status, nblocks))
             status[t * TB + r] = (uint8_t)st;
         wave_fence();
-        if (want) {
-            uint8_t* dst = data + t * (TB * K);
-            const uint32_t nout = nb * (uint32_t)K;
-            for (uint32_t p = lane; 16u * p < nout; p += 64u) {
-                const uint4 v = wg::dec_piece<T2>(lds, buf, p);
-                if (!PPFS_DBG_OK(dst + 16u * p, min(16u, nout - 16u * p), data, nblocks * K))
-                    continue;
-                if (16u * p + 16u <= nout)
-                    *(uint4*)(dst + 16u * p) = v;
-                else
-                    st_bytes(dst + 16u * p, v, nout - 16u * p);
-            }
-        }
+        if (want)
+            wg::dec_emit_partial<T2, 64>(lds, buf, data + t * (TB * K), nb * (uint32_t)K, lane, data, nblocks * K);
     }
 }
 

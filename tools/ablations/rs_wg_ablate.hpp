@@ -33,7 +33,6 @@ __global__ __launch_bounds__(320, WPC) void rs_wg_encode_dyn_kernel(const uint8_
     static_assert(WPC * LDS_ALLOC <= 163840, "LDS for WPC workgroups per CU");
     constexpr int K = L::K;
     constexpr int IN_PIECES = TB * K / 16;
-    constexpr int OUT_PIECES = TB * 255 / 16;
     constexpr int NPRO = NBUF + 1; // ring tickets + the DMA tickets of iterations 0 and 1
     constexpr uint32_t OFF_TK = D::BYTES; // NPRO prologue tiles, then 2 per-iteration slots
     __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_ALLOC];
@@ -44,12 +43,8 @@ __global__ __launch_bounds__(320, WPC) void rs_wg_encode_dyn_kernel(const uint8_
     const uint64_t nfull = nblocks / TB, ntiles = (nblocks + TB - 1) / TB;
     const uint32_t nx = gridDim.x < 8u ? gridDim.x : 8u, xc = blockIdx.x % nx;
     uint32_t* const my_ctr = ctr + 32u * xc; // 128-byte lines
-    if (worker) {
-        for (uint32_t p = tid; p < (uint32_t)D::TBL / 16; p += NTHR)
-            *(uint4*)(lds + 16 * p) = *(const uint4*)(tables + 16 * p);
-        if (tid < 128)
-            *(uint64_t*)(lds + D::OFF_PAR + 8 * tid) = 0;
-    }
+    if (worker)
+        tables_to_lds<D::TBL, D::OFF_PAR>(lds, tables, tid);
     const uint32_t gx = gridDim.x / nx;
     uint32_t fk = blockIdx.x / nx;
     if (!worker && lane == 0) {
@@ -114,18 +109,8 @@ __global__ __launch_bounds__(320, WPC) void rs_wg_encode_dyn_kernel(const uint8_
         hist = (hist << 1) | (go ? 1u : 0u);
         barrier_lds(); // B
         if (worker) {
-            uint8_t* dst = raw + t * (TB * 255);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const uint32_t p = tid + 256u * k;
-                uint4 o;
-                if constexpr (MODE & 2)
-                    o = enc_piece<T2>(lds, buf, par, p);
-                else
-                    o = *(const uint4*)(lds + buf + PAD + 16u * (p < 996u ? p : p - 64u));
-                if ((k < 3 || p < (uint32_t)OUT_PIECES) && PPFS_DBG_OK(dst + 16u * p, 16, raw, nblocks * 255u))
-                    st_nt<NTST>(dst + 16u * p, o);
-            }
+            uint4 o[4];
+            enc_emit_tile<T2, NTST, false, false, (MODE & 2) != 0>(o, lds, buf, par, raw + t * (TB * 255), tid, raw, nblocks * 255u);
             ++iter;
             const uint32_t st = 4u * (iter < (uint32_t)(NBUF - 1) ? iter : (uint32_t)(NBUF - 1));
             vm_wait_newer(st + 4u * __builtin_popcount(hist & ((1u << (NBUF - 2)) - 1u)));
@@ -151,19 +136,8 @@ __global__ __launch_bounds__(320, WPC) void rs_wg_encode_dyn_kernel(const uint8_
         if (worker)
             phase_remainder<T2, K, D::NMAP>(lds, buf, par, wave, row);
         barrier_lds();
-        if (worker) {
-            uint8_t* dst = raw + t * (TB * 255);
-            const uint32_t nout = nb * 255u;
-            for (uint32_t p = tid; 16u * p < nout; p += NTHR) {
-                const uint4 v = enc_piece<T2>(lds, buf, par, p);
-                if (!PPFS_DBG_OK(dst + 16u * p, min(16u, nout - 16u * p), raw, nblocks * 255u))
-                    continue;
-                if (16u * p + 16u <= nout)
-                    *(uint4*)(dst + 16u * p) = v;
-                else
-                    st_bytes(dst + 16u * p, v, nout - 16u * p);
-            }
-        }
+        if (worker)
+            enc_emit_partial<T2>(lds, buf, par, raw + t * (TB * 255), nb * 255u, tid, raw, nblocks * 255u);
     }
     if (!worker && lane == 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this workgroup's last ticket has returned
@@ -245,12 +219,8 @@ __global__ __launch_bounds__(512, WPC) void rs_wg_encode8_kernel(const uint8_t* 
     __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_ALLOC];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = wave_id();
     const uint32_t row = lane_row(lane);
-    for (uint32_t p = tid; p < (uint32_t)L::OFF_MAP / 16; p += NT) // SL
-        *(uint4*)(lds + 16 * p) = *(const uint4*)(tables + 16 * p);
-    for (uint32_t p = tid; p < 7u * L::MAP_STRIDE / 16; p += NT) // MAP32
-        *(uint4*)(lds + L::OFF_MAP + 16 * p) = *(const uint4*)(tables + L::OFF_MAP32 + 16 * p);
-    if (tid < 128)
-        *(uint64_t*)(lds + D::OFF_PAR + 8 * tid) = 0;
+    tables_to_lds<L::OFF_MAP, D::OFF_PAR, NT>(lds, tables, tid);                                          // SL, slots
+    tables_to_lds<7 * L::MAP_STRIDE, -1, NT>(lds + L::OFF_MAP, tables + L::OFF_MAP32, tid); // MAP32
     const uint64_t nfull = nblocks / TB, ntiles = (nblocks + TB - 1) / TB;
     uint64_t t = blockIdx.x;
     uint32_t cur = 0, pc = 0;
@@ -308,17 +278,7 @@ __global__ __launch_bounds__(512, WPC) void rs_wg_encode8_kernel(const uint8_t* 
         barrier_lds();
         phase_remainder8<T2, K>(lds, buf, par, wave, row);
         barrier_lds();
-        uint8_t* dst = raw + t * (TB * 255);
-        const uint32_t nout = nb * 255u;
-        for (uint32_t p = tid; 16u * p < nout; p += NT) {
-            const uint4 v = enc_piece<T2>(lds, buf, par, p);
-            if (!PPFS_DBG_OK(dst + 16u * p, min(16u, nout - 16u * p), raw, nblocks * 255u))
-                continue;
-            if (16u * p + 16u <= nout)
-                *(uint4*)(dst + 16u * p) = v;
-            else
-                st_bytes(dst + 16u * p, v, nout - 16u * p);
-        }
+        enc_emit_partial<T2, NT>(lds, buf, par, raw + t * (TB * 255), nb * 255u, tid, raw, nblocks * 255u);
     }
 }
 

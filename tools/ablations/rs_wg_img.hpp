@@ -51,8 +51,7 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_encode_img_kernel(const uint8_
     __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_ALLOC];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = wave_id();
     const uint32_t row = lane_row(lane);
-    for (uint32_t p = tid; p < (uint32_t)TBL / 16; p += NTHR)
-        *(uint4*)(lds + 16 * p) = *(const uint4*)(tables + 16 * p);
+    tables_to_lds<TBL>(lds, tables, tid);
     if (tid < 64)
         *(uint64_t*)(lds + OFF_PAR + 8 * tid) = 0;
     const uint64_t nfull = nblocks / TB, ntiles = (nblocks + TB - 1) / TB;

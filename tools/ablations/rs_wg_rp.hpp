@@ -62,10 +62,7 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_encode_rp_kernel(const uint8_t
     __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_ALLOC];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = wave_id();
     const uint32_t row = lane_row(lane);
-    for (uint32_t p = tid; p < (uint32_t)D::TBL / 16; p += NTHR)
-        *(uint4*)(lds + 16 * p) = *(const uint4*)(tables + 16 * p);
-    if (tid < 128)
-        *(uint64_t*)(lds + D::OFF_PAR + 8 * tid) = 0;
+    tables_to_lds<D::TBL, D::OFF_PAR>(lds, tables, tid);
     const uint64_t nfull = nblocks / TB, ntiles = (nblocks + TB - 1) / TB, G = gridDim.x;
     const uint32_t buf = D::OFF_BUF;
     uint64_t t = blockIdx.x;
@@ -120,15 +117,7 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_encode_rp_kernel(const uint8_t
         barrier_lds();
         phase_remainder<T2, K>(lds, buf, par, wave, row);
         barrier_lds();
-        uint8_t* dst = raw + t * (TB * 255);
-        const uint32_t nout = nb * 255u;
-        for (uint32_t p = tid; 16u * p < nout; p += NTHR) {
-            const uint4 v = enc_piece<T2>(lds, buf, par, p);
-            if (16u * p + 16u <= nout)
-                *(uint4*)(dst + 16u * p) = v;
-            else
-                st_bytes(dst + 16u * p, v, nout - 16u * p);
-        }
+        enc_emit_partial<T2>(lds, buf, par, raw + t * (TB * 255), nb * 255u, tid, raw, nblocks * 255u);
     }
 }
 
@@ -148,10 +137,7 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_decode_rp_kernel(uint8_t* __re
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = wave_id();
     const uint32_t row = lane_row(lane);
     const bool wb = write_back != 0; // WANT == (data != nullptr): decided at launch, so the wait counts see one path
-    for (uint32_t p = tid; p < (uint32_t)D::TBL / 16; p += NTHR)
-        *(uint4*)(lds + 16 * p) = *(const uint4*)(tables + 16 * p);
-    if (tid < 128)
-        *(uint64_t*)(lds + D::OFF_PAR + 8 * tid) = 0;
+    tables_to_lds<D::TBL, D::OFF_PAR>(lds, tables, tid);
     const uint64_t nfull = nblocks / TB, ntiles = (nblocks + TB - 1) / TB, G = gridDim.x;
     const uint32_t buf = D::OFF_BUF;
     uint64_t t = blockIdx.x;
@@ -219,17 +205,8 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_decode_rp_kernel(uint8_t* __re
                 status[t * TB + row] = (uint8_t)st;
         }
         barrier_lds();
-        if (WANT) {
-            uint8_t* dst = data + t * (TB * K);
-            const uint32_t nout = nb * (uint32_t)K;
-            for (uint32_t p = tid; 16u * p < nout; p += NTHR) {
-                const uint4 v = dec_piece<T2>(lds, buf, p);
-                if (16u * p + 16u <= nout)
-                    *(uint4*)(dst + 16u * p) = v;
-                else
-                    st_bytes(dst + 16u * p, v, nout - 16u * p);
-            }
-        }
+        if (WANT)
+            dec_emit_partial<T2>(lds, buf, data + t * (TB * K), nb * (uint32_t)K, tid, data, nblocks * K);
     }
 }
 

@@ -19,7 +19,6 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_encode_tkn_kernel(const uint8_
     static_assert(WPC * LDS_ALLOC <= 163840, "LDS for WPC workgroups per CU");
     constexpr int K = L::K;
     constexpr int IN_PIECES = TB * K / 16;
-    constexpr int OUT_PIECES = TB * 255 / 16;
     constexpr uint32_t KD = (IN_PIECES + 191) / 192; // DMA instructions per tile of a DMA wave
     constexpr uint32_t OFF_TK = D::BYTES;              // 8 ticket slots: slot i & 7 = tile of iteration i
     __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_ALLOC];
@@ -30,10 +29,7 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_encode_tkn_kernel(const uint8_
     const uint64_t nfull = nblocks / TB, ntiles = (nblocks + TB - 1) / TB;
     const uint32_t nx = gridDim.x < 8u ? gridDim.x : 8u, xc = blockIdx.x % nx;
     uint32_t* const my_ctr = ctr + 32u * xc; // 128-byte lines
-    for (uint32_t p = tid; p < (uint32_t)D::TBL / 16; p += NTHR)
-        *(uint4*)(lds + 16 * p) = *(const uint4*)(tables + 16 * p);
-    if (tid < 128)
-        *(uint64_t*)(lds + D::OFF_PAR + 8 * tid) = 0;
+    tables_to_lds<D::TBL, D::OFF_PAR>(lds, tables, tid);
     if (tk_lane) {
         const uint32_t base = atomicAdd(my_ctr, (uint32_t)NBUF);
 #pragma unroll
@@ -74,14 +70,7 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_encode_tkn_kernel(const uint8_
             *(uint64_t*)(lds + D::OFF_PAR + (pc ^ 1u) * 512u + 8u * lane) = 0;
         phase_remainder<T2, K, D::NMAP>(lds, buf, par, wave, row);
         barrier_lds(); // B: parity slots complete
-        uint8_t* dst = raw + q0 * (TB * 255);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t p = tid + 256u * k;
-            const uint4 o = enc_piece<T2>(lds, buf, par, p);
-            if ((k < 3 || p < (uint32_t)OUT_PIECES) && PPFS_DBG_OK(dst + 16u * p, 16, raw, nblocks * 255u))
-                st_nt<NTST>(dst + 16u * p, o);
-        }
+        enc_emit_tile<T2, NTST>(lds, buf, par, raw + q0 * (TB * 255), tid, raw, nblocks * 255u);
         ++iter;
         if (dmaw) {
             // the next tile's DMA (issued an iteration ago) landed; the stores since, and this
@@ -97,26 +86,7 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_encode_tkn_kernel(const uint8_
     }
     if (q0 == nfull && nfull < ntiles) { // the partial tile
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        barrier_lds();
-        const uint64_t t = nfull;
-        const uint32_t nb = (uint32_t)(nblocks - t * TB);
-        const uint32_t buf = D::OFF_BUF + cur * BUF, par = D::OFF_PAR + pc * 512u;
-        if (PPFS_DBG_OK(data + t * (TB * K), nb * K, data, nblocks * K))
-            stage_bytes(lds + buf + PAD, data + t * (TB * K), nb * K, tid);
-        barrier_lds();
-        phase_remainder<T2, K, D::NMAP>(lds, buf, par, wave, row);
-        barrier_lds();
-        uint8_t* dst = raw + t * (TB * 255);
-        const uint32_t nout = nb * 255u;
-        for (uint32_t p = tid; 16u * p < nout; p += NTHR) {
-            const uint4 v = enc_piece<T2>(lds, buf, par, p);
-            if (!PPFS_DBG_OK(dst + 16u * p, min(16u, nout - 16u * p), raw, nblocks * 255u))
-                continue;
-            if (16u * p + 16u <= nout)
-                *(uint4*)(dst + 16u * p) = v;
-            else
-                st_bytes(dst + 16u * p, v, nout - 16u * p);
-        }
+        enc_partial_tile<T2, D::NMAP>(lds, D::OFF_BUF + cur * BUF, D::OFF_PAR + pc * 512u, data, raw, nblocks, nfull, tid, wave, row);
     }
     if (tk_lane) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this workgroup's last ticket has returned
