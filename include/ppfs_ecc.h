@@ -193,17 +193,31 @@ size_t ppfs_ecc_host_chunk_blocks(ppfs_ecc_ctx* ctx);
  * emits payloads and statuses in list order.  No staging copy, no pieces, and no ordering against the
  * context's other list calls: two such decodes on different streams run side by side like two
  * contiguous calls (that ordering only ever protected the staging, never results).  The image may have
- * any alignment; nothing outside [d_image, d_image + image_blocks * 255) is read or written.  Encode
- * and write lists, every other codec, and a call whose d_data / d_status break the 16-byte rule keep
- * the staged path above; so does a context created while PPFS_ECC_LIST_DIRECT=0 is in the
- * environment (A/B measurements).  The extent reads below use the same kernel per piece for such a
- * context.
+ * any alignment; nothing outside [d_image, d_image + image_blocks * 255) is read or written.
+ * Direct list encode and write: the same contexts (ppfs_ecc_list_encode_kernel_name:
+ * "rs255-wg-list-store-lds") encode a list in ONE kernel, which stores codeword i at
+ * d_image + index[i] * 255 itself: every byte of a listed row is written once, no byte outside the
+ * listed rows is written, and nothing of the image is read, so neighbouring rows may be written by
+ * other calls at the same time.  A write list is the list decode for the old blocks' statuses (it
+ * changes nothing of the image) followed by that encode on `stream`; with d_status == NULL the encode
+ * alone, since an RS write needs nothing else of the old block.  Like the direct decode these calls
+ * use no staging and no pieces, and direct encode / write lists of one context on different streams
+ * are not ordered against each other or against the context's other list calls.  Repeated indices
+ * stay memory-safe with an unspecified result: each byte of such a row is the corresponding byte of
+ * one of the listed payloads' codewords.
+ * Every other codec, and a call whose d_data / d_status break the 16-byte rule, keep the staged path
+ * above; so does a context created while PPFS_ECC_LIST_DIRECT=0 is in the environment (A/B
+ * measurements).  The extent calls below use the same kernels per piece for such a context.
  * Host forms: same arguments with host pointers and no stream; they return when the results are in
  * host memory.
  */
 /* How ctx decodes a device list: "rs255-wg-list-lds" (the direct kernel) or "gather-stage-scatter" (the
  * staged pipeline); "" for a null ctx.  Engine extension, no reference counterpart. */
 const char* ppfs_ecc_list_kernel_name(const ppfs_ecc_ctx* ctx);
+/* How ctx encodes and writes a device list: "rs255-wg-list-store-lds" (the direct kernel) or
+ * "gather-stage-scatter" (the staged pipeline); "" for a null ctx.  Engine extension, no reference
+ * counterpart. */
+const char* ppfs_ecc_list_encode_kernel_name(const ppfs_ecc_ctx* ctx);
 int ppfs_ecc_decode_list_device(ppfs_ecc_ctx* ctx, uint8_t* d_image, size_t image_blocks, const uint32_t* d_index,
     size_t nblocks, uint8_t* d_data, uint8_t* d_status, int write_back, uint8_t* d_spill, void* stream);
 int ppfs_ecc_encode_list_device(ppfs_ecc_ctx* ctx, const uint8_t* d_data, uint8_t* d_image, size_t image_blocks,
@@ -252,7 +266,10 @@ int ppfs_ecc_write_list_host(ppfs_ecc_ctx* ctx, const uint8_t* data, uint8_t* im
  * same size on `stream`, plus a second staging allocation for the decoded payloads made at the first
  * extent call; they wait for and are waited for by the context's staged list calls.  A context that
  * decodes lists directly (ppfs_ecc_list_kernel_name) reads a piece with that one kernel in place of the
- * gather, decode, scatter and range marks; the payload staging, the pieces and their ordering stay.
+ * gather, decode, scatter and range marks, and writes a piece as that list decode (old payloads and
+ * statuses, nothing written back), the overlay of the caller's bytes and the list encode
+ * (ppfs_ecc_list_encode_kernel_name) in place of gather, decode, overlay, write, scatter and range
+ * marks; the payload staging, the pieces and their ordering stay.
  * A capturing stream gets
  * PPFS_ECC_ENOTSUP.  There is no spill argument: a shortened RS code (n < 255) is decoded as by a list
  * decode with d_spill == NULL.  PPFS_ECC_NONE: plain byte copies under the same validity rules.

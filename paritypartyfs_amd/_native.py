@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = (
     "ppfs_ecc_write_host",
     "ppfs_ecc_host_chunk_blocks",
     "ppfs_ecc_list_kernel_name",
+    "ppfs_ecc_list_encode_kernel_name",
     "ppfs_ecc_decode_list_device",
     "ppfs_ecc_encode_list_device",
     "ppfs_ecc_write_list_device",
@@ -157,6 +158,8 @@ def lib() -> ctypes.CDLL:
     L.ppfs_ecc_write_host.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]
     L.ppfs_ecc_list_kernel_name.restype = c_char_p
     L.ppfs_ecc_list_kernel_name.argtypes = [c_void_p]
+    L.ppfs_ecc_list_encode_kernel_name.restype = c_char_p
+    L.ppfs_ecc_list_encode_kernel_name.argtypes = [c_void_p]
     # block lists: (ctx, image, image_blocks, index, nblocks, data, status, write_back, spill[, stream])
     L.ppfs_ecc_decode_list_device.restype = c_int
     L.ppfs_ecc_decode_list_device.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_int,

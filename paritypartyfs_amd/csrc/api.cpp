@@ -367,7 +367,7 @@ extern "C" int ppfs_ecc_create(const ppfs_ecc_params* params, int device, ppfs_e
         if (c->rs_fast) {
             tables = build_rs_fast_tables(c->rs_t2);
             c->kname = ppfs_rs_fast_path(c->rs_t2);
-            // PPFS_ECC_LIST_DIRECT=0: list decodes of this context take the staged path (A/B runs)
+            // PPFS_ECC_LIST_DIRECT=0: list calls of this context take the staged path (A/B runs)
             const char* ld = std::getenv("PPFS_ECC_LIST_DIRECT");
             c->list_direct = rs_wb_direct(c) && !(ld && ld[0] == '0' && !ld[1]);
         } else {
@@ -551,6 +551,10 @@ extern "C" const char* ppfs_ecc_kernel_name(const ppfs_ecc_ctx* c) { return c ? 
 extern "C" const char* ppfs_ecc_list_kernel_name(const ppfs_ecc_ctx* c)
 {
     return !c ? "" : c->list_direct ? "rs255-wg-list-lds" : "gather-stage-scatter";
+}
+extern "C" const char* ppfs_ecc_list_encode_kernel_name(const ppfs_ecc_ctx* c)
+{
+    return !c ? "" : c->list_direct ? "rs255-wg-list-store-lds" : "gather-stage-scatter";
 }
 
 // PPFS_ECC_DEBUG builds: out-of-bounds global accesses the kernels detected and skipped (dbg.hpp),

@@ -139,7 +139,7 @@ struct ppfs_ecc_ctx {
     size_t list_bytes = 0, list_status_off = 0;
     hipEvent_t list_ev = nullptr;
     bool list_ev_rec = false;
-    // list decodes go through the one-kernel direct path (rs_wg_list.hpp): RS(255, 255-2t), 2t <= 8,
+    // list decodes, encodes and writes go through the one-kernel direct paths (rs_wg_list.hpp): RS(255, 255-2t), 2t <= 8,
     // unless PPFS_ECC_LIST_DIRECT=0 was set when the context was created (list_path.cpp)
     bool list_direct = false;
     // byte-extent calls (extent_path.cpp): the decoded payloads of one piece and the staged index of
@@ -194,6 +194,11 @@ int decode_device_to(ppfs_ecc_ctx* c, uint8_t* d_raw, uint8_t* d_data, uint8_t* 
 bool list_direct_args(const ppfs_ecc_ctx* c, const void* d_data, const void* d_status);
 int decode_list_direct(ppfs_ecc_ctx* c, uint8_t* d_image, size_t image_blocks, const uint32_t* d_index, size_t nblocks,
     uint8_t* d_data, uint8_t* d_status, int write_back, uint8_t* d_spill, hipStream_t s);
+// The direct list encode (list_path.cpp; the same contexts): one rs_wg_list.hpp launch on s that stores
+// the codeword of payload i at image + index[i] * 255, framed by the caller as above; list_direct_args
+// is its gate too (d_data, and a write's d_status).
+int encode_list_direct(ppfs_ecc_ctx* c, const uint8_t* d_data, uint8_t* d_image, size_t image_blocks, const uint32_t* d_index,
+    size_t nblocks, hipStream_t s);
 
 // What every device entry point does around the work it queues on a caller's stream (api.cpp), for
 // the entry points outside api.cpp: call_ordered before the first launch (after the last call on the

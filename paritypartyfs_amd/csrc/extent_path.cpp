@@ -17,7 +17,10 @@
 // A context that decodes lists directly (ctx.hpp list_direct; RS(255, 255-2t), 2t <= 8) reads a piece as
 //   read   index -> list decode(image, index -> P, status, write_back) -> pack P
 // one kernel for the gather, decode, scatter and range marks: the staged index 0xFFFFFFFF of an invalid
-// entry comes out of it as status 9 and a zero payload.  P, the piece size and list_ev stay.
+// entry comes out of it as status 9 and a zero payload, and writes it as
+//   write  index -> list decode(image, index -> P, status; nothing written back) -> overlay ->
+//          list encode(P -> image, rs_wg_encode_list_kernel)
+// where an invalid entry's codeword is stored nowhere.  P, the piece size and list_ev stay.
 // Host forms: the list is cut into runs without a repeated valid block, each run is gathered on the
 // CPU, goes through the contiguous host calls and is copied back.  The arithmetic of both is in
 // extent_plan.hpp.
@@ -167,6 +170,20 @@ extern "C" int ppfs_ecc_write_extents_device(ppfs_ecc_ctx* c, const uint8_t* d_i
             const ppfs_ecc_extent* ex = d_ext + off;
             uint8_t* st = p.status_for(d_status, off); // the scatter selects by status: always one
             r = check_hip(ppfs_extent_index_launch(ex, nb, p.blocks, ds, in_bytes, p.idx, call.s), "extent index");
+            if (!r && c->list_direct) { // P and st are 16-byte aligned (ext_stage_layout, status_for)
+                // the old payloads and statuses (9 and zeros for an invalid entry) without touching the
+                // image, the caller's bytes over them, the new codewords stored in place
+                r = decode_list_direct(c, d_image, p.blocks, p.idx, nb, p.P, st, 0, nullptr, call.s);
+                if (!r)
+                    r = check_hip(ppfs_extent_copy_launch(1, ex, p.idx, nullptr, nb, ds, p.P, p.P_cap,
+                                      const_cast<uint8_t*>(d_in), in_bytes, call.s),
+                        "extent overlay");
+                if (!r)
+                    r = encode_list_direct(c, p.P, d_image, p.blocks, p.idx, nb, call.s);
+                if (!r)
+                    r = p.status_out(st, d_status, off, nb, call.s, false);
+                continue;
+            }
             if (!r)
                 r = check_hip(ppfs_gather_blocks_launch(d_image, p.blocks, p.idx, nb, raw, p.rows, call.s), "extent gather");
             // the old payloads: where the old block fails its check (status 5 below) the row is not

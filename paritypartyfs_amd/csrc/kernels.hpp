@@ -28,6 +28,10 @@ hipError_t ppfs_rs_fast_decode(int t2, uint8_t* r, uint8_t* d, uint8_t* st, uint
 // d (16-byte aligned or null) and st (or null) in list order
 hipError_t ppfs_rs_list_decode(int t2, uint8_t* image, uint64_t image_blocks, const uint32_t* index, uint8_t* d, uint8_t* st,
     uint64_t nb, const uint8_t* tab, int wb, hipStream_t s);
+// the list encode in one kernel: payload i of d (16-byte aligned, list order) -> image row index[i]; an
+// entry >= image_blocks stores nothing
+hipError_t ppfs_rs_list_encode(int t2, const uint8_t* d, uint8_t* image, uint64_t image_blocks, const uint32_t* index,
+    uint64_t nb, const uint8_t* tab, hipStream_t s);
 hipError_t ppfs_rs_generic_encode(const uint8_t* d, uint8_t* r, uint64_t nb, int n, int t2, const uint8_t* tab,
     hipStream_t s);
 hipError_t ppfs_rs_generic_decode(uint8_t* r, uint8_t* d, uint8_t* st, uint8_t* spill, uint64_t nb, int n, int t2,

@@ -10,7 +10,11 @@
 // RS(255, 255-2t), 2t <= 8 decodes a list in one kernel instead (rs_wg_list.hpp: the rows are fetched
 // from the image by the codec kernel's loader and corrected in place): no staging, no pieces, no
 // list_ev, framed like a contiguous device call.  PPFS_ECC_LIST_DIRECT=0 at ppfs_ecc_create keeps such
-// a context on the staged path.
+// a context on the staged path.  Such a context also encodes and writes a list directly: the list encode
+// (rs_wg_list.hpp rs_wg_encode_list_kernel) stores codeword i at image + index[i] * 255 itself, and an RS
+// write needs nothing of the old block but its status (rs_block_device.cpp:61-93), which the list
+// decode gives without touching the image -- two kernels on the caller's stream in place of gather,
+// decode, encode, scatter and range marks.
 // Host forms: the list is cut into runs without a repeated index, each run is gathered on the CPU
 // and handed to the contiguous host call, and the rows that changed are copied back.
 // The arithmetic of both is in list_plan.hpp.
@@ -113,6 +117,15 @@ int ppfs::decode_list_direct(ppfs_ecc_ctx* c, uint8_t* d_image, size_t image_blo
         "rs list decode");
 }
 
+// The direct list encode.  Its gate is list_direct_args too: d_data by the rule of the contiguous RS
+// encode (ppfs_ecc_encode_device), a write's d_status by the decode's.
+int ppfs::encode_list_direct(ppfs_ecc_ctx* c, const uint8_t* d_data, uint8_t* d_image, size_t image_blocks,
+    const uint32_t* d_index, size_t nblocks, hipStream_t s)
+{
+    return check_hip(ppfs_rs_list_encode(c->rs_t2, d_data, d_image, image_blocks, d_index, nblocks, c->d_tables, s),
+        "rs list encode");
+}
+
 namespace {
 
 int list_args(ppfs_ecc_ctx* c, const void* d_image, size_t image_blocks, const void* d_index, size_t nblocks,
@@ -172,6 +185,11 @@ extern "C" int ppfs_ecc_encode_list_device(ppfs_ecc_ctx* c, const uint8_t* d_dat
     int r = list_args(c, d_image, image_blocks, d_index, nblocks, d_data, true, stream, "encode list: null argument");
     if (r || nblocks == 0)
         return r;
+    if (list_direct_args(c, d_data, nullptr)) {
+        (void)call_ordered(c, nblocks, stream);
+        r = encode_list_direct(c, d_data, d_image, image_blocks, d_index, nblocks, (hipStream_t)stream);
+        return call_queued(c, r, nblocks, stream, "encode list (async)");
+    }
     ListCall call { c, (hipStream_t)stream, stream, nblocks };
     if ((r = call.begin()))
         return r;
@@ -197,6 +215,18 @@ extern "C" int ppfs_ecc_write_list_device(ppfs_ecc_ctx* c, const uint8_t* d_data
     int r = list_args(c, d_image, image_blocks, d_index, nblocks, d_data, true, stream, "write list: null argument");
     if (r || nblocks == 0)
         return r;
+    if (list_direct_args(c, d_data, d_status)) {
+        // the old blocks' statuses (0 / 1, 9 for an entry out of range) by the list decode, which
+        // changes nothing; then the new codewords, whatever the status was.  Without d_status the
+        // encode alone: RS needs nothing else of the old block.
+        hipStream_t s = (hipStream_t)stream;
+        (void)call_ordered(c, nblocks, stream);
+        if (d_status)
+            r = decode_list_direct(c, d_image, image_blocks, d_index, nblocks, nullptr, d_status, 0, nullptr, s);
+        if (!r)
+            r = encode_list_direct(c, d_data, d_image, image_blocks, d_index, nblocks, s);
+        return call_queued(c, r, nblocks, stream, "write list (async)");
+    }
     ListCall call { c, (hipStream_t)stream, stream, nblocks };
     if ((r = call.begin()))
         return r;

@@ -4,7 +4,8 @@
 // pair kernels) live in tools/ablations/ and are built by tools/build_alt.sh.
 //   2t <= 8      rs_wg_tk.hpp ticket-counter encode / decode (every context hands a counter set
 //                for its first 16 streams, api.cpp ctr_for); rs_wg.hpp static-walk kernels otherwise;
-//                rs_wg_list.hpp the block-list decode (rows fetched from the image by the kernel)
+//                rs_wg_list.hpp the block-list decode (rows fetched from the image by the kernel) and
+//                encode (rows stored into the image by the kernel)
 //   8 < 2t <= 16 rs_fast.hpp lane-per-block kernels; 2t = 16 encodes with rs_pair.hpp's solo image kernel
 //   2t = 32      rs_bs.hpp byte-slice kernels (cfg5, RS(255,223))
 #include "rs_fast.hpp"
@@ -151,6 +152,20 @@ extern "C" hipError_t PPFS_CAT(ppfs_rs_list_decode_t, PPFS_T2)(uint8_t* image, u
 {
     PPFS_LAUNCH((wg::rs_wg_decode_list_kernel<PPFS_T2, DEC_WPC, 1>), dim3(rs_tile_grid(nb, DEC_WPC)), dim3(256), 0, s, image,
         image_blocks, index, d, st, nb, tab, wb);
+    return hipGetLastError();
+}
+// the block-list encode (rs_wg_list.hpp; list_path.cpp): payload i -> image row index[i].  A static walk
+// with two tile buffers, 3 workgroups per CU.  Plain stores: non-temporal ones measured 2x slower on
+// these scattered 255-byte rows (2^20 blocks, permuted: 368 against 173 us).
+#ifndef PPFS_LIST_ENC_NTST
+#define PPFS_LIST_ENC_NTST 0 // 1 (tools/build_alt.sh --product): non-temporal stores, the A/B build
+#endif
+constexpr int LIST_ENC_WPC = 3, LIST_ENC_NTST = PPFS_LIST_ENC_NTST;
+extern "C" hipError_t PPFS_CAT(ppfs_rs_list_encode_t, PPFS_T2)(const uint8_t* d, uint8_t* image, uint64_t image_blocks,
+    const uint32_t* index, uint64_t nb, const uint8_t* tab, hipStream_t s)
+{
+    PPFS_LAUNCH((wg::rs_wg_encode_list_kernel<PPFS_T2, LIST_ENC_WPC, LIST_ENC_NTST>), dim3(rs_tile_grid(nb, LIST_ENC_WPC)),
+        dim3(256), 0, s, d, image, image_blocks, index, nb, tab);
     return hipGetLastError();
 }
 #endif

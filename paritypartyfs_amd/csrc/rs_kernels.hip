@@ -336,6 +336,26 @@ extern "C" hipError_t ppfs_rs_list_decode(int t2, uint8_t* image, uint64_t image
     }
 }
 
+// block-list encode in one kernel (rs_wg_list.hpp), 2t <= 8
+#define X(T)                                                                                                           \
+    extern "C" hipError_t ppfs_rs_list_encode_t##T(const uint8_t*, uint8_t*, uint64_t, const uint32_t*, uint64_t,     \
+        const uint8_t*, hipStream_t);
+PPFS_RS_LIST_CASES(X)
+#undef X
+extern "C" hipError_t ppfs_rs_list_encode(int t2, const uint8_t* d, uint8_t* image, uint64_t image_blocks, const uint32_t* index,
+    uint64_t nb, const uint8_t* tab, hipStream_t s)
+{
+    switch (t2) {
+#define X(T)                                                                                                           \
+    case T:                                                                                                            \
+        return ppfs_rs_list_encode_t##T(d, image, image_blocks, index, nb, tab, s);
+        PPFS_RS_LIST_CASES(X)
+#undef X
+    default:
+        return hipErrorInvalidValue;
+    }
+}
+
 // resident small-batch servers (2t <= 8: segment-layout tables; 10, 16: lane-per-block; 32: pair layout)
 #define PPFS_RS_SERVER_CASES(X) X(2) X(4) X(6) X(8) X(10) X(16) X(32)
 #define X(T)                                                                                                           \

@@ -347,11 +347,12 @@ template <int N> __device__ __forceinline__ void lds_window(uint32_t (&d)[N], co
 // Encode emission: 16 bytes of the codeword tile at piece p, from the LDS payload rows and the
 // combined parity slots.  Codeword byte j of block b = j / 255 (off = j % 255): parity byte off if
 // off < 2t, else payload byte K b + off - 2t.  A piece may run into block b+1 (off > 239).
+// enc_piece_at: the 16 codeword bytes from byte off (any, 0..255) of block b, which is what the
+// list encode's emission cuts its rows into (rs_wg_list.hpp).
 template <int T2>
-__device__ __forceinline__ uint4 enc_piece(const uint8_t* lds, uint32_t buf, uint32_t par, uint32_t p)
+__device__ __forceinline__ uint4 enc_piece_at(const uint8_t* lds, uint32_t buf, uint32_t par, uint32_t b, uint32_t off)
 {
     constexpr uint32_t K = 255 - T2;
-    const uint32_t j0 = p * 16u, b = j0 / 255u, off = j0 - 255u * b;
     const uint32_t S = buf + PAD + K * b + off - T2; // LDS byte of output byte 0's payload source
     const uint32_t sh = (S & 3u) * 8u;
     uint32_t d[5];
@@ -392,6 +393,12 @@ __device__ __forceinline__ uint4 enc_piece(const uint8_t* lds, uint32_t buf, uin
         o[m] = v;
     }
     return make_uint4(o[0], o[1], o[2], o[3]);
+}
+template <int T2>
+__device__ __forceinline__ uint4 enc_piece(const uint8_t* lds, uint32_t buf, uint32_t par, uint32_t p)
+{
+    const uint32_t j0 = p * 16u, b = j0 / 255u;
+    return enc_piece_at<T2>(lds, buf, par, b, j0 - 255u * b);
 }
 
 // Decode emission: 16 bytes of the payload tile at piece p from the (corrected) LDS codeword rows:

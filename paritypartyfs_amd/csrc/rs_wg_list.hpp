@@ -23,8 +23,13 @@
 // An entry index[i] >= image_blocks (0xFFFFFFFF among them) is never dereferenced: its LDS row is
 // zeros -- a valid codeword, so the payload comes out zero by itself -- wave 0 stores status 9
 // (PPFS_ECC_OUT_OF_BOUNDS) for it, and it takes no write-back.
+//
+// The block-list encode (rs_wg_encode_list_kernel, at the end of the file) is the other direction:
+// the static-walk encode with another emission, which stores codeword i at image + index[i] * 255
+// by the store plan of list_store.hpp.
 #include "funnel.hpp"
 #include "list_fetch.hpp"
+#include "list_store.hpp"
 #include "rs_wg.hpp"
 
 namespace ppfs {
@@ -222,6 +227,153 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_decode_list_kernel(uint8_t* im
         cur ^= 1u;
         pc ^= 1u;
         first = false;
+    }
+}
+
+// ------------------------------------------------------------------------------------
+// The block-list encode: payload i of the (contiguous, list-order) payload array becomes the
+// codeword at image + index[i] * 255.  The static-walk encode of rs_wg.hpp with another emission:
+// loader (LDS-DMA of the packed payload rows), remainder phase and parity slots are that kernel's;
+// the emission cuts each LDS row by the store plan of list_store.hpp instead of cutting the packed
+// codeword tile into 16-byte pieces, and takes each piece from enc_piece_at, the contiguous
+// emission's own assembly at any byte of a row.  No staging rows, no scatter.
+//
+// Buffering: two tile buffers, the next tile's DMA issued after barrier A.  The waves' store counts
+// differ here (a wave's round has 60 or 64 lanes on full windows, one wave has the edges, rows that
+// name no block store nothing), so the contiguous encode's counted wait -- "4 stores per wave per
+// tile" -- does not hold, and no count is kept: every wave waits vmcnt(0) once per tile, after its
+// remainder phase and before barrier B.  What is outstanding there is the last tile's stores and
+// this iteration's DMA, both issued a whole remainder phase earlier; this tile's stores are issued
+// after it and fly through the next tile's remainder phase.  Exact because it counts nothing: after
+// barrier B every wave's DMA pieces of the next tile have landed, which is all barrier A of the next
+// iteration needs.
+//
+// The tile's 64 entries are one coalesced load of wave 1, issued at the top of the iteration before
+// and parked in one of two 256-byte LDS slots after that iteration's vmcnt(0), so a store address
+// depends on no global load of its own iteration.  The partial last tile is staged by plain loads
+// (never past data + nblocks * K) and goes through the same emission: list_entry gives the rows past
+// the list's end the entry 0xFFFFFFFF, which stores nothing.
+// ------------------------------------------------------------------------------------
+template <int NT, typename T> __device__ __forceinline__ void st_narrow(uint8_t* dst, T v)
+{
+    if constexpr (NT)
+        __builtin_nontemporal_store(v, (T*)dst);
+    else
+        *(T*)dst = v;
+}
+
+// bytes [o, o + 8) of the 16-byte piece v (o in [0, 16); bytes past the piece read as zero)
+__device__ __forceinline__ uint64_t piece_bytes8(uint4 v, uint32_t o)
+{
+    const uint64_t lo = ((uint64_t)v.y << 32) | v.x, hi = ((uint64_t)v.w << 32) | v.z;
+    const uint64_t a = o < 8u ? lo : hi, b = o < 8u ? hi : 0ull;
+    const uint32_t s = 8u * (o & 7u);
+    return s ? (a >> s) | (b << (64u - s)) : a;
+}
+
+// Emission of the tile in `buf` (parity slots `par`) whose 64 entries are slot[0..63]: this thread's 4
+// slots of the store plan (slot tid + 256 k)
+template <int T2, int NTST>
+__device__ __forceinline__ void list_emit_tile(const uint8_t* lds, uint32_t buf, uint32_t par, const uint32_t* slot,
+    uint8_t* image, uint64_t image_blocks, uint32_t tid)
+{
+    const uint64_t base = (uint64_t)(uintptr_t)image;
+    [[maybe_unused]] const uint64_t img_bytes = image_blocks * liststore::ROW;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t s = tid + 256u * k;
+        if (k < 3 || s < liststore::TILE_FULL) { // k = 3: waves 0..2
+            const liststore::Full f = liststore::full_slot(s);
+            const liststore::Dst x = liststore::row_dst(base, image_blocks, slot[f.row]);
+            const liststore::Piece pc = liststore::full_piece(x, f.j);
+            const uint4 v = enc_piece_at<T2>(lds, buf, par, f.row, pc.c0);
+            if (x.live) {
+                uint8_t* p = image + (pc.a - base);
+                if (PPFS_DBG_OK(p, 16, image, img_bytes))
+                    st_nt<NTST>(p, v);
+            }
+        } else { // the 64 edges: wave 3, a row per lane
+            const uint32_t r = s - liststore::TILE_FULL;
+            const liststore::Dst x = liststore::row_dst(base, image_blocks, slot[r]);
+            const uint32_t tail0 = x.h + liststore::TAIL_C0;
+            const uint4 hv = enc_piece_at<T2>(lds, buf, par, r, 0u), tv = enc_piece_at<T2>(lds, buf, par, r, tail0);
+#pragma unroll
+            for (int q = 0; q < (int)liststore::EDGE_PIECES; ++q) {
+                const liststore::Piece pc = liststore::edge_piece(x, (uint32_t)q);
+                const uint64_t bits = piece_bytes8(q < 4 ? hv : tv, pc.c0 - (q < 4 ? 0u : tail0));
+                if (x.live && pc.size) {
+                    uint8_t* p = image + (pc.a - base);
+                    if (!PPFS_DBG_OK(p, pc.size, image, img_bytes))
+                        continue;
+                    const int SIZE = q < 4 ? 1 << q : 8 >> (q - 4); // pc.size where there is a piece; a constant once unrolled
+                    if (SIZE == 1)
+                        st_narrow<NTST>(p, (uint8_t)bits);
+                    else if (SIZE == 2)
+                        st_narrow<NTST>(p, (uint16_t)bits);
+                    else if (SIZE == 4)
+                        st_narrow<NTST>(p, (uint32_t)bits);
+                    else
+                        st_narrow<NTST>(p, bits);
+                }
+            }
+        }
+    }
+}
+
+template <int T2, int WPC = 3, int NTST = 1>
+__global__ __launch_bounds__(256, WPC) void rs_wg_encode_list_kernel(const uint8_t* __restrict__ data, uint8_t* image,
+    uint64_t image_blocks, const uint32_t* __restrict__ index, uint64_t nblocks, const uint8_t* __restrict__ tables)
+{
+    using L = RsWgLayout<T2>;
+    using D = Lds<T2, false, 2>;
+    constexpr int OFF_IDX = D::BYTES; // two sets of 64 entries: this tile's and the next one's
+    constexpr int LDS_ALLOC = lds_alloc<D::BYTES + 512, WPC>();
+    static_assert(WPC * LDS_ALLOC <= 163840, "LDS for WPC workgroups per CU");
+    static_assert(OFF_IDX % 16 == 0, "aligned index slots");
+    constexpr int K = L::K;
+    constexpr int IN_PIECES = TB * K / 16;
+    __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_ALLOC];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = wave_id();
+    const uint32_t row = lane_row(lane);
+    uint32_t* const slot = (uint32_t*)(lds + OFF_IDX);
+    tables_to_lds<D::TBL, D::OFF_PAR>(lds, tables, tid);
+    const uint64_t nfull = nblocks / TB, ntiles = (nblocks + TB - 1) / TB;
+    const uint64_t G = gridDim.x;
+    uint64_t t = blockIdx.x;
+    if (t >= ntiles)
+        return;
+    uint32_t cur = 0, pc = 0; // tile buffer; parity-slot and entry set
+    if (t < nfull)
+        dma_tile<IN_PIECES>(lds + D::OFF_BUF + PAD, data + t * (TB * K), tid, data, nblocks * K);
+    if (wave == 1)
+        slot[lane] = list_entry(index, t * TB + lane, nblocks);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    for (; t < ntiles; t += G) {
+        barrier_lds(); // A: tile t and its entries in LDS, last tile's emission reads done
+        const uint32_t buf = D::OFF_BUF + cur * BUF, par = D::OFF_PAR + pc * 512u;
+        const uint64_t nx = t + G;
+        if (nx < nfull)
+            dma_tile<IN_PIECES>(lds + D::OFF_BUF + (cur ^ 1u) * BUF + PAD, data + nx * (TB * K), tid, data, nblocks * K);
+        uint32_t next_idx = 0xFFFFFFFFu;
+        if (wave == 1 && nx < ntiles)
+            next_idx = list_entry(index, nx * TB + lane, nblocks);
+        if (t >= nfull) { // the partial last tile: no DMA brought it
+            const uint32_t nb = (uint32_t)(nblocks - t * TB);
+            if (PPFS_DBG_OK(data + t * (TB * K), nb * K, data, nblocks * K))
+                stage_bytes(lds + buf + PAD, data + t * (TB * K), nb * K, tid);
+            barrier_lds();
+        }
+        if (wave == 0)
+            *(uint64_t*)(lds + D::OFF_PAR + (pc ^ 1u) * 512u + 8u * lane) = 0;
+        phase_remainder<T2, K, D::NMAP>(lds, buf, par, wave, row);
+        // the last tile's stores and the next tile's DMA and entries (see the header comment)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (wave == 1 && nx < ntiles)
+            slot[64u * (pc ^ 1u) + lane] = next_idx;
+        barrier_lds(); // B: parity slots complete, the next tile landed
+        list_emit_tile<T2, NTST>(lds, buf, par, slot + 64u * pc, image, image_blocks, tid);
+        cur ^= 1u;
+        pc ^= 1u;
     }
 }
 

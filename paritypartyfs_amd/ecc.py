@@ -197,6 +197,12 @@ class EccEngine:
         the listed rows itself (RS bs >= 255, t <= 4), or "gather-stage-scatter", the staged pipeline."""
         return lib().ppfs_ecc_list_kernel_name(self._h).decode()
 
+    def list_encode_kernel_name(self) -> str:
+        """How encode_list and write_list run (ppfs_ecc_list_encode_kernel_name): "rs255-wg-list-store-lds",
+        one kernel that stores each codeword at its row of the image (RS bs >= 255, t <= 4), or
+        "gather-stage-scatter", the staged pipeline."""
+        return lib().ppfs_ecc_list_encode_kernel_name(self._h).decode()
+
     def decode_list(self, image, index, data=None, status=None, write_back: bool = True, spill=None, stream=None) -> None:
         n, blocks = self._list_check("device", image, index, data, status, spill)
         check(lib().ppfs_ecc_decode_list_device(self._h, _ptr(image), blocks, self._index_ptr(index), n, _ptr(data),

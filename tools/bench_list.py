@@ -20,13 +20,27 @@ With --extents, for RS(255,249) only, the two byte-extent legs beside their yard
   device copy of the packed bytes    what the pack's traffic costs as a plain copy
   write_extents, 64 bytes at 32      one 64-byte segment at offset 32 of every permuted block
   write_list, same permutation       the yardstick of the write
+  (all four legs again under PPFS_ECC_LIST_DIRECT=0: staged_*_us)
 Recorded, not gating: DESIGN.md "Byte extents".
+
+With --writes, the write side: RS(255,249) and RS(255,251) at 2^12, 2^16 and 2^20 blocks, RS(255,223)
+(staged only) at 2^20:
+  encode_list, identity / permuted   the codewords stored at image + index[i] * 255
+  encode (contiguous)                ppfs_ecc_encode_device of the same payloads: the yardstick
+  write_list, identity / permuted    old blocks with one byte error each (re-corrupted untimed)
+  write (contiguous)                 ppfs_ecc_write_device over the same image
+  device copy                        the image's bytes
+A codec whose list encode is the direct kernel (EccEngine.list_encode_kernel_name) is measured again in a
+worker under PPFS_ECC_LIST_DIRECT=0; the record carries both, their ratio, and per leg whether the direct
+median lies below the staged minimum of its runs (direct_below_staged_min_*: the routing rule of
+DESIGN.md "Block lists").
 
 Every codec is measured in a child process of its own under a time limit; the first child that
 fails ends the run.
 
     python tools/bench_list.py [--blocks 4096,65536,1048576 --reps 7 --out profiles/list_io.json]
     python tools/bench_list.py --extents [--out profiles/extent_io.json]
+    python tools/bench_list.py --writes [--out profiles/list_write_io.json]
 """
 import argparse
 import json
@@ -183,11 +197,84 @@ def worker_extents(bs: int, t: int, blocks: int, reps: int) -> dict:
     return res
 
 
-def run_worker(bs: int, t: int, blocks: int, reps: int, extents: bool, staged: bool):
-    """One measurement in a child process under a time limit; staged: with PPFS_ECC_LIST_DIRECT=0 in its
-    environment.  None when the child failed."""
+def worker_writes(bs: int, t: int, blocks: int, reps: int) -> dict:
+    import numpy as np
+    import torch
+
+    from paritypartyfs_amd import ECC_REED_SOLOMON, EccEngine, device_copy, inject_bytes
+
+    torch.cuda.set_device(0)
+    eng = EccEngine(ECC_REED_SOLOMON, bs, t)
+    n, k = eng.raw_block_size, eng.data_size
+    g = torch.Generator(device="cuda").manual_seed(20240611)
+    old = torch.randint(0, 256, (blocks * k,), dtype=torch.uint8, device="cuda", generator=g)
+    data = torch.randint(0, 256, (blocks * k,), dtype=torch.uint8, device="cuda", generator=g)  # the payloads written
+    image = torch.empty(blocks * n, dtype=torch.uint8, device="cuda")
+    want = torch.empty_like(image)  # the new codewords in list order
+    eng.encode(data, want)
+    pos = torch.randint(0, n, (blocks,), dtype=torch.uint8, device="cuda", generator=g)
+    val = torch.randint(1, 256, (blocks,), dtype=torch.uint8, device="cuda", generator=g)
+    st = torch.empty(blocks, dtype=torch.uint8, device="cuda")
+    dst = torch.empty_like(image)
+    ident = torch.arange(blocks, dtype=torch.int32, device="cuda")
+    perm = torch.from_numpy(np.random.default_rng(7).permutation(blocks).astype(np.int32)).cuda()
+
+    spread = {}
+
+    def timed(name, fn, before=None):
+        ms = []
+        for r in range(reps + 2):  # two warm-up runs
+            if before:
+                before()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if r >= 2:
+                ms.append(a.elapsed_time(b))
+        spread[name + "_minmax_us"] = [min(ms) * 1e3, max(ms) * 1e3]
+        return statistics.median(ms) * 1e3  # us
+
+    def old_blocks():  # valid old codewords with one byte error each, untimed
+        eng.encode(old, image)
+        inject_bytes(image, n, pos, val, xor=True)
+
+    def landed(ix, what):
+        assert torch.equal(image.view(blocks, n)[ix.long()], want.view(blocks, n)), what + ": codewords differ"
+
+    res = {}
+    image.zero_()
+    res["encode_list_identity_us"] = timed("encode_list_identity", lambda: eng.encode_list(data, image, ident))
+    landed(ident, "encode_list identity")
+    image.zero_()
+    res["encode_list_permuted_us"] = timed("encode_list_permuted", lambda: eng.encode_list(data, image, perm))
+    landed(perm, "encode_list permuted")
+    res["encode_us"] = timed("encode", lambda: eng.encode(data, image))
+    res["write_list_identity_us"] = timed("write_list_identity", lambda: eng.write_list(data, image, ident, st), old_blocks)
+    assert int(st.min()) == 1 and int(st.max()) == 1, "write_list identity: every old block had one error"
+    landed(ident, "write_list identity")
+    res["write_list_permuted_us"] = timed("write_list_permuted", lambda: eng.write_list(data, image, perm, st), old_blocks)
+    assert int(st.min()) == 1 and int(st.max()) == 1, "write_list permuted: every old block had one error"
+    landed(perm, "write_list permuted")
+    res["write_us"] = timed("write", lambda: eng.write(data, image, st), old_blocks)
+    assert int(st.min()) == 1 and int(st.max()) == 1
+    res["copy_us"] = timed("copy", lambda: device_copy(dst, image))
+    res.update(spread)
+    for leg, yard in (("encode_list_identity", "encode"), ("encode_list_permuted", "encode"),
+                      ("write_list_identity", "write"), ("write_list_permuted", "write")):
+        res[leg + "_over_contiguous"] = res[leg + "_us"] / res[yard + "_us"]
+    res.update(blocks=blocks, raw_block_size=n, data_size=k, reps=reps, image_bytes=blocks * n,
+               piece_blocks=eng.host_chunk_blocks() & ~1023, kernel=eng.kernel_name, list_kernel=eng.list_kernel_name(),
+               list_encode_kernel=eng.list_encode_kernel_name(), device=torch.cuda.get_device_name(0))
+    return res
+
+
+def run_worker(bs: int, t: int, blocks: int, reps: int, mode: str, staged: bool):
+    """One measurement in a child process under a time limit; mode: "", "--extents" or "--writes"; staged:
+    with PPFS_ECC_LIST_DIRECT=0 in its environment.  None when the child failed."""
     cmd = ["timeout", "-k", "10", str(STEP_TIMEOUT_S), sys.executable, os.path.abspath(__file__), "--blocks", str(blocks),
-           "--reps", str(reps), "--worker", str(bs), str(t)] + (["--extents"] if extents else [])
+           "--reps", str(reps), "--worker", str(bs), str(t)] + ([mode] if mode else [])
     env = {k: v for k, v in os.environ.items() if k != "PPFS_ECC_LIST_DIRECT"}
     if staged:
         env["PPFS_ECC_LIST_DIRECT"] = "0"
@@ -200,7 +287,15 @@ def run_worker(bs: int, t: int, blocks: int, reps: int, extents: bool, staged: b
 
 
 # the legs a staged worker repeats, by mode
-STAGED_LEGS = {False: ("list_identity", "list_permuted"), True: ("read_extents", "decode_list")}
+STAGED_LEGS = {"": ("list_identity", "list_permuted"),
+               "--extents": ("read_extents", "decode_list", "write_extents", "write_list"),
+               "--writes": ("encode_list_identity", "encode_list_permuted", "write_list_identity", "write_list_permuted")}
+WORKERS = {"": worker, "--extents": worker_extents, "--writes": worker_writes}
+WHAT = {"": "block-list decode (direct and staged) vs contiguous decode, one byte error per block (tools/bench_list.py)",
+        "--extents": "byte-extent read / write vs the list decode / list write of the same build, direct and staged, one byte "
+                     "error per block (tools/bench_list.py --extents)",
+        "--writes": "block-list encode / write (direct and staged) vs contiguous encode / write, old blocks of the writes with "
+                    "one byte error each (tools/bench_list.py --writes)"}
 
 
 def main() -> int:
@@ -209,40 +304,45 @@ def main() -> int:
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=None, help="write the records here as one JSON document")
     ap.add_argument("--extents", action="store_true", help="the byte-extent legs (RS(255,249)) instead of the list legs")
+    ap.add_argument("--writes", action="store_true", help="the list encode / write legs instead of the list decode legs")
     ap.add_argument("--worker", nargs=2, type=int, metavar=("BLOCK_SIZE", "T"), help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.extents and a.writes:
+        ap.error("--extents and --writes are two modes")
+    mode = "--extents" if a.extents else "--writes" if a.writes else ""
     sizes = [int(x) for x in (a.blocks or ("1048576" if a.extents else SIZES)).split(",")]
     if a.worker:
-        run = worker_extents if a.extents else worker
-        print(json.dumps(run(a.worker[0], a.worker[1], sizes[0], a.reps)))
+        print(json.dumps(WORKERS[mode](a.worker[0], a.worker[1], sizes[0], a.reps)))
         return 0
     records = []
     for name, bs, t in (CODECS[:1] if a.extents else CODECS):
         for blocks in sizes:
-            rec = run_worker(bs, t, blocks, a.reps, a.extents, False)
+            if a.writes and t == 16 and blocks != max(sizes):
+                continue  # the staged-only codec: its largest size alone
+            rec = run_worker(bs, t, blocks, a.reps, mode, False)
             if rec is None:
                 return 1
             rec = {"codec": name, **rec}
             if rec["list_kernel"] != "gather-stage-scatter":
-                st = run_worker(bs, t, blocks, a.reps, a.extents, True)
+                st = run_worker(bs, t, blocks, a.reps, mode, True)
                 if st is None:
                     return 1
                 assert st["list_kernel"] == "gather-stage-scatter"
-                for leg in STAGED_LEGS[a.extents]:
+                for leg in STAGED_LEGS[mode]:
                     rec["staged_" + leg + "_us"] = st[leg + "_us"]
                     rec["staged_" + leg + "_minmax_us"] = st[leg + "_minmax_us"]
                     rec["direct_over_staged_" + leg] = rec[leg + "_us"] / st[leg + "_us"]
-                if not a.extents:  # how far the two workers' runs of the unchanged contiguous decode lie apart
+                    if a.writes:  # the routing rule: the direct median below the staged runs' minimum
+                        rec["direct_below_staged_min_" + leg] = rec[leg + "_us"] < st[leg + "_minmax_us"][0]
+                if not mode:  # how far the two workers' runs of the unchanged contiguous decode lie apart
                     rec["staged_worker_contiguous_us"] = st["contiguous_us"]
+                if a.writes:
+                    rec["staged_worker_encode_us"], rec["staged_worker_write_us"] = st["encode_us"], st["write_us"]
             records.append(rec)
             print(json.dumps(rec))
     if a.out:
         with open(a.out, "w") as f:
-            what = ("byte-extent read / write vs the list decode / list write of the same build, one byte error per block "
-                    "(tools/bench_list.py --extents)" if a.extents else
-                    "block-list decode (direct and staged) vs contiguous decode, one byte error per block "
-                    "(tools/bench_list.py)")
-            json.dump({"what": what, "records": records}, f, indent=1)
+            json.dump({"what": WHAT[mode], "records": records}, f, indent=1)
             f.write("\n")
     return 0
 
