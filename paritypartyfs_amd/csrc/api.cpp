@@ -860,7 +860,7 @@ struct ScrubOps { // decode a block range of the image; copy spill bytes into th
 
 int scrub_run(const ppfs_ecc_ctx* c, size_t image_bytes, size_t nblocks, uint8_t* st, const ScrubOps& ops)
 {
-    const bool wb = c->p.ecc_type == PPFS_ECC_REED_SOLOMON || c->p.ecc_type == PPFS_ECC_HAMMING;
+    const bool wb = has_write_back(c);
     if (!(c->p.ecc_type == PPFS_ECC_REED_SOLOMON && c->rs_n < 255))
         return ops.decode(0, nblocks, wb ? 1 : 0, st, nullptr);
     const size_t n = c->raw, sb = 256 - n;
@@ -930,7 +930,7 @@ extern "C" int ppfs_ecc_scrub_device(ppfs_ecc_ctx* c, uint8_t* d_image, size_t i
     if (!c || (nblocks && !d_image) || image_bytes < nblocks * (size_t)c->raw)
         return fail(PPFS_ECC_EINVAL, "scrub: bad argument");
     hipStream_t s = (hipStream_t)stream;
-    const size_t n = c->raw, sb = 256 - std::min<size_t>(n, 255);
+    const size_t n = c->raw, sb = spill_bytes(c);
     const bool chain = c->p.ecc_type == PPFS_ECC_REED_SOLOMON && c->rs_n < 255;
     uint8_t* d_spill = nullptr;
     uint8_t* bounce = nullptr; // page-locked: the spill records and patches never DMA pageable memory
@@ -1198,7 +1198,7 @@ extern "C" int ppfs_ecc_group_decode_host(ppfs_ecc_group* g, uint8_t* raw, uint8
     size_t nblocks, int write_back, uint8_t* spill)
 {
     return group_run(g, nblocks, [&](ppfs_ecc_ctx* c, size_t b0, size_t nb) {
-        const size_t sp = 256 - std::min<size_t>(c->raw, 255);
+        const size_t sp = spill_bytes(c);
         return ppfs_ecc_decode_host(c, raw + b0 * c->raw, data ? data + b0 * c->data : nullptr,
             status ? status + b0 : nullptr, nb, write_back, spill ? spill + b0 * sp : nullptr);
     });

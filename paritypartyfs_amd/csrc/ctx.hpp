@@ -12,6 +12,7 @@
 #include <string>
 
 #include "../../include/ppfs_ecc.h"
+#include "host_plan.hpp"
 #include "server_box.hpp"
 
 #pragma GCC visibility push(hidden)
@@ -188,17 +189,13 @@ inline bool rs_wb_direct(const ppfs_ecc_ctx* c)
 int decode_device_to(ppfs_ecc_ctx* c, uint8_t* d_raw, uint8_t* d_data, uint8_t* d_status, size_t nblocks, int write_back,
     uint8_t* d_spill, void* stream, uint8_t* wb_dst);
 
-// The direct list decode (list_path.cpp; c->list_direct contexts): queues one rs_wg_list.hpp launch on s
-// for "entry i = image row index[i]" and the memset of the spill records, nothing else -- the caller
-// frames it (call_ordered / call_queued).  list_direct_args: do d_data / d_status meet its 16-byte rule?
-bool list_direct_args(const ppfs_ecc_ctx* c, const void* d_data, const void* d_status);
-int decode_list_direct(ppfs_ecc_ctx* c, uint8_t* d_image, size_t image_blocks, const uint32_t* d_index, size_t nblocks,
-    uint8_t* d_data, uint8_t* d_status, int write_back, uint8_t* d_spill, hipStream_t s);
-// The direct list encode (list_path.cpp; the same contexts): one rs_wg_list.hpp launch on s that stores
-// the codeword of payload i at image + index[i] * 255, framed by the caller as above; list_direct_args
-// is its gate too (d_data, and a write's d_status).
-int encode_list_direct(ppfs_ecc_ctx* c, const uint8_t* d_data, uint8_t* d_image, size_t image_blocks, const uint32_t* d_index,
-    size_t nblocks, hipStream_t s);
+// RS and Hamming: a decode with write-back may change the raw block
+inline bool has_write_back(const ppfs_ecc_ctx* c)
+{
+    return c->p.ecc_type == PPFS_ECC_REED_SOLOMON || c->p.ecc_type == PPFS_ECC_HAMMING;
+}
+// bytes of a decode's spill record per block (host_plan.hpp)
+inline size_t spill_bytes(const ppfs_ecc_ctx* c) { return plan::spill_bytes(c->raw); }
 
 // What every device entry point does around the work it queues on a caller's stream (api.cpp), for
 // the entry points outside api.cpp: call_ordered before the first launch (after the last call on the

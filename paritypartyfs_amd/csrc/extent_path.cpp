@@ -5,22 +5,18 @@
 // (lib/file_io/src/file_io.cpp:24-42, 50-88) issue for a file range that starts and ends mid-block, and
 // what the inode table, bitmap and directory code issue for their few bytes.
 //
-// Device forms: the block-list calls' pipeline with its kernels and codecs unchanged (list_path.cpp:
-// gather the listed rows into the context's staging, run the codec there, scatter the changed rows
-// back), in pieces of the same size, plus a second staging for the decoded payloads P of a piece and
-// the staged index of its entries.  An entry that is invalid is staged as index 0xFFFFFFFF, which the
-// gather, scatter and range-mark kernels already treat as out of range.
-//   read   index -> gather -> decode(rows -> P, status, write_back) -> scatter (status 1) -> pack P into
-//          the caller's buffer -> range marks
-//   write  index -> gather -> decode(rows -> P) -> overlay the caller's bytes onto P ->
-//          write(P, rows, status) -> scatter (status other than 5) -> range marks
-// A context that decodes lists directly (ctx.hpp list_direct; RS(255, 255-2t), 2t <= 8) reads a piece as
-//   read   index -> list decode(image, index -> P, status, write_back) -> pack P
-// one kernel for the gather, decode, scatter and range marks: the staged index 0xFFFFFFFF of an invalid
-// entry comes out of it as status 9 and a zero payload, and writes it as
-//   write  index -> list decode(image, index -> P, status; nothing written back) -> overlay ->
-//          list encode(P -> image, rs_wg_encode_list_kernel)
-// where an invalid entry's codeword is stored nowhere.  P, the piece size and list_ev stay.
+// Device forms: the block-list calls' frame and piece of listed rows (ListCall, PieceIO: list_call.hpp,
+// the table in list_path.cpp), in pieces of the same size, plus a second staging for the decoded
+// payloads P of a piece and the staged index of its entries.  An entry that is invalid is staged as
+// index 0xFFFFFFFF, which every way to reach the rows treats as out of range: status 9, a zero payload,
+// nothing stored.
+//   read   index, fetch, decode (rows -> P, status, write_back), pack P into the caller's buffer,
+//          status out, marks
+//   write  index, fetch, old payloads (rows -> P), overlay the caller's bytes onto P,
+//          write (P -> rows, status), status out, marks
+// The piece is direct when the context is (ctx.hpp list_direct): P and the status array the codec gets are
+// 16-byte aligned by construction.  Every extent call uses the shared staging, the context's own status
+// array (in the row staging) included, so every one is ordered by list_ev.
 // Host forms: the list is cut into runs without a repeated valid block, each run is gathered on the
 // CPU, goes through the contiguous host calls and is copied back.  The arithmetic of both is in
 // extent_plan.hpp.
@@ -53,53 +49,36 @@ int ensure_ext_stage(ppfs_ecc_ctx* c)
     return 0;
 }
 
-int extent_args(ppfs_ecc_ctx* c, const void* image, size_t image_blocks, const void* ext, size_t n, const void* buf,
-    size_t buf_bytes, const char* what)
-{
-    if (!c)
-        return fail(PPFS_ECC_EINVAL, what);
-    if (n && (!ext || ((uintptr_t)ext & 7u) || (image_blocks && !image) || (buf_bytes && !buf)))
-        return fail(PPFS_ECC_EINVAL, what);
-    return 0;
-}
-
-// What the pieces of one device call work with
-struct Pieces {
+// What a piece of a device extent call works with besides its rows
+struct ExtStage {
     ppfs_ecc_ctx* c;
-    size_t piece, blocks; // entries per piece; image blocks as the kernels see them
-    uint8_t *rows, *P, *own_status;
+    hipStream_t s;
+    uint8_t* P;
     uint32_t* idx;
-    size_t P_cap;
-    explicit Pieces(ppfs_ecc_ctx* ctx, size_t image_blocks)
-        : c(ctx)
-        , piece(piece_of(ctx))
-        , blocks(image_blocks_seen(image_blocks))
-        , rows(ctx->d_list)
-        , P(ctx->d_ext)
-        , own_status(ctx->d_list + ctx->list_status_off)
-        , idx((uint32_t*)(ctx->d_ext + ctx->ext_index_off))
-        , P_cap(ctx->ext_index_off)
+    ExtStage(ppfs_ecc_ctx* ctx, hipStream_t stream)
+        : c(ctx), s(stream), P(ctx->d_ext), idx((uint32_t*)(ctx->d_ext + ctx->ext_index_off))
     {
     }
-    // the codecs want a 16-byte aligned status array (RS, Hamming): the caller's where it is, else the
-    // context's own, copied out afterwards
+    int index(const ppfs_ecc_extent* ex, uint32_t nb, size_t blocks, size_t buf_bytes) const
+    {
+        return check_hip(ppfs_extent_index_launch(ex, nb, blocks, c->data, buf_bytes, idx, s), "extent index");
+    }
+    // to_stage 0: pack P's bytes into buf, selected by st; 1: overlay buf's bytes, which the kernel only reads, onto P
+    int copy(int to_stage, const ppfs_ecc_extent* ex, const uint8_t* st, uint32_t nb, const uint8_t* buf, size_t buf_bytes) const
+    {
+        return check_hip(ppfs_extent_copy_launch(to_stage, ex, idx, st, nb, c->data, P, c->ext_index_off,
+                             const_cast<uint8_t*>(buf), buf_bytes, s),
+            to_stage ? "extent overlay" : "extent pack");
+    }
+    // the codecs want a 16-byte aligned status array (RS, Hamming), and the pack and the scatter select
+    // by status: the caller's where it is aligned, else the context's own, copied out afterwards
     uint8_t* status_for(uint8_t* d_status, size_t off) const
     {
-        return d_status && (((uintptr_t)d_status & 15u) == 0) ? d_status + off : own_status;
+        return d_status && (((uintptr_t)d_status & 15u) == 0) ? d_status + off : c->d_list + c->list_status_off;
     }
-    // marks: the range marks are still to be made (the direct list decode made them itself)
-    int status_out(uint8_t* st, uint8_t* d_status, size_t off, uint32_t nb, hipStream_t s, bool marks = true) const
+    int status_out(const uint8_t* st, uint8_t* out, uint32_t nb) const // out: the caller's piece, or null
     {
-        if (!d_status)
-            return 0;
-        if (st != d_status + off) {
-            int r = check_hip(dma_async(d_status + off, st, nb, hipMemcpyDeviceToDevice, s), "extent status copy");
-            if (r)
-                return r;
-        }
-        if (!marks)
-            return 0;
-        return check_hip(ppfs_list_oob_launch(idx, nb, blocks, d_status + off, nullptr, 0, s), "extent range marks");
+        return out && st != out ? check_hip(dma_async(out, st, nb, hipMemcpyDeviceToDevice, s), "extent status copy") : 0;
     }
 };
 
@@ -108,44 +87,25 @@ struct Pieces {
 extern "C" int ppfs_ecc_read_extents_device(ppfs_ecc_ctx* c, uint8_t* d_image, size_t image_blocks,
     const ppfs_ecc_extent* d_ext, size_t n, uint8_t* d_out, size_t out_bytes, uint8_t* d_status, int write_back, void* stream)
 {
-    int r = extent_args(c, d_image, image_blocks, d_ext, n, d_out, out_bytes, "read extents: null or misaligned argument");
+    int r = entry_args(c, d_image, image_blocks, d_ext, 8, n, d_out, out_bytes != 0, "read extents: null or misaligned argument");
     if (r || n == 0)
         return r;
-    if (stream_capturing((hipStream_t)stream))
-        return fail(PPFS_ECC_ENOTSUP, "extent calls cannot be captured into a graph (shared staging)");
-    ListCall call { c, (hipStream_t)stream, stream, n };
+    ListCall call { c, stream, n, "extent", true };
     if ((r = call.begin()))
         return r;
     if (!(r = ensure_ext_stage(c))) {
-        const Pieces p(c, image_blocks);
+        const ExtStage x(c, call.s());
+        PieceIO io { c, d_image, image_blocks_seen(image_blocks), stream, c->list_direct };
         const bool wb = write_back && has_write_back(c);
-        const uint32_t raw = c->raw, ds = c->data;
-        for (size_t off = 0; off < n && !r; off += p.piece) {
-            const uint32_t nb = (uint32_t)std::min(p.piece, n - off);
+        for (size_t off = 0, piece = call.piece(); off < n && !r; off += piece) {
+            const uint32_t nb = (uint32_t)std::min(piece, n - off);
             const ppfs_ecc_extent* ex = d_ext + off;
-            uint8_t* st = p.status_for(d_status, off); // the pack selects by status: always one
-            r = check_hip(ppfs_extent_index_launch(ex, nb, p.blocks, ds, out_bytes, p.idx, call.s), "extent index");
-            if (!r && c->list_direct) { // P and st are 16-byte aligned (ext_stage_layout, status_for)
-                r = decode_list_direct(c, d_image, p.blocks, p.idx, nb, p.P, st, wb ? 1 : 0, nullptr, call.s);
-                if (!r)
-                    r = check_hip(ppfs_extent_copy_launch(0, ex, p.idx, st, nb, ds, p.P, p.P_cap, d_out, out_bytes, call.s),
-                        "extent pack");
-                if (!r)
-                    r = p.status_out(st, d_status, off, nb, call.s, false);
-                continue;
-            }
-            if (!r)
-                r = check_hip(ppfs_gather_blocks_launch(d_image, p.blocks, p.idx, nb, raw, p.rows, call.s), "extent gather");
-            if (!r)
-                r = ppfs_ecc_decode_device(c, p.rows, ds ? p.P : nullptr, st, nb, wb ? 1 : 0, nullptr, stream);
-            if (!r && wb)
-                r = check_hip(ppfs_scatter_blocks_launch(p.rows, d_image, p.blocks, p.idx, st, 1, nb, raw, call.s),
-                    "extent scatter");
-            if (!r)
-                r = check_hip(ppfs_extent_copy_launch(0, ex, p.idx, st, nb, ds, p.P, p.P_cap, d_out, out_bytes, call.s),
-                    "extent pack");
-            if (!r)
-                r = p.status_out(st, d_status, off, nb, call.s);
+            uint8_t* st = x.status_for(d_status, off);
+            uint8_t* out_st = d_status ? d_status + off : nullptr;
+            (void)((r = x.index(ex, nb, io.blocks, out_bytes)) || (r = io.fetch(x.idx, nb))
+                || (r = io.decode(x.idx, nb, c->data ? x.P : nullptr, st, wb, nullptr))
+                || (r = x.copy(0, ex, st, nb, d_out, out_bytes)) || (r = x.status_out(st, out_st, nb))
+                || (r = io.marks(x.idx, nb, out_st, nullptr)));
         }
     }
     return call.end(r, "read extents (async)");
@@ -154,53 +114,24 @@ extern "C" int ppfs_ecc_read_extents_device(ppfs_ecc_ctx* c, uint8_t* d_image, s
 extern "C" int ppfs_ecc_write_extents_device(ppfs_ecc_ctx* c, const uint8_t* d_in, size_t in_bytes, uint8_t* d_image,
     size_t image_blocks, const ppfs_ecc_extent* d_ext, size_t n, uint8_t* d_status, void* stream)
 {
-    int r = extent_args(c, d_image, image_blocks, d_ext, n, d_in, in_bytes, "write extents: null or misaligned argument");
+    int r = entry_args(c, d_image, image_blocks, d_ext, 8, n, d_in, in_bytes != 0, "write extents: null or misaligned argument");
     if (r || n == 0)
         return r;
-    if (stream_capturing((hipStream_t)stream))
-        return fail(PPFS_ECC_ENOTSUP, "extent calls cannot be captured into a graph (shared staging)");
-    ListCall call { c, (hipStream_t)stream, stream, n };
+    ListCall call { c, stream, n, "extent", true };
     if ((r = call.begin()))
         return r;
     if (!(r = ensure_ext_stage(c))) {
-        const Pieces p(c, image_blocks);
-        const uint32_t raw = c->raw, ds = c->data;
-        for (size_t off = 0; off < n && !r; off += p.piece) {
-            const uint32_t nb = (uint32_t)std::min(p.piece, n - off);
+        const ExtStage x(c, call.s());
+        PieceIO io { c, d_image, image_blocks_seen(image_blocks), stream, c->list_direct };
+        for (size_t off = 0, piece = call.piece(); off < n && !r; off += piece) {
+            const uint32_t nb = (uint32_t)std::min(piece, n - off);
             const ppfs_ecc_extent* ex = d_ext + off;
-            uint8_t* st = p.status_for(d_status, off); // the scatter selects by status: always one
-            r = check_hip(ppfs_extent_index_launch(ex, nb, p.blocks, ds, in_bytes, p.idx, call.s), "extent index");
-            if (!r && c->list_direct) { // P and st are 16-byte aligned (ext_stage_layout, status_for)
-                // the old payloads and statuses (9 and zeros for an invalid entry) without touching the
-                // image, the caller's bytes over them, the new codewords stored in place
-                r = decode_list_direct(c, d_image, p.blocks, p.idx, nb, p.P, st, 0, nullptr, call.s);
-                if (!r)
-                    r = check_hip(ppfs_extent_copy_launch(1, ex, p.idx, nullptr, nb, ds, p.P, p.P_cap,
-                                      const_cast<uint8_t*>(d_in), in_bytes, call.s),
-                        "extent overlay");
-                if (!r)
-                    r = encode_list_direct(c, p.P, d_image, p.blocks, p.idx, nb, call.s);
-                if (!r)
-                    r = p.status_out(st, d_status, off, nb, call.s, false);
-                continue;
-            }
-            if (!r)
-                r = check_hip(ppfs_gather_blocks_launch(d_image, p.blocks, p.idx, nb, raw, p.rows, call.s), "extent gather");
-            // the old payloads: where the old block fails its check (status 5 below) the row is not
-            // scattered and what P holds for it does not matter
-            if (!r && ds)
-                r = ppfs_ecc_decode_device(c, p.rows, p.P, nullptr, nb, 0, nullptr, stream);
-            if (!r) // the kernel only reads the caller's bytes
-                r = check_hip(ppfs_extent_copy_launch(1, ex, p.idx, nullptr, nb, ds, p.P, p.P_cap, const_cast<uint8_t*>(d_in),
-                                  in_bytes, call.s),
-                    "extent overlay");
-            if (!r)
-                r = ppfs_ecc_write_device(c, ds ? p.P : nullptr, p.rows, st, nb, stream);
-            if (!r)
-                r = check_hip(ppfs_scatter_blocks_launch(p.rows, d_image, p.blocks, p.idx, st, 2, nb, raw, call.s),
-                    "extent scatter");
-            if (!r)
-                r = p.status_out(st, d_status, off, nb, call.s);
+            uint8_t* st = x.status_for(d_status, off);
+            uint8_t* out_st = d_status ? d_status + off : nullptr;
+            (void)((r = x.index(ex, nb, io.blocks, in_bytes)) || (r = io.fetch(x.idx, nb))
+                || (r = io.old_payloads(x.idx, nb, x.P, st)) || (r = x.copy(1, ex, nullptr, nb, d_in, in_bytes))
+                || (r = io.write(x.idx, nb, c->data ? x.P : nullptr, st)) || (r = x.status_out(st, out_st, nb))
+                || (r = io.marks(x.idx, nb, out_st, nullptr)));
         }
     }
     return call.end(r, "write extents (async)");
@@ -226,7 +157,7 @@ struct HostExtents {
 
 int host_extents_run(ppfs_ecc_ctx* c, const HostExtents& h)
 {
-    int r = extent_args(c, h.image, h.image_blocks, h.ext, h.n, h.write ? h.in : h.out, h.buf_bytes,
+    int r = entry_args(c, h.image, h.image_blocks, h.ext, 8, h.n, h.write ? h.in : h.out, h.buf_bytes != 0,
         "extents (host): null or misaligned argument");
     if (r || h.n == 0)
         return r;

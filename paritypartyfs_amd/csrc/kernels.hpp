@@ -58,8 +58,10 @@ hipError_t ppfs_patch_list_launch(const uint8_t* cur, const uint8_t* orig, const
     uint32_t S, uint32_t* patch, uint8_t* image, hipStream_t s);
 hipError_t ppfs_inject_launch(uint8_t* raw, uint64_t stride, uint64_t nblocks, const uint8_t* pos, const uint8_t* val,
     int mode, hipStream_t s);
-// block lists (list_path.cpp): stage is 16-byte aligned with a capacity of nb * raw rounded up to 16;
-// scatter mode 0 = every in-range entry, 1 = status 1, 2 = status other than 5
+// block lists, the staged side of a piece of listed rows (list_path.cpp PieceIO: fetch = gather, the
+// scatter after decode / encode / write, marks = list_oob; the direct side is the two ppfs_rs_list_*
+// calls above): stage is 16-byte aligned with a capacity of nb * raw rounded up to 16;
+// scatter mode 0 = every in-range entry (encode), 1 = status 1 (decode), 2 = status other than 5 (write)
 hipError_t ppfs_gather_blocks_launch(const uint8_t* img, uint64_t image_blocks, const uint32_t* index, uint32_t nb,
     uint32_t raw, uint8_t* stage, hipStream_t s);
 hipError_t ppfs_scatter_blocks_launch(const uint8_t* stage, uint8_t* img, uint64_t image_blocks, const uint32_t* index,

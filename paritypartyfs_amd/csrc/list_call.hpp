@@ -1,6 +1,6 @@
 // list_call.hpp -- what the block-list calls (list_path.cpp) and the byte-extent calls
-// (extent_path.cpp) share: the frame of one device call over the context's row staging, the piece
-// size, and which codecs write a corrected block back.  Defined in list_path.cpp.
+// (extent_path.cpp) share: the argument check, the frame of one device call, and the piece of listed
+// rows that a call decodes, encodes or writes.  Defined in list_path.cpp.
 #pragma once
 
 #include "ctx.hpp"
@@ -8,19 +8,60 @@
 #pragma GCC visibility push(hidden)
 namespace ppfs {
 
-bool has_write_back(const ppfs_ecc_ctx* c); // RS and Hamming: a decode may change the raw block
-size_t piece_of(ppfs_ecc_ctx* c);           // blocks per piece of a device list / extent call
+size_t piece_of(ppfs_ecc_ctx* c); // blocks per piece of a staged device list / extent call
 
-// begin(): makes the row staging at the context's first call, orders the call after the last call on
-// the stream and after the previous user of the staging (list_ev); end(): records list_ev again, also
-// after a failure, and does what every device entry point does after its last launch.
+// Null context; with n entries: a null or misaligned (align: a power of two) entry array, a null image
+// of image_blocks blocks, a null buffer that is needed.  Fails as PPFS_ECC_EINVAL under the caller's text.
+int entry_args(const ppfs_ecc_ctx* c, const void* image, size_t image_blocks, const void* entries, unsigned align, size_t n,
+    const void* buf, bool buf_needed, const char* what);
+
+// The frame of one device call.  begin(): refuses a capturing stream (kind: "list" / "extent", the
+// refusal's wording), orders the call after the last call on the stream and, when the call uses the
+// context's shared staging, makes the row staging at the context's first call and waits for its
+// previous user (list_ev).  end(): records list_ev again, also after a failure, and does what every
+// device entry point does after its last launch.  A call without staging (a direct list call) is one
+// piece and queues nothing but its codec kernels in between.
 struct ListCall {
     ppfs_ecc_ctx* c;
-    hipStream_t s;
     void* stream;
     size_t nblocks;
+    const char* kind;
+    bool staging;
+    hipStream_t s() const { return (hipStream_t)stream; }
+    size_t piece() const { return staging ? piece_of(c) : nblocks; }
     int begin();
     int end(int r, const char* what);
+};
+
+// One piece of listed rows: entry i = image row ix[i], nb entries, every operation queued on the
+// caller's stream.  The one place where the two ways to reach the rows part (the table in list_path.cpp):
+// staged, through a gathered copy in the context's row staging, or direct, by codec kernels that fetch
+// and store the listed rows themselves.  direct is the entry point's decision; data and st are the
+// piece's, 16-byte aligned when direct.
+struct PieceIO {
+    ppfs_ecc_ctx* c;
+    uint8_t* image;
+    size_t blocks; // image blocks as the kernels see them
+    void* stream;
+    bool direct;
+    bool old_status_known = false; // old_payloads() left the old blocks' statuses in st: write() need not ask again
+
+    int fetch(const uint32_t* ix, size_t nb);
+    // payloads into data, statuses into st (either may be null), corrected rows back into the image when
+    // wb, spill records (null: none)
+    int decode(const uint32_t* ix, size_t nb, uint8_t* data, uint8_t* st, bool wb, uint8_t* spill);
+    // the old payloads into P before an overlay; the image stays as it is
+    int old_payloads(const uint32_t* ix, size_t nb, uint8_t* P, uint8_t* st);
+    int encode(const uint32_t* ix, size_t nb, const uint8_t* data);
+    // the old blocks' statuses into st (null: not wanted), then the new codewords
+    int write(const uint32_t* ix, size_t nb, const uint8_t* data, uint8_t* st);
+    // status 9 and a zero payload for the entries out of range, in the caller's arrays (null: none)
+    int marks(const uint32_t* ix, size_t nb, uint8_t* st, uint8_t* data);
+
+private:
+    hipStream_t s() const { return (hipStream_t)stream; }
+    uint8_t* rows() const { return c->d_list; }
+    uint8_t* own_status() const { return c->d_list + c->list_status_off; }
 };
 
 } // namespace ppfs

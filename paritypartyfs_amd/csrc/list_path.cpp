@@ -3,24 +3,32 @@
 // FileIO's BlockIndexIterator loop (lib/file_io/src/file_io.cpp:27-35, 53-69) needs for a file
 // whose blocks lie wherever the bitmap allocator put them.
 //
-// Device forms: the listed rows are gathered into a dense, context-owned staging copy
-// (vote.hip gather_blocks_kernel), the unchanged codec kernels run on that copy through the
-// contiguous entry points, and the rows that changed are scattered back (scatter_blocks_kernel).
-// Lists longer than one piece (list_plan.hpp piece_blocks) go piece by piece on the caller's stream.
-// RS(255, 255-2t), 2t <= 8 decodes a list in one kernel instead (rs_wg_list.hpp: the rows are fetched
-// from the image by the codec kernel's loader and corrected in place): no staging, no pieces, no
-// list_ev, framed like a contiguous device call.  PPFS_ECC_LIST_DIRECT=0 at ppfs_ecc_create keeps such
-// a context on the staged path.  Such a context also encodes and writes a list directly: the list encode
-// (rs_wg_list.hpp rs_wg_encode_list_kernel) stores codeword i at image + index[i] * 255 itself, and an RS
-// write needs nothing of the old block but its status (rs_block_device.cpp:61-93), which the list
-// decode gives without touching the image -- two kernels on the caller's stream in place of gather,
-// decode, encode, scatter and range marks.
+// Device forms: a frame (ListCall) around one straight sequence of operations per piece of listed rows
+// (PieceIO; both in list_call.hpp, both used by the byte-extent calls of extent_path.cpp too):
+//   decode: fetch, decode, marks    encode: fetch if the encode keeps old bits, encode    write: fetch, write, marks
+// PieceIO is the one place where the two ways to reach the rows part:
+//   operation     staged (every codec)                                direct (RS(255, 255-2t), 2t <= 8)
+//   fetch         gather into the row staging (vote.hip)              nothing
+//   decode        contiguous decode of the staging; scatter of the    one list decode (rs_wg_list.hpp), and the
+//                 corrected rows (status 1) when writing back         spill memset
+//   old payloads  contiguous decode into P without status (not when   list decode into P and the status array,
+//                 the data size is 0)                                 nothing written back
+//   encode        contiguous encode into the staging; scatter of      one list encode: codeword i stored at
+//                 every row                                           image + index[i] * 255
+//   write         contiguous write of the staging; scatter of the     status-only list decode (not when the statuses
+//                 rows with a status other than 5                     are known or unwanted), list encode
+//   marks         list_oob_kernel: status 9, zero payload             nothing: the kernels made them
+// Staged lists longer than one piece (list_plan.hpp piece_blocks) go piece by piece through the context's
+// shared staging, which list_ev orders between calls.  A list call is direct when the context is
+// (PPFS_ECC_LIST_DIRECT=0 at ppfs_ecc_create keeps it staged) and the caller's arrays meet the kernels'
+// 16-byte rule; it is one piece without staging or list_ev, framed like a contiguous device call.
 // Host forms: the list is cut into runs without a repeated index, each run is gathered on the CPU
 // and handed to the contiguous host call, and the rows that changed are copied back.
 // The arithmetic of both is in list_plan.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "ctx.hpp"
@@ -43,16 +51,13 @@ bool encode_keeps_old_bits(const ppfs_ecc_ctx* c)
         || (c->p.ecc_type == PPFS_ECC_CRC && c->crc_n % 8 != 0);
 }
 
-} // namespace
-
-bool ppfs::has_write_back(const ppfs_ecc_ctx* c)
+// The gate of a direct list call: the 16-byte rule of the contiguous RS decode and encode
+// (ppfs_ecc_decode_device, ppfs_ecc_encode_device); a call that breaks it takes the staged path, which
+// refuses it as before
+bool list_direct_args(const ppfs_ecc_ctx* c, const void* d_data, const void* d_status)
 {
-    return c->p.ecc_type == PPFS_ECC_REED_SOLOMON || c->p.ecc_type == PPFS_ECC_HAMMING;
+    return c->list_direct && (((uintptr_t)d_data | (uintptr_t)d_status) & 15u) == 0;
 }
-
-size_t ppfs::piece_of(ppfs_ecc_ctx* c) { return piece_blocks(ppfs_ecc_host_chunk_blocks(c), c->raw); }
-
-namespace {
 
 // The staging of the list calls, made once per context (the piece size does not change)
 int ensure_stage(ppfs_ecc_ctx* c)
@@ -70,111 +75,142 @@ int ensure_stage(ppfs_ecc_ctx* c)
 
 } // namespace
 
-// One device list call: the common frame around its pieces (list_call.hpp).  The staging is shared by
-// every stream of the context, so the call first waits for the event recorded after the previous list
-// call's last kernel and records it again after its own.
+size_t ppfs::piece_of(ppfs_ecc_ctx* c) { return piece_blocks(ppfs_ecc_host_chunk_blocks(c), c->raw); }
+
+int ppfs::entry_args(const ppfs_ecc_ctx* c, const void* image, size_t image_blocks, const void* entries, unsigned align,
+    size_t n, const void* buf, bool buf_needed, const char* what)
+{
+    if (!c || (n && (!entries || ((uintptr_t)entries & (align - 1)) || (image_blocks && !image) || (buf_needed && !buf))))
+        return fail(PPFS_ECC_EINVAL, what);
+    return 0;
+}
+
+// The frame of one device call (list_call.hpp).  The staging is shared by every stream of the context,
+// so a call that uses it first waits for the event recorded after the previous such call's last kernel
+// and records it again after its own.
 int ppfs::ListCall::begin()
 {
-    int r = ensure_stage(c);
-    if (r)
-        return r;
+    if (stream_capturing(s()))
+        return fail(PPFS_ECC_ENOTSUP, (std::string(kind) + " calls cannot be captured into a graph (shared staging)").c_str());
+    if (staging) {
+        int r = ensure_stage(c);
+        if (r)
+            return r;
+    }
     (void)call_ordered(c, nblocks, stream);
-    if (c->list_ev_rec)
-        HIP_TRY(hipStreamWaitEvent(s, c->list_ev, 0), "list staging wait");
+    if (staging && c->list_ev_rec)
+        HIP_TRY(hipStreamWaitEvent(s(), c->list_ev, 0), "list staging wait");
     return 0;
 }
 
 int ppfs::ListCall::end(int r, const char* what)
 {
+    if (!staging)
+        return call_queued(c, r, nblocks, stream, what);
     // also after a failure: pieces queued before it may still use the staging
-    if (hipEventRecord(c->list_ev, s) == hipSuccess) {
+    if (hipEventRecord(c->list_ev, s()) == hipSuccess) {
         c->list_ev_rec = true;
     } else {
         (void)hipGetLastError();
-        (void)hipStreamSynchronize(s); // nothing to order the next call by: drain instead
+        (void)hipStreamSynchronize(s()); // nothing to order the next call by: drain instead
         c->list_ev_rec = false;
     }
     return call_queued(c, r, nblocks, stream, what);
 }
 
 // ---------------------------------------------------------------------------------------
-// The direct list decode (ctx.hpp)
+// One piece of listed rows (list_call.hpp): the table above
 // ---------------------------------------------------------------------------------------
-bool ppfs::list_direct_args(const ppfs_ecc_ctx* c, const void* d_data, const void* d_status)
+int ppfs::PieceIO::fetch(const uint32_t* ix, size_t nb)
 {
-    // the rule of the contiguous RS decode (ppfs_ecc_decode_device); a call that breaks it takes the
-    // staged path, which refuses it as before
-    return c->list_direct && (((uintptr_t)d_data | (uintptr_t)d_status) & 15u) == 0;
+    if (direct)
+        return 0;
+    return check_hip(ppfs_gather_blocks_launch(image, blocks, ix, (uint32_t)nb, c->raw, rows(), s()), "list gather");
 }
 
-int ppfs::decode_list_direct(ppfs_ecc_ctx* c, uint8_t* d_image, size_t image_blocks, const uint32_t* d_index,
-    size_t nblocks, uint8_t* d_data, uint8_t* d_status, int write_back, uint8_t* d_spill, hipStream_t s)
+int ppfs::PieceIO::decode(const uint32_t* ix, size_t nb, uint8_t* data, uint8_t* st, bool wb, uint8_t* spill)
 {
-    if (d_spill) // n = 255: one count byte per entry, always zero (a write-back never passes the block's end)
-        HIP_TRY(hipMemsetAsync(d_spill, 0, nblocks, s), "list spill");
-    return check_hip(ppfs_rs_list_decode(c->rs_t2, d_image, image_blocks, d_index, d_data, d_status, nblocks, c->d_tables,
-                         write_back ? 1 : 0, s),
-        "rs list decode");
+    if (direct) {
+        if (spill) // n = 255: one count byte per entry, always zero (a write-back never passes the block's end)
+            HIP_TRY(hipMemsetAsync(spill, 0, nb * spill_bytes(c), s()), "list spill");
+        return check_hip(ppfs_rs_list_decode(c->rs_t2, image, blocks, ix, data, st, nb, c->d_tables, wb ? 1 : 0, s()),
+            "rs list decode");
+    }
+    if (!st && wb) // the scatter selects by status: the context's own array when the caller wants none
+        st = own_status();
+    int r = ppfs_ecc_decode_device(c, rows(), data, st, nb, wb ? 1 : 0, spill, stream);
+    if (!r && wb)
+        r = check_hip(ppfs_scatter_blocks_launch(rows(), image, blocks, ix, st, 1, (uint32_t)nb, c->raw, s()), "list scatter");
+    return r;
 }
 
-// The direct list encode.  Its gate is list_direct_args too: d_data by the rule of the contiguous RS
-// encode (ppfs_ecc_encode_device), a write's d_status by the decode's.
-int ppfs::encode_list_direct(ppfs_ecc_ctx* c, const uint8_t* d_data, uint8_t* d_image, size_t image_blocks,
-    const uint32_t* d_index, size_t nblocks, hipStream_t s)
+int ppfs::PieceIO::old_payloads(const uint32_t* ix, size_t nb, uint8_t* P, uint8_t* st)
 {
-    return check_hip(ppfs_rs_list_encode(c->rs_t2, d_data, d_image, image_blocks, d_index, nblocks, c->d_tables, s),
-        "rs list encode");
+    if (direct) { // the statuses come with the payloads (9 and zeros for an entry out of range)
+        old_status_known = true;
+        return decode(ix, nb, P, st, false, nullptr);
+    }
+    // where the old block fails its check (status 5 in write()) the row is not scattered and what P
+    // holds for it does not matter
+    return c->data ? ppfs_ecc_decode_device(c, rows(), P, nullptr, nb, 0, nullptr, stream) : 0;
 }
 
-namespace {
-
-int list_args(ppfs_ecc_ctx* c, const void* d_image, size_t image_blocks, const void* d_index, size_t nblocks,
-    const void* d_data, bool data_required, void* stream, const char* what)
+int ppfs::PieceIO::encode(const uint32_t* ix, size_t nb, const uint8_t* data)
 {
-    if (!c)
-        return fail(PPFS_ECC_EINVAL, what);
-    if (nblocks && (!d_index || (image_blocks && !d_image) || (data_required && c->data && !d_data)))
-        return fail(PPFS_ECC_EINVAL, what);
-    if (nblocks && stream_capturing((hipStream_t)stream))
-        return fail(PPFS_ECC_ENOTSUP, "list calls cannot be captured into a graph (shared staging)");
-    return 0;
+    if (direct)
+        return check_hip(ppfs_rs_list_encode(c->rs_t2, data, image, blocks, ix, nb, c->d_tables, s()), "rs list encode");
+    int r = ppfs_ecc_encode_device(c, data, rows(), nb, stream);
+    if (!r)
+        r = check_hip(ppfs_scatter_blocks_launch(rows(), image, blocks, ix, nullptr, 0, (uint32_t)nb, c->raw, s()), "list scatter");
+    return r;
 }
 
-} // namespace
+int ppfs::PieceIO::write(const uint32_t* ix, size_t nb, const uint8_t* data, uint8_t* st)
+{
+    if (direct) {
+        // the old blocks' statuses (0 / 1, 9 for an entry out of range) by the list decode, which changes
+        // nothing; then the new codewords, whatever the status was: RS needs nothing else of the old block
+        // (rs_block_device.cpp:61-93)
+        int r = st && !old_status_known ? decode(ix, nb, nullptr, st, false, nullptr) : 0;
+        old_status_known = false;
+        return r ? r : encode(ix, nb, data);
+    }
+    if (!st) // the scatter selects by status
+        st = own_status();
+    int r = ppfs_ecc_write_device(c, data, rows(), st, nb, stream);
+    if (!r)
+        r = check_hip(ppfs_scatter_blocks_launch(rows(), image, blocks, ix, st, 2, (uint32_t)nb, c->raw, s()), "list scatter");
+    return r;
+}
 
+int ppfs::PieceIO::marks(const uint32_t* ix, size_t nb, uint8_t* st, uint8_t* data)
+{
+    if (direct)
+        return 0;
+    return check_hip(ppfs_list_oob_launch(ix, (uint32_t)nb, blocks, st, data, data ? c->data : 0, s()), "list range marks");
+}
+
+// ---------------------------------------------------------------------------------------
+// Device forms
+// ---------------------------------------------------------------------------------------
 extern "C" int ppfs_ecc_decode_list_device(ppfs_ecc_ctx* c, uint8_t* d_image, size_t image_blocks, const uint32_t* d_index,
     size_t nblocks, uint8_t* d_data, uint8_t* d_status, int write_back, uint8_t* d_spill, void* stream)
 {
-    int r = list_args(c, d_image, image_blocks, d_index, nblocks, d_data, false, stream, "decode list: null argument");
+    int r = entry_args(c, d_image, image_blocks, d_index, 1, nblocks, d_data, false, "decode list: null argument");
     if (r || nblocks == 0)
         return r;
-    if (list_direct_args(c, d_data, d_status)) {
-        (void)call_ordered(c, nblocks, stream);
-        r = decode_list_direct(c, d_image, image_blocks, d_index, nblocks, d_data, d_status, write_back, d_spill,
-            (hipStream_t)stream);
-        return call_queued(c, r, nblocks, stream, "decode list (async)");
-    }
-    ListCall call { c, (hipStream_t)stream, stream, nblocks };
+    const bool direct = list_direct_args(c, d_data, d_status), wb = write_back && has_write_back(c);
+    ListCall call { c, stream, nblocks, "list", !direct };
     if ((r = call.begin()))
         return r;
-    const size_t piece = piece_of(c), sb = 256 - std::min<size_t>(c->raw, 255);
-    const bool wb = write_back && has_write_back(c);
-    uint8_t* rows = c->d_list;
-    for (size_t off = 0; off < nblocks && !r; off += piece) {
-        const uint32_t nb = (uint32_t)std::min(piece, nblocks - off);
+    PieceIO io { c, d_image, image_blocks, stream, direct };
+    for (size_t off = 0, piece = call.piece(); off < nblocks && !r; off += piece) {
+        const size_t nb = std::min(piece, nblocks - off);
         const uint32_t* ix = d_index + off;
-        // the scatter selects by status: the context's own array when the caller wants none
-        uint8_t* st = d_status ? d_status + off : (wb ? c->d_list + c->list_status_off : nullptr);
+        uint8_t* st = d_status ? d_status + off : nullptr;
         uint8_t* dd = d_data ? d_data + off * c->data : nullptr;
-        r = check_hip(ppfs_gather_blocks_launch(d_image, image_blocks, ix, nb, c->raw, rows, call.s), "list gather");
-        if (!r)
-            r = ppfs_ecc_decode_device(c, rows, dd, st, nb, wb ? 1 : 0, d_spill ? d_spill + off * sb : nullptr, stream);
-        if (!r && wb)
-            r = check_hip(ppfs_scatter_blocks_launch(rows, d_image, image_blocks, ix, st, 1, nb, c->raw, call.s),
-                "list scatter");
-        if (!r)
-            r = check_hip(
-                ppfs_list_oob_launch(ix, nb, image_blocks, d_status ? st : nullptr, dd, c->data, call.s), "list range marks");
+        uint8_t* sp = d_spill ? d_spill + off * spill_bytes(c) : nullptr;
+        (void)((r = io.fetch(ix, nb)) || (r = io.decode(ix, nb, dd, st, wb, sp)) || (r = io.marks(ix, nb, st, dd)));
     }
     return call.end(r, "decode list (async)");
 }
@@ -182,29 +218,20 @@ extern "C" int ppfs_ecc_decode_list_device(ppfs_ecc_ctx* c, uint8_t* d_image, si
 extern "C" int ppfs_ecc_encode_list_device(ppfs_ecc_ctx* c, const uint8_t* d_data, uint8_t* d_image, size_t image_blocks,
     const uint32_t* d_index, size_t nblocks, void* stream)
 {
-    int r = list_args(c, d_image, image_blocks, d_index, nblocks, d_data, true, stream, "encode list: null argument");
+    int r = entry_args(c, d_image, image_blocks, d_index, 1, nblocks, d_data, c && c->data, "encode list: null argument");
     if (r || nblocks == 0)
         return r;
-    if (list_direct_args(c, d_data, nullptr)) {
-        (void)call_ordered(c, nblocks, stream);
-        r = encode_list_direct(c, d_data, d_image, image_blocks, d_index, nblocks, (hipStream_t)stream);
-        return call_queued(c, r, nblocks, stream, "encode list (async)");
-    }
-    ListCall call { c, (hipStream_t)stream, stream, nblocks };
+    const bool direct = list_direct_args(c, d_data, nullptr);
+    ListCall call { c, stream, nblocks, "list", !direct };
     if ((r = call.begin()))
         return r;
-    const size_t piece = piece_of(c);
-    uint8_t* rows = c->d_list;
-    for (size_t off = 0; off < nblocks && !r; off += piece) {
-        const uint32_t nb = (uint32_t)std::min(piece, nblocks - off);
+    PieceIO io { c, d_image, image_blocks, stream, direct };
+    for (size_t off = 0, piece = call.piece(); off < nblocks && !r; off += piece) {
+        const size_t nb = std::min(piece, nblocks - off);
         const uint32_t* ix = d_index + off;
-        if (encode_keeps_old_bits(c))
-            r = check_hip(ppfs_gather_blocks_launch(d_image, image_blocks, ix, nb, c->raw, rows, call.s), "list gather");
-        if (!r)
-            r = ppfs_ecc_encode_device(c, d_data ? d_data + off * c->data : nullptr, rows, nb, stream);
-        if (!r)
-            r = check_hip(ppfs_scatter_blocks_launch(rows, d_image, image_blocks, ix, nullptr, 0, nb, c->raw, call.s),
-                "list scatter");
+        const uint8_t* dd = d_data ? d_data + off * c->data : nullptr;
+        if (!(r = encode_keeps_old_bits(c) ? io.fetch(ix, nb) : 0))
+            r = io.encode(ix, nb, dd);
     }
     return call.end(r, "encode list (async)");
 }
@@ -212,38 +239,20 @@ extern "C" int ppfs_ecc_encode_list_device(ppfs_ecc_ctx* c, const uint8_t* d_dat
 extern "C" int ppfs_ecc_write_list_device(ppfs_ecc_ctx* c, const uint8_t* d_data, uint8_t* d_image, size_t image_blocks,
     const uint32_t* d_index, uint8_t* d_status, size_t nblocks, void* stream)
 {
-    int r = list_args(c, d_image, image_blocks, d_index, nblocks, d_data, true, stream, "write list: null argument");
+    int r = entry_args(c, d_image, image_blocks, d_index, 1, nblocks, d_data, c && c->data, "write list: null argument");
     if (r || nblocks == 0)
         return r;
-    if (list_direct_args(c, d_data, d_status)) {
-        // the old blocks' statuses (0 / 1, 9 for an entry out of range) by the list decode, which
-        // changes nothing; then the new codewords, whatever the status was.  Without d_status the
-        // encode alone: RS needs nothing else of the old block.
-        hipStream_t s = (hipStream_t)stream;
-        (void)call_ordered(c, nblocks, stream);
-        if (d_status)
-            r = decode_list_direct(c, d_image, image_blocks, d_index, nblocks, nullptr, d_status, 0, nullptr, s);
-        if (!r)
-            r = encode_list_direct(c, d_data, d_image, image_blocks, d_index, nblocks, s);
-        return call_queued(c, r, nblocks, stream, "write list (async)");
-    }
-    ListCall call { c, (hipStream_t)stream, stream, nblocks };
+    const bool direct = list_direct_args(c, d_data, d_status);
+    ListCall call { c, stream, nblocks, "list", !direct };
     if ((r = call.begin()))
         return r;
-    const size_t piece = piece_of(c);
-    uint8_t* rows = c->d_list;
-    for (size_t off = 0; off < nblocks && !r; off += piece) {
-        const uint32_t nb = (uint32_t)std::min(piece, nblocks - off);
+    PieceIO io { c, d_image, image_blocks, stream, direct };
+    for (size_t off = 0, piece = call.piece(); off < nblocks && !r; off += piece) {
+        const size_t nb = std::min(piece, nblocks - off);
         const uint32_t* ix = d_index + off;
-        uint8_t* st = d_status ? d_status + off : c->d_list + c->list_status_off;
-        r = check_hip(ppfs_gather_blocks_launch(d_image, image_blocks, ix, nb, c->raw, rows, call.s), "list gather");
-        if (!r)
-            r = ppfs_ecc_write_device(c, d_data ? d_data + off * c->data : nullptr, rows, st, nb, stream);
-        if (!r)
-            r = check_hip(ppfs_scatter_blocks_launch(rows, d_image, image_blocks, ix, st, 2, nb, c->raw, call.s),
-                "list scatter");
-        if (!r && d_status)
-            r = check_hip(ppfs_list_oob_launch(ix, nb, image_blocks, st, nullptr, 0, call.s), "list range marks");
+        uint8_t* st = d_status ? d_status + off : nullptr;
+        const uint8_t* dd = d_data ? d_data + off * c->data : nullptr;
+        (void)((r = io.fetch(ix, nb)) || (r = io.write(ix, nb, dd, st)) || (r = io.marks(ix, nb, st, nullptr)));
     }
     return call.end(r, "write list (async)");
 }
@@ -274,7 +283,7 @@ int host_list_run(ppfs_ecc_ctx* c, const HostList& h)
         return 0;
     if (!h.index || (h.image_blocks && !h.image) || (h.op != OP_DECODE && c->data && !h.data_in))
         return fail(PPFS_ECC_EINVAL, "list (host): null argument");
-    const size_t raw = c->raw, ds = c->data, sb = 256 - std::min<size_t>(raw, 255);
+    const size_t raw = c->raw, ds = c->data, sb = spill_bytes(c);
     const size_t max_run = 8 * ppfs_ecc_host_chunk_blocks(c); // bounds the gathered copy; any cut gives the same result
     const bool wb = h.op == OP_DECODE && h.write_back && has_write_back(c);
     const bool need_rows = h.op != OP_ENCODE || encode_keeps_old_bits(c);

@@ -16,6 +16,7 @@ from tests.conftest import gpu_available
 from tests.oracle_lib import OracleDevice
 from tests.test_gpu_list import (BLOCKS, GUARD, LISTED, Codec, Guarded, _rs_errors, corrupted_image, dev, host, rng_for,
                                  small_list)
+from tests.test_gpu_list_direct import staged_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -412,6 +413,90 @@ def test_extents_longer_than_one_piece(oracle):
     c.eng.write_extents(dev(new), image_d, ext, st_d)
     assert np.array_equal(host(st_d), o_st[ix])
     assert np.array_equal(host(image_d), exp_image.reshape(-1))
+
+
+def test_extents_direct_equals_staged(oracle):
+    """RS(255, 249) over two pieces, the second shorter than one 64-row tile, through the direct engine
+    and through one created under PPFS_ECC_LIST_DIRECT=0 (the staged piece loop, which no other extent
+    test runs for a 255-byte RS code): packed bytes, statuses and the whole image are byte-identical, with
+    the status array 16-byte aligned, 3 bytes past a boundary (the copy out of the context's own array)
+    and absent; the aligned leg equals the oracle too.  1 .. t byte errors in every seventh block, five
+    invalid entries of each of test_invalid_entries' four kinds, in both pieces."""
+    c = Codec(oracle, "rs", 512, 3)
+    staged = staged_engine(ECC_REED_SOLOMON, 512, 3)
+    assert (c.eng.list_kernel_name(), staged.list_kernel_name()) == ("rs255-wg-list-lds", "gather-stage-scatter")
+    rng = rng_for("xdiff")
+    piece = c.eng.host_chunk_blocks() & ~1023
+    n = c.eng.host_chunk_blocks() + 37
+    assert piece < n < 2 * piece and n - piece < 64
+    blocks = n + 50
+    rows = c.valid_image(rng, blocks).reshape(blocks, c.raw).copy()
+    hit = np.arange(0, blocks, 7)
+    ne, start = 1 + np.arange(hit.size) % c.t, rng.integers(0, c.raw, hit.size)
+    for j in range(c.t):  # 37 is a unit mod 255: distinct positions per block
+        rows[hit[ne > j], (start[ne > j] + 37 * j) % c.raw] ^= rng.integers(1, 256, int((ne > j).sum()), dtype=np.uint8)
+    image = rows.reshape(-1)
+    ix = rng.permutation(blocks)[:n].astype(np.uint32)
+    off, ln = 11, 7
+    nbytes = n * ln
+    ext = np.zeros(n, EXTENT_DTYPE)
+    ext["pos"], ext["block"], ext["offset"], ext["length"] = np.arange(n, dtype=np.uint64) * ln, ix, off, ln
+    for k, (field, value) in enumerate((("block", blocks), ("block", 0xFFFFFFFF), ("offset", c.ds + 1),
+                                        ("pos", nbytes + 1 - ln))):
+        at = np.array([5 + k, 1000 + k, piece - 1 - k, piece + 3 + 8 * k, piece + 7 + 8 * k])
+        ext[field][at] = value
+    valid = (ext["block"] < blocks) & (ext["offset"] <= c.ds) & (ext["pos"] + ln <= nbytes)
+    assert (~valid).sum() == 20 and (~valid)[:piece].sum() == 12 and valid[-1]
+    ixv = ix[valid]
+    o_data, o_st, o_fixed, _ = c.decode(image)
+    assert not (o_st == 5).any() and {1, 2, 3} <= set(ne) and (o_st[hit] == 1).all()
+    exp_st = np.where(valid, o_st[ix], 9).astype(np.uint8)
+    exp_out = np.full((n, ln), 0xA5, np.uint8)
+    exp_out[valid] = o_data[ixv][:, off:off + ln]
+    exp_read = rows.copy()
+    exp_read[ixv] = o_fixed[ixv]
+    new = rng.integers(0, 256, nbytes, dtype=np.uint8)
+    payload = o_data[ixv].copy()
+    payload[:, off:off + ln] = new.reshape(n, ln)[valid]
+    exp_write = rows.copy()
+    exp_write[ixv] = c.encode(payload.reshape(-1), None).reshape(-1, c.raw)
+    new_d = dev(new)
+
+    def status(leg):
+        """(the whole guarded buffer, the n bytes the call gets)"""
+        if leg == "absent":
+            return None, None
+        t = torch.full((n + 48,), 77, dtype=torch.uint8, device="cuda")
+        lo = 16 if leg == "aligned" else 19
+        assert t.data_ptr() % 16 == 0
+        return t, t[lo:lo + n]
+
+    def status_of(t, leg):
+        if t is None:
+            return None
+        b, lo = host(t), 16 if leg == "aligned" else 19
+        assert (b[:lo] == 77).all() and (b[lo + n:] == 77).all(), "write outside the status array"
+        return b[lo:lo + n]
+
+    for leg in ("aligned", "skewed", "absent"):
+        res = []
+        for eng in (c.eng, staged):
+            image_d = dev(image)
+            out_d = torch.full((nbytes,), 0xA5, dtype=torch.uint8, device="cuda")
+            t, st = status(leg)
+            eng.read_extents(image_d, ext, out_d, st, write_back=True)
+            read = (host(out_d), status_of(t, leg), host(image_d))
+            image_d = dev(image)
+            t, st = status(leg)
+            eng.write_extents(new_d, image_d, ext, st)
+            res.append(read + (status_of(t, leg), host(image_d)))
+        for a, b in zip(*res):
+            assert (a is None and b is None) or np.array_equal(a, b), leg
+        if leg == "aligned":
+            out, r_st, r_img, w_st, w_img = res[0]
+            assert np.array_equal(out, exp_out.reshape(-1)) and np.array_equal(r_st, exp_st)
+            assert np.array_equal(r_img, exp_read.reshape(-1))
+            assert np.array_equal(w_st, exp_st) and np.array_equal(w_img, exp_write.reshape(-1))
 
 
 # ------------------------------------------------------------------------------------
