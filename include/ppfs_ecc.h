@@ -312,6 +312,75 @@ int ppfs_ecc_scrub_device(ppfs_ecc_ctx* ctx, uint8_t* d_image, size_t image_byte
     uint8_t* d_status, void* stream);
 
 /*
+ * Scrub of named blocks only: a block list, or the blocks an allocation bitmap marks.  After an
+ * irradiation run the blocks that matter are the ones the allocator handed out; free blocks may never have
+ * been written, cost HBM traffic, and their failures would drown the "failed" count of a sparsely filled
+ * CRC or parity device.  Engine extension; the reference has no scrub at all.
+ *
+ * counts record: 64 bytes, OVERWRITTEN (not accumulated) by each call; may be NULL.  d_counts is 8-byte
+ * aligned device memory.
+ *
+ * ppfs_ecc_scrub_list_*: exactly ppfs_ecc_decode_list_* with data == NULL, write_back = 1 and
+ * spill == NULL, plus the counts.  Everything is the list decode's: statuses in list order, status 9 for
+ * an entry out of range (it touches nothing), the repeated-index rules, the direct / staged choice and
+ * the alignment rule of d_status.  d_status / status and d_counts / counts may each be NULL; when only
+ * the counts are wanted the call uses a status scratch of its own (device form: the context's scrub
+ * scratch, below).  The device form never synchronises `stream`; a capturing stream gets
+ * PPFS_ECC_ENOTSUP.  Every entry counts once, repeated ones included.
+ *
+ * ppfs_ecc_scrub_allocated_*: the reference's on-disk bitmap (lib/bitmap/src/bitmap.cpp), consumed as it
+ * lies in the image.
+ *   bitmap_block   first block of the bitmap; it spans B = ceil(ceil(nbits / 8) / dataSize()) blocks
+ *                  (Bitmap::blocksSpanned, bitmap.cpp:27-31; integer arithmetic here, float there)
+ *   first_block    bit j stands for image block first_block + j
+ *   nbits          bits of the bitmap.  Bit j is byte j / 8 of the payloads of the B blocks taken back to
+ *                  back, under mask 0x80 >> (j % 8) (bitmap.cpp:8-14, 98-100)
+ *   d_status       (may be NULL) nbits bytes, any alignment: 0, 1, 5 or 9 for a set bit,
+ *                  PPFS_ECC_NOT_ALLOCATED for a clear one, whose block is not read
+ *   d_bitmap_status (may be NULL) B bytes, any alignment: the statuses of the bitmap's own blocks
+ * In this order: (1) the B bitmap blocks are decoded with write-back, scrubbed like any read of them
+ * (bitmap_* counts); (2) the bits are expanded into the ascending list of allocated blocks, the bits of a
+ * bitmap block with status 5 counting as SET: its payload is undefined, so every block it covers is
+ * scrubbed; (3) that list is list-scrubbed; (4) the per-bit statuses and the counts are written.  A data
+ * block at or past image_blocks gets status 9, as a list entry would.
+ * Shortened RS (n < 255): blocks are decoded independently and a spill is never applied, as in every list
+ * call.  This DIFFERS from ppfs_ecc_scrub_*, which chains a spill into the following blocks as the
+ * sequential reference does.
+ * Errors: PPFS_ECC_EINVAL, checked before anything touches the GPU, for a null ctx or image,
+ * dataSize() == 0, bitmap_block + B > image_blocks, or first_block + nbits passing 2^32.  nbits == 0
+ * returns 0 with zeroed counts.
+ * Device form: the bit range runs in pieces of 1 Mi bits, which bounds the scratch (4 bytes of index and
+ * 1 byte of status per bit).  The scratch is the context's: stream-ordered pool memory made on the
+ * context's own stream at the first scrub call that needs it (a larger one when a later call needs
+ * more), kept until ppfs_ecc_destroy and shared by all streams of the context, so a scrub call that uses
+ * it waits for the previous one, whichever stream that ran on; no call allocates or frees on the
+ * caller's stream.  Per piece the host reads back one 8-byte
+ * count to size the list call: the call SYNCHRONISES `stream` once per piece (compare
+ * ppfs_ecc_scrub_device, which synchronises between runs for n < 255) and returns with everything
+ * queued.  A capturing stream gets PPFS_ECC_ENOTSUP.
+ * Host form: ppfs_ecc_decode_host over the bitmap blocks in place, the same expansion on the CPU,
+ * ppfs_ecc_decode_list_host, and a CPU tally.
+ */
+#define PPFS_ECC_NOT_ALLOCATED 255 /* status of a bit that is 0 in the bitmap: block not read (engine extension) */
+
+typedef struct ppfs_ecc_scrub_counts { /* 64 bytes, overwritten (not accumulated) by each call */
+    uint64_t ok, corrected, failed; /* data blocks / list entries with status 0, 1, 5 */
+    uint64_t out_of_range;          /* status 9 */
+    uint64_t not_allocated;         /* bitmap form only: bits that are 0 */
+    uint64_t bitmap_ok, bitmap_corrected, bitmap_failed; /* bitmap form only: the bitmap's own blocks */
+} ppfs_ecc_scrub_counts;
+
+int ppfs_ecc_scrub_list_device(ppfs_ecc_ctx* ctx, uint8_t* d_image, size_t image_blocks, const uint32_t* d_index,
+    size_t nblocks, uint8_t* d_status, ppfs_ecc_scrub_counts* d_counts, void* stream);
+int ppfs_ecc_scrub_list_host(ppfs_ecc_ctx* ctx, uint8_t* image, size_t image_blocks, const uint32_t* index,
+    size_t nblocks, uint8_t* status, ppfs_ecc_scrub_counts* counts);
+int ppfs_ecc_scrub_allocated_device(ppfs_ecc_ctx* ctx, uint8_t* d_image, size_t image_blocks, uint32_t bitmap_block,
+    uint32_t first_block, size_t nbits, uint8_t* d_status, uint8_t* d_bitmap_status, ppfs_ecc_scrub_counts* d_counts,
+    void* stream);
+int ppfs_ecc_scrub_allocated_host(ppfs_ecc_ctx* ctx, uint8_t* image, size_t image_blocks, uint32_t bitmap_block,
+    uint32_t first_block, size_t nbits, uint8_t* status, uint8_t* bitmap_status, ppfs_ecc_scrub_counts* counts);
+
+/*
  * 2-of-3 bitwise majority of nrec replicated records of rec_bytes each, replacing
  * SuperBlockManager::_performBitVoting (lib/super_block_manager/src/super_block_manager.cpp:133-165):
  *   out[i] = majority(a[i], b[i], c[i]) bit by bit;

@@ -612,6 +612,87 @@ public:
             std::memcpy(err, e.data(), count);
         return {};
     }
+
+    // Scrub of named blocks only (ppfs_ecc.h ppfs_ecc_scrub_list_* / ppfs_ecc_scrub_allocated_*): the disk and
+    // log effect of readBlock({b, 0}, dataSize()) for the blocks named, without the payloads.  counts (may be
+    // null) is overwritten.  These per-block loops are the definition; the codecs run one engine call.
+    //   scrubList       the blocks idx[0 .. n) in list order; err (may be null) as readBlockList.  This default
+    //                   cannot tell a corrected block from a clean one (both count as ok); the codecs can.
+    //   scrubAllocated  the blocks first_data_block + j whose bit j is set in the on-disk bitmap (lib/bitmap/src/
+    //                   bitmap.cpp) of nbits bits that starts at bitmap_block: first the bitmap's own
+    //                   blocks_spanned(nbits) blocks (bitmap_err, may be null, and the bitmap_* counts), then the
+    //                   allocated blocks in ascending order.  All bits of a bitmap block that cannot be read count
+    //                   as set.  err (may be null): nbits bytes, 0 or the FsError for a set bit,
+    //                   PPFS_ECC_NOT_ALLOCATED (255) for a clear one, whose block is not read.
+    size_t bitmapBlocks(size_t nbits) const // Bitmap::blocksSpanned (bitmap.cpp:27-31) in integer arithmetic
+    {
+        const size_t ds = dataSize();
+        return ds ? ((nbits + 7) / 8 + ds - 1) / ds : 0;
+    }
+    virtual expected<void> scrubList(const block_index_t* idx, size_t n, ppfs_ecc_scrub_counts* counts, uint8_t* err)
+    {
+        std::vector<uint8_t> out(n * dataSize()), e(n);
+        auto r = readBlockList(idx, n, out.data(), e.data());
+        if (!r)
+            return r;
+        if (counts) {
+            *counts = ppfs_ecc_scrub_counts {};
+            for (uint8_t x : e)
+                ++(x == 0 ? counts->ok : x == (uint8_t)FsError::Disk_OutOfBounds ? counts->out_of_range : counts->failed);
+        }
+        if (err && n)
+            std::memcpy(err, e.data(), n);
+        return {};
+    }
+    virtual expected<void> scrubAllocated(block_index_t bitmap_block, block_index_t first_data_block, size_t nbits,
+        ppfs_ecc_scrub_counts* counts, uint8_t* err, uint8_t* bitmap_err)
+    {
+        const size_t ds = dataSize(), B = bitmapBlocks(nbits);
+        if (ds == 0 || (uint64_t)first_data_block + nbits > (1ull << 32))
+            return unexpected(FsError::Disk_OutOfBounds);
+        if (counts)
+            *counts = ppfs_ecc_scrub_counts {};
+        if (nbits == 0)
+            return {};
+        std::vector<uint8_t> stream(B * ds), be(B);
+        ppfs_ecc_scrub_counts bc {};
+        {
+            std::vector<block_index_t> bidx(B);
+            for (size_t b = 0; b < B; ++b)
+                bidx[b] = bitmap_block + (block_index_t)b;
+            if ((size_t)bitmap_block + B > numOfBlocks())
+                return unexpected(FsError::Disk_OutOfBounds);
+            auto r = readBlocks(bitmap_block, B, stream.data(), be.data());
+            if (!r)
+                return r;
+            for (uint8_t x : be)
+                ++(x == 0 ? bc.bitmap_ok : bc.bitmap_failed);
+        }
+        if (bitmap_err)
+            std::memcpy(bitmap_err, be.data(), B);
+        std::vector<block_index_t> list;
+        for (size_t j = 0; j < nbits; ++j)
+            if (be[j / (8 * ds)] != 0 || (stream[j / 8] & (0x80u >> (j % 8))))
+                list.push_back(first_data_block + (block_index_t)j);
+        std::vector<uint8_t> e(list.size());
+        ppfs_ecc_scrub_counts lc {};
+        auto r = scrubList(list.data(), list.size(), &lc, e.data());
+        if (!r)
+            return r;
+        if (err) {
+            std::memset(err, PPFS_ECC_NOT_ALLOCATED, nbits);
+            for (size_t k = 0; k < list.size(); ++k)
+                err[list[k] - first_data_block] = e[k];
+        }
+        if (counts) {
+            *counts = lc;
+            counts->not_allocated = nbits - list.size();
+            counts->bitmap_ok = bc.bitmap_ok;
+            counts->bitmap_corrected = 0;
+            counts->bitmap_failed = bc.bitmap_failed;
+        }
+        return {};
+    }
 };
 
 // The entries of a FileIO::readFile / writeFile walk (file_io.cpp:24-42, 50-88) over the blocks
@@ -1176,6 +1257,82 @@ public:
         return {};
     }
 
+    // One engine call (ppfs_ecc_scrub_list_host) on a mapped disk image.  Elsewhere, and for a shortened RS
+    // code, whose write-back may run into the next block, the per-block loop; its corrections are the
+    // events the reads logged.
+    expected<void> scrubList(const block_index_t* idx, size_t n, ppfs_ecc_scrub_counts* counts, uint8_t* err) override
+    {
+        uint8_t* img = _disk.mapped();
+        if (!img || has_spill() || !_raw) {
+            const size_t logged = _logged;
+            ppfs_ecc_scrub_counts c {};
+            auto r = IBlockDevice::scrubList(idx, n, &c, err);
+            if (!r)
+                return r;
+            c.corrected = _logged - logged;
+            c.ok -= std::min<uint64_t>(c.ok, c.corrected);
+            if (counts)
+                *counts = c;
+            return {};
+        }
+        std::vector<uint8_t> status(n);
+        ppfs_ecc_scrub_counts c {};
+        if (!EccEngine::ok(ppfs_ecc_scrub_list_host(_eng.ctx(), img, _disk.size() / _raw, idx, n, status.data(), &c), "scrub list"))
+            return unexpected(FsError::Disk_IOError);
+        for (size_t i = 0; i < n; ++i) {
+            if (status[i] == PPFS_ECC_CORRECTED)
+                log(idx[i]);
+            if (err) // statuses 5 and 9 are FsError's BlockDevice_CorrectionError and Disk_OutOfBounds
+                err[i] = status[i] == PPFS_ECC_CORRECTED ? 0 : status[i];
+        }
+        if (counts)
+            *counts = c;
+        return {};
+    }
+
+    // One engine call (ppfs_ecc_scrub_allocated_host) on a mapped disk image: the bitmap's blocks, then the
+    // allocated blocks, each group's corrections logged in ascending block order as the reads would.
+    expected<void> scrubAllocated(block_index_t bitmap_block, block_index_t first_data_block, size_t nbits,
+        ppfs_ecc_scrub_counts* counts, uint8_t* err, uint8_t* bitmap_err) override
+    {
+        uint8_t* img = _disk.mapped();
+        if (!img || has_spill() || !_raw || !_ds) {
+            const size_t logged = _logged;
+            ppfs_ecc_scrub_counts c {};
+            auto r = IBlockDevice::scrubAllocated(bitmap_block, first_data_block, nbits, &c, err, bitmap_err);
+            if (!r)
+                return r;
+            // scrubList above counted the data blocks' corrections; the rest were the bitmap's
+            c.bitmap_corrected = _logged - logged - c.corrected;
+            c.bitmap_ok -= std::min<uint64_t>(c.bitmap_ok, c.bitmap_corrected);
+            if (counts)
+                *counts = c;
+            return {};
+        }
+        const size_t B = bitmapBlocks(nbits);
+        std::vector<uint8_t> status(nbits), bst(B);
+        ppfs_ecc_scrub_counts c {};
+        if (!EccEngine::ok(ppfs_ecc_scrub_allocated_host(_eng.ctx(), img, _disk.size() / _raw, bitmap_block, first_data_block,
+                               nbits, status.data(), bst.data(), &c),
+                "scrub allocated"))
+            return unexpected(FsError::Disk_OutOfBounds); // the only failures are the arguments': a range off the image
+        for (size_t b = 0; b < B; ++b) {
+            if (bst[b] == PPFS_ECC_CORRECTED)
+                log(bitmap_block + (block_index_t)b);
+            if (bitmap_err)
+                bitmap_err[b] = bst[b] == PPFS_ECC_CORRECTED ? 0 : bst[b];
+        }
+        for (size_t j = 0; j < nbits; ++j) {
+            if (status[j] == PPFS_ECC_CORRECTED)
+                log(first_data_block + (block_index_t)j);
+            if (err)
+                err[j] = status[j] == PPFS_ECC_CORRECTED ? 0 : status[j];
+        }
+        if (counts)
+            *counts = c;
+        return {};
+    }
+
 protected:
     EngineBlockDevice(IDisk& disk, std::shared_ptr<Logger> logger, uint32_t type, uint32_t bs, uint32_t t,
         uint64_t poly, int device, const char* log_name)
@@ -1234,6 +1391,7 @@ protected:
 
     void log(block_index_t b)
     {
+        ++_logged;
         if (_logger && _log_name)
             _logger->logEvent(ErrorCorrectionEvent(_log_name, b));
     }
@@ -1294,6 +1452,7 @@ protected:
     EccEngine _eng;
     size_t _raw, _ds;
     const char* _log_name;
+    size_t _logged = 0; // correction events so far (log()): what a per-block scrub loop corrected
 };
 
 class ReedSolomonBlockDevice : public EngineBlockDevice {

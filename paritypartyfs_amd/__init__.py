@@ -3,17 +3,18 @@
 Product path: paritypartyfs_amd/csrc (HIP kernels for gfx950 + the C ABI of include/ppfs_ecc.h),
 loaded from the in-tree libppfs_ecc.so.  Python pieces:
   - ecc.EccEngine            batch encode/decode/write/scrub on HBM tensors or host arrays, contiguous
-                             ranges, block lists or byte extents (block, offset, length)
+                             ranges, block lists or byte extents (block, offset, length); scrub of a
+                             block list or of the blocks an on-disk allocation bitmap marks
   - ecc.EccGroup             the host calls sharded over several GPUs (one thread per device)
   - ecc.vote3 / vote3_host   2-of-3 bitwise voting of replicated records (superblock copies)
   - block_device.*           IBlockDevice mirror (ReedSolomon/Crc/Hamming/Parity/Raw devices)
 """
 from ._native import (ECC_CRC, ECC_HAMMING, ECC_NONE, ECC_PARITY, ECC_REED_SOLOMON, STATUS_CORRECTED,
-                      STATUS_CORRECTION_ERROR, STATUS_OK, STATUS_OUT_OF_BOUNDS, NativeLibraryMissing)
-from .ecc import EccEngine, EccGroup, crc_implicit_to_explicit, device_copy, inject_bytes, pinned, vote3, vote3_host
+                      STATUS_CORRECTION_ERROR, STATUS_NOT_ALLOCATED, STATUS_OK, STATUS_OUT_OF_BOUNDS, NativeLibraryMissing)
+from .ecc import EccEngine, EccGroup, ScrubCounts, crc_implicit_to_explicit, device_copy, inject_bytes, pinned, vote3, vote3_host
 
 __all__ = [
-    "EccEngine", "EccGroup", "crc_implicit_to_explicit", "device_copy", "inject_bytes", "pinned", "vote3", "vote3_host", "NativeLibraryMissing",
+    "EccEngine", "EccGroup", "ScrubCounts", "crc_implicit_to_explicit", "device_copy", "inject_bytes", "pinned", "vote3", "vote3_host", "NativeLibraryMissing",
     "ECC_NONE", "ECC_CRC", "ECC_HAMMING", "ECC_PARITY", "ECC_REED_SOLOMON",
-    "STATUS_OK", "STATUS_CORRECTED", "STATUS_CORRECTION_ERROR", "STATUS_OUT_OF_BOUNDS",
+    "STATUS_OK", "STATUS_CORRECTED", "STATUS_CORRECTION_ERROR", "STATUS_OUT_OF_BOUNDS", "STATUS_NOT_ALLOCATED",
 ]

@@ -20,6 +20,7 @@ ECC_NONE, ECC_CRC, ECC_HAMMING, ECC_PARITY, ECC_REED_SOLOMON = 0, 1, 2, 3, 4
 
 STATUS_OK, STATUS_CORRECTED, STATUS_CORRECTION_ERROR = 0, 1, 5
 STATUS_OUT_OF_BOUNDS = 9  # a block-list entry past the image (FsError::Disk_OutOfBounds)
+STATUS_NOT_ALLOCATED = 255  # scrub_allocated: the block's bit is clear, the block was not read
 
 # every symbol include/ppfs_ecc.h declares
 EXPORTED_SYMBOLS = (
@@ -52,6 +53,10 @@ EXPORTED_SYMBOLS = (
     "ppfs_ecc_write_extents_host",
     "ppfs_ecc_scrub_host",
     "ppfs_ecc_scrub_device",
+    "ppfs_ecc_scrub_list_device",
+    "ppfs_ecc_scrub_list_host",
+    "ppfs_ecc_scrub_allocated_device",
+    "ppfs_ecc_scrub_allocated_host",
     "ppfs_vote3_device",
     "ppfs_vote3_host",
     "ppfs_copy_device",
@@ -87,6 +92,12 @@ class EccParams(ctypes.Structure):
         ("reserved", c_uint32),
         ("crc_polynomial", c_uint64),
     ]
+
+
+class ScrubCounts(ctypes.Structure):
+    """ppfs_ecc_scrub_counts: what a list / allocated scrub found (64 bytes, overwritten by each call)."""
+    _fields_ = [(n, c_uint64) for n in ("ok", "corrected", "failed", "out_of_range", "not_allocated", "bitmap_ok",
+                                        "bitmap_corrected", "bitmap_failed")]
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -194,6 +205,18 @@ def lib() -> ctypes.CDLL:
     L.ppfs_ecc_scrub_host.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, POINTER(c_size_t)]
     L.ppfs_ecc_scrub_device.restype = c_int
     L.ppfs_ecc_scrub_device.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]
+    # list scrub: (ctx, image, image_blocks, index, nblocks, status, counts[, stream]); allocated scrub:
+    # (ctx, image, image_blocks, bitmap_block, first_block, nbits, status, bitmap_status, counts[, stream])
+    L.ppfs_ecc_scrub_list_device.restype = c_int
+    L.ppfs_ecc_scrub_list_device.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]
+    L.ppfs_ecc_scrub_list_host.restype = c_int
+    L.ppfs_ecc_scrub_list_host.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p]
+    L.ppfs_ecc_scrub_allocated_device.restype = c_int
+    L.ppfs_ecc_scrub_allocated_device.argtypes = [c_void_p, c_void_p, c_size_t, c_uint32, c_uint32, c_size_t, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p]
+    L.ppfs_ecc_scrub_allocated_host.restype = c_int
+    L.ppfs_ecc_scrub_allocated_host.argtypes = [c_void_p, c_void_p, c_size_t, c_uint32, c_uint32, c_size_t, c_void_p,
+                                                c_void_p, c_void_p]
     L.ppfs_vote3_device.restype = c_int
     L.ppfs_vote3_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]
     L.ppfs_copy_device.restype = c_int

@@ -26,8 +26,8 @@ from typing import Generic, List, Optional, Tuple, TypeVar
 import numpy as np
 
 from ._native import (ECC_CRC, ECC_HAMMING, ECC_NONE, ECC_PARITY, ECC_REED_SOLOMON, EXTENT_DTYPE, STATUS_CORRECTED,
-                      STATUS_CORRECTION_ERROR, STATUS_OUT_OF_BOUNDS)
-from .ecc import EccEngine
+                      STATUS_CORRECTION_ERROR, STATUS_NOT_ALLOCATED, STATUS_OUT_OF_BOUNDS)
+from .ecc import EccEngine, ScrubCounts
 
 MAX_BLOCK_SIZE = 4096  # iblock_device.hpp:3
 MAX_RS_BLOCK_SIZE = 255  # rs_block_device.hpp:7
@@ -206,6 +206,53 @@ class IBlockDevice:
         _, err = self.readBlocks(first, count)
         failed = int(np.count_nonzero(err))
         return (count - failed, 0, failed), err
+
+    # scrub of named blocks only (include/ppfs_ecc.h ppfs_ecc_scrub_list_* / ppfs_ecc_scrub_allocated_*): the
+    # per-block loops; the codecs override them with one engine call
+    def bitmapBlocks(self, nbits: int) -> int:
+        """Bitmap::blocksSpanned (bitmap.cpp:27-31) in integer arithmetic."""
+        return -(-(-(-int(nbits) // 8)) // self.dataSize())
+
+    def _log_count(self) -> int:
+        logger = getattr(self, "_logger", None)
+        return len(logger.corrections) if logger is not None else 0
+
+    def scrubList(self, indices) -> Tuple[ScrubCounts, np.ndarray]:
+        """The disk and log effect of readBlock(DataLocation(i, 0), dataSize()) for i in indices, in list
+        order, without the payloads.  Returns (ScrubCounts, FsError-or-0 per entry)."""
+        log0 = self._log_count()
+        _, err = self.readBlockList(indices)
+        corrected = self._log_count() - log0
+        oob = int(np.count_nonzero(err == int(FsError.Disk_OutOfBounds)))
+        failed = int(np.count_nonzero(err)) - oob
+        return ScrubCounts(len(err) - failed - oob - corrected, corrected, failed, oob, 0, 0, 0, 0), err
+
+    def scrubAllocated(self, bitmap_block: int, first_data_block: int, nbits: int) -> Tuple[ScrubCounts, np.ndarray, np.ndarray]:
+        """Scrub of the blocks first_data_block + j whose bit j is set in the on-disk bitmap (lib/bitmap/src/
+        bitmap.cpp) of nbits bits that starts at bitmap_block: the bitmap's own blocks are read first, then the
+        allocated blocks in ascending order; all bits of a bitmap block that cannot be read count as set.
+        Returns (ScrubCounts, per bit: 0 or the FsError, 255 where the bit is clear and the block was not
+        read, FsError-or-0 per bitmap block)."""
+        ds, B = self.dataSize(), self.bitmapBlocks(nbits)
+        bitmap_err = np.zeros(B, dtype=np.uint8)
+        bits = np.zeros(nbits, dtype=bool)
+        bc = [0, 0, 0]
+        for b in range(B):
+            log0 = self._log_count()
+            r = self.readBlock(DataLocation(bitmap_block + b, 0), ds)
+            lo, hi = b * 8 * ds, min(nbits, (b + 1) * 8 * ds)
+            if r:
+                bits[lo:hi] = np.unpackbits(np.frombuffer(r.value(), dtype=np.uint8))[:hi - lo].astype(bool)
+                bc[1 if self._log_count() > log0 else 0] += 1
+            else:
+                bitmap_err[b] = int(r.error())
+                bits[lo:hi] = True
+                bc[2] += 1
+        alloc = np.nonzero(bits)[0]
+        c, e = self.scrubList(first_data_block + alloc)
+        err = np.full(nbits, STATUS_NOT_ALLOCATED, dtype=np.uint8)
+        err[alloc] = e
+        return ScrubCounts(c.ok, c.corrected, c.failed, c.out_of_range, nbits - alloc.size, *bc), err, bitmap_err
 
     def writeBlocks(self, first: int, payloads: np.ndarray) -> np.ndarray:
         err = np.zeros(len(payloads), dtype=np.uint8)
@@ -481,6 +528,49 @@ class _EngineDevice(IBlockDevice):
             if not w:
                 err[:] = int(w.error())
         return counts, err
+
+    def _scrub_image(self):
+        """The whole disk image for one engine call on it, or None where the per-block loop has to run: a
+        shortened RS code, whose write-back may run into the next block, and a disk that cannot be read whole."""
+        if self._has_spill() or not self._raw or not self._ds:
+            return None
+        r = self._disk.read(0, self._disk.size())
+        return np.frombuffer(r.value(), dtype=np.uint8).copy() if r else None
+
+    def _scrub_done(self, image: np.ndarray, before: np.ndarray, status: np.ndarray, blocks) -> np.ndarray:
+        """After an engine scrub of `image`: a correction event per status 1 in the order of `blocks`, the
+        changed bytes onto the disk; returns the statuses as FsError-or-0 (5, 9 and 255 are kept)."""
+        for k in np.nonzero(status == STATUS_CORRECTED)[0]:
+            self._log(int(blocks[int(k)]))
+        changed = np.nonzero(image != before)[0]
+        if changed.size:
+            lo, hi = int(changed[0]), int(changed[-1]) + 1
+            self._disk.write(lo, image[lo:hi].tobytes())
+        return np.where(status == STATUS_CORRECTED, 0, status).astype(np.uint8)
+
+    def scrubList(self, indices) -> Tuple[ScrubCounts, np.ndarray]:
+        """IBlockDevice.scrubList in one engine call (EccEngine.scrub_list_host) on the disk image."""
+        image = self._scrub_image()
+        if image is None:
+            return super().scrubList(indices)
+        ix = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        before, status = image.copy(), np.zeros(ix.size, dtype=np.uint8)
+        counts = self._engine.scrub_list_host(image, ix, status=status)
+        return counts, self._scrub_done(image, before, status, ix)
+
+    def scrubAllocated(self, bitmap_block: int, first_data_block: int, nbits: int) -> Tuple[ScrubCounts, np.ndarray, np.ndarray]:
+        """IBlockDevice.scrubAllocated in one engine call (EccEngine.scrub_allocated_host) on the disk image;
+        the bitmap blocks' corrections are logged first, then the data blocks', each in ascending order."""
+        image = self._scrub_image()
+        B = self.bitmapBlocks(nbits) if self._ds else 0
+        if image is None or bitmap_block + B > self.numOfBlocks():
+            return super().scrubAllocated(bitmap_block, first_data_block, nbits)
+        before, status, bst = image.copy(), np.zeros(nbits, dtype=np.uint8), np.zeros(B, dtype=np.uint8)
+        counts = self._engine.scrub_allocated_host(image, bitmap_block, first_data_block, nbits, status=status,
+                                                   bitmap_status=bst)
+        blocks = np.concatenate([bitmap_block + np.arange(B), first_data_block + np.arange(nbits)])
+        err = self._scrub_done(image, before, np.concatenate([bst, status]), blocks)
+        return counts, err[B:], err[:B]
 
     def _log_count(self) -> int:
         return len(self._logger.corrections) if self._logger is not None else 0

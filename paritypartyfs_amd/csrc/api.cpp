@@ -508,7 +508,7 @@ extern "C" void ppfs_ecc_destroy(ppfs_ecc_ctx* c)
         (void)hipEventSynchronize(c->ev[i]);
         (void)hipEventDestroy(c->ev[i]);
     }
-    if (c->ev_overflow && (c->d_tables || c->d_scratch || c->d_ctr || c->d_list))
+    if (c->ev_overflow && (c->d_tables || c->d_scratch || c->d_ctr || c->d_list || c->d_scrub))
         (void)hipDeviceSynchronize();
     (void)hipGetLastError();
     if (!srv_gone) {
@@ -536,6 +536,11 @@ extern "C" void ppfs_ecc_destroy(ppfs_ecc_ctx* c)
     mem_free(c, c->d_scratch);
     mem_free(c, c->d_list); // list calls ran on caller streams: waited for above
     mem_free(c, c->d_ext);  // ... and so did the extent calls
+    mem_free(c, c->d_scrub); // ... and the scrub calls
+    for (void* p : c->scrub_old)
+        mem_free(c, p);
+    if (c->scrub_ev)
+        (void)hipEventDestroy(c->scrub_ev);
     if (c->list_ev)
         (void)hipEventDestroy(c->list_ev);
     pin_free(c->h_zc, c->zc_bytes, kPinMapped);
@@ -562,7 +567,8 @@ extern "C" const char* ppfs_ecc_list_encode_kernel_name(const ppfs_ecc_ctx* c)
 #ifdef PPFS_ECC_DEBUG
 #define PPFS_DBG_UNITS(X) X(ppfs_dbg_faults_rs_t2) X(ppfs_dbg_faults_rs_t4) X(ppfs_dbg_faults_rs_t6) \
     X(ppfs_dbg_faults_rs_t8) X(ppfs_dbg_faults_rs_t10) X(ppfs_dbg_faults_rs_t16) X(ppfs_dbg_faults_rs_t32)   \
-    X(ppfs_dbg_faults_rs_generic) X(ppfs_dbg_faults_bit) X(ppfs_dbg_faults_bitfast) X(ppfs_dbg_faults_vote)
+    X(ppfs_dbg_faults_rs_generic) X(ppfs_dbg_faults_bit) X(ppfs_dbg_faults_bitfast) X(ppfs_dbg_faults_vote) \
+    X(ppfs_dbg_alloc_faults)
 #define PPFS_DBG_DECL(f) extern "C" long long f(void);
 PPFS_DBG_UNITS(PPFS_DBG_DECL)
 extern "C" long long ppfs_ecc_debug_faults(void)

@@ -10,6 +10,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "../../include/ppfs_ecc.h"
 #include "host_plan.hpp"
@@ -147,6 +148,15 @@ struct ppfs_ecc_ctx {
     // its entries, made at the first extent call; ordered by list_ev like the rows they go with
     uint8_t* d_ext = nullptr;
     size_t ext_bytes = 0, ext_index_off = 0;
+    // list and allocated scrub (scrub_path.cpp): the scratch of one call (bitmap stream, a piece's list and
+    // statuses), made at the first call that needs it and replaced by a larger one when a call needs more
+    // (the replaced ones are kept until destroy: queued work may still read them); shared by every stream
+    // of the context, so a call that uses it waits for scrub_ev, recorded after the previous such call
+    uint8_t* d_scrub = nullptr;
+    size_t scrub_bytes = 0;
+    std::vector<void*> scrub_old;
+    hipEvent_t scrub_ev = nullptr;
+    bool scrub_ev_rec = false;
 };
 
 #pragma GCC visibility push(hidden)

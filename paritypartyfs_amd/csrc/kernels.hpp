@@ -1,6 +1,7 @@
 // kernels.hpp -- the host-callable launchers of the kernel translation units, declared once:
 // rs_kernels.hip (Reed-Solomon and its servers), bit_kernels.hip (CRC, Hamming, parity and the bit
-// server) and vote.hip (vote, copy, gather, patch list, inject, flag, block lists).  The
+// server) vote.hip (vote, copy, gather, patch list, inject, flag, block lists) and alloc_scan.hip (bitmap
+// expansion, scrub tally).  The
 // three table-sizing functions are in host_tables.hpp, beside the builders that use them.
 #pragma once
 
@@ -75,4 +76,17 @@ hipError_t ppfs_extent_index_launch(const ppfs_ecc_extent* ext, uint32_t nb, uin
     uint64_t buf_bytes, uint32_t* index, hipStream_t s);
 hipError_t ppfs_extent_copy_launch(int to_stage, const ppfs_ecc_extent* ext, const uint32_t* index, const uint8_t* status,
     uint32_t nb, uint32_t ds, uint8_t* stage, uint64_t stage_cap, uint8_t* buf, uint64_t buf_bytes, hipStream_t s);
+// allocated-block and list scrub (scrub_path.cpp; alloc_scan.hip, arithmetic in alloc_plan.hpp).
+// expand: piece `piece` of the decoded bitmap (stream: 4-byte aligned, B * ds bytes; bstatus: its blocks'
+// statuses) -> the ascending list of first_block + j for its set bits in index, their number in
+// *piece_total (8-byte aligned); scratch: 2 * alloc::PIECE_CHUNKS dwords; counts (may be null): the
+// 64-byte record whose not_allocated grows by the piece's clear bits.
+// iota: index[i] = first + i.  tally: list-order statuses st[k] of entries index[k] -> status_out[index[k] -
+// first] (below out_n; null: no scatter, index unused) and counts[slot0 + slot] for the slots below ncat.
+hipError_t ppfs_alloc_expand_launch(const uint8_t* stream, const uint8_t* bstatus, uint64_t B, uint64_t ds, uint64_t nbits,
+    uint32_t first_block, uint64_t piece, uint32_t* scratch, unsigned long long* piece_total, uint32_t* index,
+    unsigned long long* counts, hipStream_t s);
+hipError_t ppfs_alloc_iota_launch(uint32_t* index, uint32_t first, uint64_t n, hipStream_t s);
+hipError_t ppfs_scrub_tally_launch(const uint8_t* st, const uint32_t* index, uint64_t n, uint32_t first, uint8_t* status_out,
+    uint64_t out_n, unsigned long long* counts, int slot0, int ncat, hipStream_t s);
 }

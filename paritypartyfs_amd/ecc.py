@@ -7,6 +7,7 @@ stream provider.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 from ctypes import byref, c_void_p
 from typing import Optional
@@ -315,6 +316,86 @@ class EccEngine:
         check(lib().ppfs_ecc_scrub_device(self._h, _ptr(image), image.numel(), n, _ptr(status),
                                           _stream_handle(stream)))
 
+    # ---------------- scrub of named blocks (ppfs_ecc_scrub_list_*, ppfs_ecc_scrub_allocated_*) ----------------
+    # A list scrub is decode_list(data=None, write_back=True) plus counts; an allocated scrub reads the
+    # reference's on-disk bitmap as it lies in the image (bit j of the bitmap starting at block
+    # bitmap_block stands for block first_block + j) and list-scrubs the blocks whose bit is set.
+    @staticmethod
+    def _device_counts(counts):
+        """The 64-byte device record of a device scrub: None, True (a fresh tensor) or the caller's tensor of
+        eight int64."""
+        if counts is None or counts is False:
+            return None
+        import torch
+
+        if counts is True:
+            return torch.zeros(8, dtype=torch.int64, device="cuda")
+        if not getattr(counts, "is_cuda", False) or counts.dtype != torch.int64 or not counts.is_contiguous() \
+                or counts.numel() < 8:
+            raise ValueError("counts: a contiguous CUDA int64 tensor of 8 elements (fields of SCRUB_COUNT_FIELDS)")
+        return counts
+
+    def bitmap_blocks(self, nbits: int) -> int:
+        """Blocks a bitmap of nbits bits spans (Bitmap::blocksSpanned, in integer arithmetic)."""
+        if not self.data_size:
+            raise ValueError("blocks of this codec have no payload")
+        return -(-(-(-int(nbits) // 8)) // self.data_size)
+
+    def scrub_list(self, image, index, status=None, counts=None, stream=None):
+        """Device list scrub.  counts: None, True (returns a fresh CUDA int64 tensor of the eight fields of
+        SCRUB_COUNT_FIELDS; read it after synchronising) or such a tensor of the caller's.  Never synchronises."""
+        n, blocks = self._list_check("device", image, index, status=status)
+        d_counts = self._device_counts(counts)
+        check(lib().ppfs_ecc_scrub_list_device(self._h, _ptr(image), blocks, self._index_ptr(index), n, _ptr(status),
+                                               None if d_counts is None else d_counts.data_ptr(),
+                                               _stream_handle(stream)))
+        return d_counts
+
+    def scrub_list_host(self, image: np.ndarray, index: np.ndarray, status: Optional[np.ndarray] = None) -> "ScrubCounts":
+        n, blocks = self._list_check("host", image, index, status=status)
+        rec = _native.ScrubCounts()
+        check(lib().ppfs_ecc_scrub_list_host(self._h, _ptr(image), blocks, self._index_ptr(index), n, _ptr(status),
+                                             byref(rec)))
+        return ScrubCounts(*[int(getattr(rec, f)) for f in SCRUB_COUNT_FIELDS])
+
+    def _allocated_check(self, kind, image, nbits, status, bitmap_status):
+        if image is None:
+            raise ValueError("image: required")
+        if nbits < 0:
+            raise ValueError("nbits must be >= 0")
+        _need("image", image, 0, kind)
+        _need("status", status, nbits, kind)
+        _need("bitmap_status", bitmap_status, self.bitmap_blocks(nbits), kind)
+        _ptr(image), _ptr(status), _ptr(bitmap_status)  # contiguous uint8
+        return _size(image) // self.raw_block_size
+
+    def scrub_allocated(self, image, bitmap_block: int, first_block: int, nbits: int, status=None, bitmap_status=None,
+                        counts=None, stream=None):
+        """Device allocated scrub; counts as in scrub_list.  Synchronises the stream once per 1 Mi bits."""
+        blocks = self._allocated_check("device", image, nbits, status, bitmap_status)
+        d_counts = self._device_counts(counts)
+        check(lib().ppfs_ecc_scrub_allocated_device(self._h, _ptr(image), blocks, int(bitmap_block), int(first_block),
+                                                    int(nbits), _ptr(status), _ptr(bitmap_status),
+                                                    None if d_counts is None else d_counts.data_ptr(),
+                                                    _stream_handle(stream)))
+        return d_counts
+
+    def scrub_allocated_host(self, image: np.ndarray, bitmap_block: int, first_block: int, nbits: int,
+                             status: Optional[np.ndarray] = None,
+                             bitmap_status: Optional[np.ndarray] = None) -> "ScrubCounts":
+        blocks = self._allocated_check("host", image, nbits, status, bitmap_status)
+        rec = _native.ScrubCounts()
+        check(lib().ppfs_ecc_scrub_allocated_host(self._h, _ptr(image), blocks, int(bitmap_block), int(first_block),
+                                                  int(nbits), _ptr(status), _ptr(bitmap_status), byref(rec)))
+        return ScrubCounts(*[int(getattr(rec, f)) for f in SCRUB_COUNT_FIELDS])
+
+
+# ppfs_ecc_scrub_counts: the host forms return it as this tuple, the device forms as a CUDA int64 tensor
+# in the same field order (ScrubCounts(*tensor.tolist()) after synchronising)
+SCRUB_COUNT_FIELDS = ("ok", "corrected", "failed", "out_of_range", "not_allocated", "bitmap_ok", "bitmap_corrected",
+                      "bitmap_failed")
+ScrubCounts = collections.namedtuple("ScrubCounts", SCRUB_COUNT_FIELDS)
+
 
 class EccGroup:
     """Multi-GPU host path (include/ppfs_ecc.h ppfs_ecc_group_*): one context per
@@ -460,4 +541,4 @@ def crc_implicit_to_explicit(p: int) -> int:
     return int(lib().ppfs_ecc_crc_implicit_to_explicit(ctypes.c_uint64(p)))
 
 
-__all__ = ["EccEngine", "crc_implicit_to_explicit", "device_copy", "inject_bytes", "pinned", "vote3", "vote3_host", "_native"]
+__all__ = ["EccEngine", "ScrubCounts", "SCRUB_COUNT_FIELDS", "crc_implicit_to_explicit", "device_copy", "inject_bytes", "pinned", "vote3", "vote3_host", "_native"]
