@@ -381,6 +381,99 @@ int ppfs_ecc_scrub_allocated_host(ppfs_ecc_ctx* ctx, uint8_t* image, size_t imag
     uint32_t first_block, size_t nbits, uint8_t* status, uint8_t* bitmap_status, ppfs_ecc_scrub_counts* counts);
 
 /*
+ * Read a file from its inode: the read-only walk of the index-block tree on the GPU.  FileIO::readFile
+ * (lib/file_io/src/file_io.cpp:12-44) gets its blocks from BlockIndexIterator (:186-463), which reads the
+ * file's singly, doubly and trebly indirect index blocks one readBlock at a time (_readIndexBlock,
+ * :465-480), each read depending on the one before.  Here the 64 bytes of the inode that describe the
+ * tree are the argument, and the walk is at most three list decodes with an expansion kernel between
+ * them.  Engine extension; read-only: nothing allocates or grows.
+ *
+ * The tree (inode.hpp:18-41): ds = dataSize(), ipb = ds / 4 entries per index block, little-endian
+ * uint32 at payload bytes [4 slot, 4 slot + 4); payload bytes past 4 ipb are ignored.  A file occupies
+ * ceil(file_size / ds) blocks, the tree holds 12 + ipb + ipb^2 + ipb^3 (its capacity, in 64 bits).  File
+ * block j: j < 12 is direct[j]; s = j - 12 < ipb is entry s of `indirect`; s = j - 12 - ipb < ipb^2 is
+ * entry s % ipb of the leaf named by entry s / ipb of `doubly_indirect`; s = j - 12 - ipb - ipb^2 < ipb^3
+ * is entry s % ipb of the leaf named by entry (s / ipb) % ipb of the mid block named by entry s / ipb^2
+ * of `trebly_indirect`.
+ *
+ * ppfs_ecc_file_span: readFile(offset, nbytes)'s first file block, block count and the bytes it delivers
+ * (nbytes clamped to file_size - offset).  -EINVAL for offset >= file_size with nbytes > 0 and for a range
+ * whose blocks pass the capacity; nbytes == 0 gives zeros.  Outputs may be NULL.  No GPU.
+ * ppfs_ecc_file_tree_blocks: the number T of index blocks a walk over [first_block, first_block + nblocks)
+ * visits, or a negative error under the rules below.  No GPU.
+ *
+ * ppfs_ecc_file_blocks_*: the image blocks of file blocks [first_block, first_block + nblocks).
+ *   file          HOST pointer in both forms
+ *   index         (may be NULL, 4-byte aligned) index[i] = image block of file block first_block + i;
+ *                 0xFFFFFFFF where the path to it failed
+ *   path_status   (may be NULL) 0, or the 5 / 9 inherited from the index block that failed above it
+ *   tree_index / tree_status  (may be NULL) the T index blocks in LEVEL ORDER -- A: the roots visited, in
+ *                 the order indirect, doubly_indirect, trebly_indirect; B: the doubly tree's leaves
+ *                 ascending, then the trebly tree's mid blocks ascending; C: the trebly tree's leaves
+ *                 ascending -- and their statuses 0 / 1 / 5 / 9
+ *   counts        (may be NULL; device form: 8-byte aligned device memory) overwritten: index_* count the T
+ *                 tree blocks by status, the first four the file blocks by path status
+ *   write_back    applies to the index blocks, as in ppfs_ecc_decode_list_*
+ * Each needed index block is decoded exactly once per call, as readBlock({b, 0}, 4 ipb) with the codec's
+ * write-back.  An index block with status 5 (payload undefined) or 9 hands that status to everything under
+ * it, whose pointer becomes 0xFFFFFFFF; status 1 is not handed down.  A pointer to an index block at or past
+ * image_blocks gives that block status 9; it touches nothing.  A data pointer at or past image_blocks is
+ * reported as it stands (the read gives it 9).
+ * ppfs_ecc_read_file_*: ppfs_ecc_file_span's checks, the walk, then the extent read of FileIO::readFile's
+ * shape: the first block from offset % ds, the last one up to where the bytes run out.
+ *   out           out[0, clamped_bytes) is the file range; out_bytes >= clamped_bytes (-EINVAL otherwise);
+ *                 bytes past clamped_bytes are not written
+ *   status        (may be NULL) one byte per file block touched: the path status where that is non-zero,
+ *                 else the read's 0 / 1 / 5 / 9.  The range of a block with status 5 is zero-filled (a failed
+ *                 read, or a failed index block above it); a block with status 9 is not written
+ *   counts        both halves: the file blocks by final status, the tree blocks as above
+ *   write_back    applies to index and data blocks
+ * Batch semantics: every block of the range is attempted; the reference stops at the first failure (the
+ * adapters restore that result).  Shortened RS (n < 255): blocks are decoded independently and a spill is
+ * dropped, as in every list call.  Repeated pointers (a corrupt or hand-made tree): the calls stay
+ * memory-safe and results follow the repeated-index rules of ppfs_ecc_decode_list_*.
+ * Errors: -EINVAL, checked before anything touches the GPU, for a null ctx, file, image or required
+ * buffer, a misaligned index array or counts record, and blocks at or past ceil(file_size / ds) or the
+ * capacity (so any block >= 12 when ds < 4).  nblocks == 0 / nbytes == 0 returns 0 with zeroed counts.
+ * Device forms: up to three ppfs_ecc_decode_list_device calls (levels A, B, C) write payloads and statuses
+ * into scratch, an expansion kernel runs after each, and the data blocks go through
+ * ppfs_ecc_read_extents_device from extents built on the device, in pieces of 32 Ki file blocks.  The call
+ * never synchronises `stream` and reads nothing back.  The scratch is the context's scrub scratch (see
+ * ppfs_ecc_scrub_allocated_device: pool memory made on the context's stream, shared by all streams, each
+ * call waits for the previous user, nothing is allocated or freed on the caller's stream): per tree block
+ * ds + 6 bytes, every level rounded up to 16 entries so that the payload and status pointers keep the
+ * 16-byte rule and a context that decodes lists directly keeps doing so -- with T <= about nblocks / ipb
+ * that is some 4 + 6 / ipb bytes per file block -- plus 22 bytes per block of a piece (index, path status,
+ * extent, read status: 704 KiB).  A capturing stream gets PPFS_ECC_ENOTSUP.
+ * Host forms: ppfs_ecc_decode_list_host per level, the same plan on the CPU, ppfs_ecc_read_extents_host, a
+ * CPU tally.
+ */
+typedef struct ppfs_ecc_file { /* 64 bytes: the fields of Inode the walk reads */
+    uint32_t direct[12], indirect, doubly_indirect, trebly_indirect, file_size;
+} ppfs_ecc_file;
+typedef struct ppfs_ecc_file_counts { /* 64 bytes, overwritten by each call */
+    uint64_t ok, corrected, failed, out_of_range;                         /* file blocks, inherited path statuses included */
+    uint64_t index_ok, index_corrected, index_failed, index_out_of_range; /* the tree's own blocks */
+} ppfs_ecc_file_counts;
+
+int ppfs_ecc_file_span(const ppfs_ecc_ctx* ctx, const ppfs_ecc_file* file, uint64_t offset, uint64_t nbytes,
+    uint64_t* first_block, uint64_t* nblocks, uint64_t* clamped_bytes);
+long long ppfs_ecc_file_tree_blocks(const ppfs_ecc_ctx* ctx, const ppfs_ecc_file* file, uint64_t first_block,
+    uint64_t nblocks);
+int ppfs_ecc_file_blocks_device(ppfs_ecc_ctx* ctx, uint8_t* d_image, size_t image_blocks, const ppfs_ecc_file* file,
+    uint64_t first_block, uint64_t nblocks, uint32_t* d_index, uint8_t* d_path_status, uint32_t* d_tree_index,
+    uint8_t* d_tree_status, ppfs_ecc_file_counts* d_counts, int write_back, void* stream);
+int ppfs_ecc_file_blocks_host(ppfs_ecc_ctx* ctx, uint8_t* image, size_t image_blocks, const ppfs_ecc_file* file,
+    uint64_t first_block, uint64_t nblocks, uint32_t* index, uint8_t* path_status, uint32_t* tree_index,
+    uint8_t* tree_status, ppfs_ecc_file_counts* counts, int write_back);
+int ppfs_ecc_read_file_device(ppfs_ecc_ctx* ctx, uint8_t* d_image, size_t image_blocks, const ppfs_ecc_file* file,
+    uint64_t offset, uint64_t nbytes, uint8_t* d_out, size_t out_bytes, uint8_t* d_status, ppfs_ecc_file_counts* d_counts,
+    int write_back, void* stream);
+int ppfs_ecc_read_file_host(ppfs_ecc_ctx* ctx, uint8_t* image, size_t image_blocks, const ppfs_ecc_file* file,
+    uint64_t offset, uint64_t nbytes, uint8_t* out, size_t out_bytes, uint8_t* status, ppfs_ecc_file_counts* counts,
+    int write_back);
+
+/*
  * 2-of-3 bitwise majority of nrec replicated records of rec_bytes each, replacing
  * SuperBlockManager::_performBitVoting (lib/super_block_manager/src/super_block_manager.cpp:133-165):
  *   out[i] = majority(a[i], b[i], c[i]) bit by bit;

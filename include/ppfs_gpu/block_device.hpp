@@ -37,6 +37,8 @@
  * readExtents / writeExtents take byte ranges (block, offset, length) of such blocks -- a file range
  * that starts and ends mid-block (file_extents), or a few bytes of an inode or bitmap block -- again
  * in one engine call.
+ * fileBlocks / readFile take the 64 bytes of an inode that describe its index-block tree (ppfs_ecc_file)
+ * and resolve the tree themselves: FileIO::readFile of any size without the BlockIndexIterator loop.
  */
 #include <algorithm>
 #include <cstddef>
@@ -693,6 +695,144 @@ public:
         }
         return {};
     }
+
+    // File extension (ppfs_ecc.h ppfs_ecc_file_blocks_* / ppfs_ecc_read_file_*): a file read from the 64 bytes of
+    // its inode that describe the index-block tree (inode.hpp:18-41).  These per-block loops are the definition:
+    // the read-only BlockIndexIterator (file_io.cpp:186-463) through readBlock.  An index block is read, as
+    // readBlock({b, 0}, 4 * ipb), immediately before the first requested file block under it, outer levels
+    // first, each one once; the first error ends the walk.  The codecs walk the whole tree in engine calls.
+    //   fileBlocks  idx[i] = the image block of file block first + i.  On an error the call returns it; the
+    //               blocks before the failing one are resolved, err (may be null) holds 0 for them and the
+    //               error from the failing block on.
+    //   readFile    FileIO::readFile (file_io.cpp:12-44): out[0, n) = the file's bytes from offset, n =
+    //               min(bytes_to_read, file_size - offset), which is the value returned.  On an error the call
+    //               returns it; the bytes before the failing block are delivered, *delivered (may be null)
+    //               says how many.
+    struct FilePath {
+        unsigned segment; // 0: direct[slot[0]]; 1, 2, 3: that many index blocks above the block; 4: past the tree
+        uint64_t slot[3]; // the slot taken at each index block, from the root down
+    };
+    static FilePath file_path(uint64_t j, uint64_t ipb)
+    {
+        FilePath p { 4, { 0, 0, 0 } };
+        if (j < 12) {
+            p.segment = 0;
+            p.slot[0] = j;
+            return p;
+        }
+        uint64_t s = j - 12;
+        if (s < ipb) {
+            p.segment = 1;
+            p.slot[0] = s;
+            return p;
+        }
+        s -= ipb;
+        if (s < ipb * ipb) {
+            p.segment = 2;
+            p.slot[0] = s / ipb;
+            p.slot[1] = s % ipb;
+            return p;
+        }
+        s -= ipb * ipb;
+        if (s < ipb * ipb * ipb) {
+            p.segment = 3;
+            p.slot[0] = s / (ipb * ipb);
+            p.slot[1] = (s / ipb) % ipb;
+            p.slot[2] = s % ipb;
+        }
+        return p;
+    }
+    static uint64_t file_occupied(const ppfs_ecc_file& file, size_t ds) { return ds ? ((uint64_t)file.file_size + ds - 1) / ds : 0; }
+    // The iterator: the index block loaded at each depth and which one it is.  File blocks are asked for in
+    // ascending order, so one block per depth is all the walk ever holds.
+    class FileWalk {
+    public:
+        FileWalk(IBlockDevice& dev, const ppfs_ecc_file& file)
+            : _dev(dev)
+            , _file(file)
+            , _ds(dev.dataSize())
+            , _ipb(_ds / 4)
+        {
+        }
+        expected<block_index_t> block(uint64_t j)
+        {
+            const FilePath p = file_path(j, _ipb);
+            if (j >= file_occupied(_file, _ds) || p.segment > 3)
+                return unexpected(FsError::FileIO_OutOfBounds);
+            if (p.segment == 0)
+                return _file.direct[j];
+            block_index_t pointer = p.segment == 1 ? _file.indirect : p.segment == 2 ? _file.doubly_indirect : _file.trebly_indirect;
+            uint64_t id = p.segment; // which index block: the segment and the slots taken so far
+            for (unsigned d = 0; d < p.segment; ++d) {
+                if (!_have[d] || _id[d] != id) {
+                    _entries[d].assign(_ds, 0);
+                    static_vector<uint8_t> v(_entries[d].data(), _ds, 0);
+                    _have[d] = false;
+                    auto r = _dev.readBlock(DataLocation((int)pointer, 0), 4 * _ipb, v);
+                    if (!r)
+                        return unexpected(r.error());
+                    _have[d] = true;
+                    _id[d] = id;
+                }
+                const uint8_t* e = _entries[d].data() + 4 * p.slot[d];
+                pointer = (block_index_t)e[0] | (block_index_t)e[1] << 8 | (block_index_t)e[2] << 16 | (block_index_t)e[3] << 24;
+                id = id * (_ipb + 1) + p.slot[d] + 1;
+            }
+            return pointer;
+        }
+
+    private:
+        IBlockDevice& _dev;
+        const ppfs_ecc_file& _file;
+        size_t _ds, _ipb;
+        bool _have[3] = { false, false, false };
+        uint64_t _id[3] = { 0, 0, 0 };
+        std::vector<uint8_t> _entries[3];
+    };
+    virtual expected<void> fileBlocks(const ppfs_ecc_file& file, uint64_t first, size_t count, block_index_t* idx, uint8_t* err)
+    {
+        FileWalk walk(*this, file);
+        for (size_t i = 0; i < count; ++i) {
+            auto r = walk.block(first + i);
+            if (!r) {
+                if (err)
+                    std::memset(err + i, (int)(uint8_t)r.error(), count - i);
+                return unexpected(r.error());
+            }
+            idx[i] = *r;
+            if (err)
+                err[i] = 0;
+        }
+        return {};
+    }
+    virtual expected<size_t> readFile(const ppfs_ecc_file& file, size_t offset, size_t bytes_to_read, uint8_t* out,
+        size_t* delivered = nullptr)
+    {
+        const size_t ds = dataSize();
+        if (delivered)
+            *delivered = 0;
+        if (bytes_to_read == 0)
+            return (size_t)0;
+        if (ds == 0 || offset >= file.file_size)
+            return unexpected(FsError::FileIO_OutOfBounds);
+        const size_t n = std::min<size_t>(bytes_to_read, file.file_size - offset);
+        FileWalk walk(*this, file);
+        size_t done = 0;
+        for (uint64_t j = offset / ds; done < n; ++j) {
+            auto b = walk.block(j);
+            if (!b)
+                return unexpected(b.error());
+            const size_t off = done == 0 ? offset % ds : 0, len = std::min(ds - off, n - done);
+            static_vector<uint8_t> v(out + done, len, 0);
+            auto r = readBlock(DataLocation((int)*b, (int)off), len, v);
+            if (!r)
+                return unexpected(r.error());
+            done += len;
+            if (delivered)
+                *delivered = done;
+        }
+        return n;
+    }
 };
 
 // The entries of a FileIO::readFile / writeFile walk (file_io.cpp:24-42, 50-88) over the blocks
@@ -1333,7 +1473,151 @@ public:
         return {};
     }
 
+    // The file calls as engine calls on a mapped disk image: the whole tree in one ppfs_ecc_file_blocks_host (at
+    // most three list decodes), for readFile followed by one ppfs_ecc_read_extents_host over the blocks whose
+    // path held.  The result and the bytes equal the loop's; so does the log: each corrected index block's event
+    // comes immediately before the event (if any) of the first requested file block under it, outer levels
+    // first.  On a failing block the error and the byte count equal the loop's; blocks after the failing one may
+    // additionally have been corrected and logged (the one deviation).  Elsewhere, for a shortened RS code and
+    // for a range the loop refuses partway (past the file or the tree), the per-block loop.
+    expected<void> fileBlocks(const ppfs_ecc_file& file, uint64_t first, size_t count, block_index_t* idx, uint8_t* err) override
+    {
+        uint8_t* img = file_image(file, first, count);
+        if (!img)
+            return IBlockDevice::fileBlocks(file, first, count, idx, err);
+        std::vector<uint8_t> path(count);
+        std::vector<FileEvent> events;
+        if (!file_walk(img, file, first, count, idx, path.data(), events))
+            return unexpected(FsError::Disk_IOError);
+        log_in_order(events);
+        size_t bad = 0;
+        while (bad < count && path[bad] == 0)
+            ++bad;
+        if (err) {
+            std::memset(err, 0, bad);
+            if (bad < count)
+                std::memset(err + bad, path[bad], count - bad);
+        }
+        if (bad < count)
+            return unexpected((FsError)path[bad]); // 5 and 9 are BlockDevice_CorrectionError and Disk_OutOfBounds
+        return {};
+    }
+    expected<size_t> readFile(const ppfs_ecc_file& file, size_t offset, size_t bytes_to_read, uint8_t* out,
+        size_t* delivered = nullptr) override
+    {
+        if (bytes_to_read == 0 || _ds == 0 || offset >= file.file_size)
+            return IBlockDevice::readFile(file, offset, bytes_to_read, out, delivered);
+        const size_t n = std::min<size_t>(bytes_to_read, file.file_size - offset);
+        const uint64_t first = offset / _ds;
+        const size_t count = (offset % _ds + n + _ds - 1) / _ds;
+        uint8_t* img = file_image(file, first, count);
+        if (!img)
+            return IBlockDevice::readFile(file, offset, bytes_to_read, out, delivered);
+        std::vector<block_index_t> idx(count);
+        std::vector<uint8_t> path(count), status(count, 0);
+        std::vector<FileEvent> events;
+        if (!file_walk(img, file, first, count, idx.data(), path.data(), events))
+            return unexpected(FsError::Disk_IOError);
+        const std::vector<ppfs_ecc_extent> all = file_extents(idx.data(), count, offset % _ds, n, _ds);
+        std::vector<ppfs_ecc_extent> live;
+        std::vector<size_t> live_at;
+        for (size_t i = 0; i < count; ++i)
+            if (!path[i]) {
+                live.push_back(all[i]);
+                live_at.push_back(i);
+            }
+        if (!live.empty()) {
+            std::vector<uint8_t> st(live.size());
+            const int wb = (_type == PPFS_ECC_REED_SOLOMON || _type == PPFS_ECC_HAMMING) ? 1 : 0;
+            if (!EccEngine::ok(ppfs_ecc_read_extents_host(_eng.ctx(), img, _disk.size() / _raw, live.data(), live.size(), out, n,
+                                   st.data(), wb),
+                    "read file extents"))
+                return unexpected(FsError::Disk_IOError);
+            for (size_t k = 0; k < live.size(); ++k)
+                status[live_at[k]] = st[k];
+        }
+        for (size_t i = 0; i < count; ++i)
+            if (status[i] == PPFS_ECC_CORRECTED)
+                events.push_back(FileEvent { first + i, 3, idx[i] });
+        log_in_order(events);
+        if (delivered)
+            *delivered = n;
+        for (size_t i = 0; i < count; ++i) {
+            const uint8_t e = path[i] ? path[i] : status[i] == PPFS_ECC_CORRECTED ? 0 : status[i];
+            if (e) {
+                if (delivered)
+                    *delivered = (size_t)all[i].pos;
+                return unexpected((FsError)e);
+            }
+        }
+        return n;
+    }
+
 protected:
+    // a corrected block of a file call: the file block it is read before (itself, for a data block), its level
+    // (0-2: the tree's, 3: data) and its image block
+    struct FileEvent {
+        uint64_t at;
+        int level;
+        block_index_t block;
+    };
+    void log_in_order(std::vector<FileEvent>& events)
+    {
+        std::stable_sort(events.begin(), events.end(),
+            [](const FileEvent& a, const FileEvent& b) { return a.at != b.at ? a.at < b.at : a.level < b.level; });
+        for (const FileEvent& e : events)
+            log(e.block);
+    }
+    // the mapped image when the engine walks [first, first + count) of the file, else null
+    uint8_t* file_image(const ppfs_ecc_file& file, uint64_t first, size_t count)
+    {
+        uint8_t* img = _disk.mapped();
+        if (!img || has_spill() || !_raw || !_ds || !count)
+            return nullptr;
+        if (first + count > file_occupied(file, _ds) || file_path(first + count - 1, _ds / 4).segment > 3)
+            return nullptr;
+        return img;
+    }
+    // one engine walk of the tree: the blocks, their path statuses, and the corrected index blocks' events
+    bool file_walk(uint8_t* img, const ppfs_ecc_file& file, uint64_t first, size_t count, block_index_t* idx, uint8_t* path,
+        std::vector<FileEvent>& events)
+    {
+        const long long T = ppfs_ecc_file_tree_blocks(_eng.ctx(), &file, first, count);
+        if (T < 0)
+            return false;
+        std::vector<block_index_t> tidx((size_t)T);
+        std::vector<uint8_t> tst((size_t)T);
+        const int wb = (_type == PPFS_ECC_REED_SOLOMON || _type == PPFS_ECC_HAMMING) ? 1 : 0;
+        if (!EccEngine::ok(ppfs_ecc_file_blocks_host(_eng.ctx(), img, _disk.size() / _raw, &file, first, count, idx, path,
+                               tidx.data(), tst.data(), nullptr, wb),
+                "file blocks"))
+            return false;
+        // the tree's entries in level order (ppfs_ecc.h) with the first requested file block under each: a new
+        // index block at depth d starts where the slots above the block's own change
+        std::vector<uint64_t> under[3];
+        const uint64_t ipb = _ds / 4;
+        FilePath prev { 4, { 0, 0, 0 } };
+        for (uint64_t j = first; j < first + count; ++j) {
+            const FilePath p = file_path(j, ipb);
+            bool fresh = p.segment != prev.segment;
+            for (unsigned d = 0; d < p.segment; ++d) {
+                if (d > 0)
+                    fresh = fresh || p.slot[d - 1] != prev.slot[d - 1];
+                if (fresh)
+                    under[d].push_back(j);
+            }
+            prev = p;
+        }
+        size_t k = 0;
+        for (int d = 0; d < 3; ++d)
+            for (uint64_t j : under[d]) {
+                if (k < (size_t)T && tst[k] == PPFS_ECC_CORRECTED)
+                    events.push_back(FileEvent { j, d, tidx[k] });
+                ++k;
+            }
+        return k == (size_t)T;
+    }
+
     EngineBlockDevice(IDisk& disk, std::shared_ptr<Logger> logger, uint32_t type, uint32_t bs, uint32_t t,
         uint64_t poly, int device, const char* log_name)
         : _disk(disk)

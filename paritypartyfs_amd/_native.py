@@ -57,6 +57,12 @@ EXPORTED_SYMBOLS = (
     "ppfs_ecc_scrub_list_host",
     "ppfs_ecc_scrub_allocated_device",
     "ppfs_ecc_scrub_allocated_host",
+    "ppfs_ecc_file_span",
+    "ppfs_ecc_file_tree_blocks",
+    "ppfs_ecc_file_blocks_device",
+    "ppfs_ecc_file_blocks_host",
+    "ppfs_ecc_read_file_device",
+    "ppfs_ecc_read_file_host",
     "ppfs_vote3_device",
     "ppfs_vote3_host",
     "ppfs_copy_device",
@@ -83,6 +89,10 @@ EXPORTED_SYMBOLS = (
 # in the packed caller buffer
 EXTENT_DTYPE = np.dtype([("pos", "<u8"), ("block", "<u4"), ("offset", "<u2"), ("length", "<u2")])
 
+# ppfs_ecc_file: the 64 bytes of an Inode that the read-only file walk reads
+FILE_DTYPE = np.dtype([("direct", "<u4", (12,)), ("indirect", "<u4"), ("doubly_indirect", "<u4"),
+                       ("trebly_indirect", "<u4"), ("file_size", "<u4")])
+
 
 class EccParams(ctypes.Structure):
     _fields_ = [
@@ -98,6 +108,12 @@ class ScrubCounts(ctypes.Structure):
     """ppfs_ecc_scrub_counts: what a list / allocated scrub found (64 bytes, overwritten by each call)."""
     _fields_ = [(n, c_uint64) for n in ("ok", "corrected", "failed", "out_of_range", "not_allocated", "bitmap_ok",
                                         "bitmap_corrected", "bitmap_failed")]
+
+
+class FileCounts(ctypes.Structure):
+    """ppfs_ecc_file_counts: what a file walk / file read found (64 bytes, overwritten by each call)."""
+    _fields_ = [(n, c_uint64) for n in ("ok", "corrected", "failed", "out_of_range", "index_ok", "index_corrected",
+                                        "index_failed", "index_out_of_range")]
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -217,6 +233,27 @@ def lib() -> ctypes.CDLL:
     L.ppfs_ecc_scrub_allocated_host.restype = c_int
     L.ppfs_ecc_scrub_allocated_host.argtypes = [c_void_p, c_void_p, c_size_t, c_uint32, c_uint32, c_size_t, c_void_p,
                                                 c_void_p, c_void_p]
+    # file walk: span (ctx, file, offset, nbytes, &first, &nblocks, &clamped); tree_blocks (ctx, file, first, nblocks);
+    # blocks (ctx, image, image_blocks, file, first, nblocks, index, path_status, tree_index, tree_status, counts,
+    # write_back[, stream]); read (ctx, image, image_blocks, file, offset, nbytes, out, out_bytes, status, counts,
+    # write_back[, stream])
+    L.ppfs_ecc_file_span.restype = c_int
+    L.ppfs_ecc_file_span.argtypes = [c_void_p, c_void_p, c_uint64, c_uint64, POINTER(c_uint64), POINTER(c_uint64),
+                                     POINTER(c_uint64)]
+    L.ppfs_ecc_file_tree_blocks.restype = c_longlong
+    L.ppfs_ecc_file_tree_blocks.argtypes = [c_void_p, c_void_p, c_uint64, c_uint64]
+    L.ppfs_ecc_file_blocks_device.restype = c_int
+    L.ppfs_ecc_file_blocks_device.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_int, c_void_p]
+    L.ppfs_ecc_file_blocks_host.restype = c_int
+    L.ppfs_ecc_file_blocks_host.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_int]
+    L.ppfs_ecc_read_file_device.restype = c_int
+    L.ppfs_ecc_read_file_device.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_uint64, c_uint64, c_void_p, c_size_t,
+                                            c_void_p, c_void_p, c_int, c_void_p]
+    L.ppfs_ecc_read_file_host.restype = c_int
+    L.ppfs_ecc_read_file_host.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_uint64, c_uint64, c_void_p, c_size_t,
+                                          c_void_p, c_void_p, c_int]
     L.ppfs_vote3_device.restype = c_int
     L.ppfs_vote3_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]
     L.ppfs_copy_device.restype = c_int

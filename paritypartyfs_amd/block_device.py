@@ -14,7 +14,8 @@ write-back and logging order.  Batched ``readBlocks`` / ``writeBlocks`` run a co
 range of blocks through one engine call (the GPU-worthwhile form, SURVEY section 8f-1);
 ``readBlockList`` / ``writeBlockList`` do so for blocks in any order, ``read_extents`` /
 ``write_extents`` for byte ranges (block, offset, length) of them -- a file range built by
-``file_extents``, or a few bytes of an inode or bitmap block.
+``file_extents``, or a few bytes of an inode or bitmap block; ``file_blocks`` / ``read_file``
+take the inode's 64-byte tree record (``FILE_DTYPE``) and resolve the index blocks themselves.
 """
 from __future__ import annotations
 
@@ -25,7 +26,7 @@ from typing import Generic, List, Optional, Tuple, TypeVar
 
 import numpy as np
 
-from ._native import (ECC_CRC, ECC_HAMMING, ECC_NONE, ECC_PARITY, ECC_REED_SOLOMON, EXTENT_DTYPE, STATUS_CORRECTED,
+from ._native import (ECC_CRC, ECC_HAMMING, ECC_NONE, ECC_PARITY, ECC_REED_SOLOMON, EXTENT_DTYPE, FILE_DTYPE, STATUS_CORRECTED,
                       STATUS_CORRECTION_ERROR, STATUS_NOT_ALLOCATED, STATUS_OUT_OF_BOUNDS)
 from .ecc import EccEngine, ScrubCounts
 
@@ -54,6 +55,7 @@ class FsError(enum.IntEnum):  # lib/common/include/ppfs/common/types.hpp:11-80 (
     Disk_OutOfBounds = 9
     Disk_InvalidRequest = 10
     Disk_IOError = 11
+    FileIO_OutOfBounds = 12
 
 
 T = TypeVar("T")
@@ -337,6 +339,86 @@ class IBlockDevice:
             if not r:
                 err[k] = int(r.error())
         return err
+
+    # read a file from its inode (include/ppfs_ecc.h ppfs_ecc_file_blocks_* / ppfs_ecc_read_file_*): `file` is one
+    # record of FILE_DTYPE.  The per-block loops are the definition -- the read-only BlockIndexIterator
+    # (file_io.cpp:186-463) through readBlock: an index block is read, as readBlock({b, 0}, 4 ipb), immediately
+    # before the first requested file block under it, outer levels first, each one once; the first error ends the
+    # walk.  The codecs override both with engine calls on the whole tree.
+    def _file_walk(self, file, first: int, count: int):
+        """Yields the image block of file blocks first, first + 1, ... or, once and last, the FsError that ends the walk."""
+        f = np.asarray(file).reshape(-1)[0]
+        ds = self.dataSize()
+        ipb = ds // 4
+        occupied = -(-int(f["file_size"]) // ds) if ds else 0
+        loaded = {}
+        for j in range(first, first + count):
+            p = file_path_of(j, ipb)
+            if j >= occupied or p is None:
+                yield FsError.FileIO_OutOfBounds
+                return
+            if p[0] == 0:
+                yield int(f["direct"][j])
+                continue
+            pointer = int(f[("indirect", "doubly_indirect", "trebly_indirect")[p[0] - 1]])
+            for d in range(1, len(p)):
+                node = p[:d]
+                if node not in loaded:
+                    r = self.readBlock(DataLocation(pointer, 0), 4 * ipb)
+                    if not r:
+                        yield r.error()
+                        return
+                    loaded[node] = np.frombuffer(r.value(), dtype="<u4")
+                pointer = int(loaded[node][p[d]])
+            yield pointer
+
+    def file_blocks(self, file, first: int, count: int) -> Tuple[np.ndarray, Optional[FsError]]:
+        """The image blocks of file blocks [first, first + count): (those resolved before the first error, that
+        error or None)."""
+        out = []
+        for v in self._file_walk(file, first, count):
+            if isinstance(v, FsError):
+                return np.array(out, dtype=np.uint32), v
+            out.append(v)
+        return np.array(out, dtype=np.uint32), None
+
+    def read_file(self, file, offset: int, bytes_to_read: int) -> Tuple[bytes, Optional[FsError]]:
+        """FileIO::readFile (file_io.cpp:12-44): (the bytes delivered before the first error, that error or None)."""
+        f = np.asarray(file).reshape(-1)[0]
+        size, ds = int(f["file_size"]), self.dataSize()
+        if bytes_to_read <= 0:
+            return b"", None
+        if offset >= size or ds == 0:
+            return b"", FsError.FileIO_OutOfBounds
+        n = min(bytes_to_read, size - offset)
+        first, count = offset // ds, (offset % ds + n + ds - 1) // ds
+        out = bytearray()
+        for k, v in enumerate(self._file_walk(file, first, count)):
+            if isinstance(v, FsError):
+                return bytes(out), v
+            off = offset % ds if k == 0 else 0
+            r = self.readBlock(DataLocation(v, off), min(ds - off, n - len(out)))
+            if not r:
+                return bytes(out), r.error()
+            out += r.value()
+        return bytes(out), None
+
+
+def file_path_of(j: int, ipb: int):
+    """Where file block j lies in an inode's tree (inode.hpp:18-41): (segment, slot at each index block from the
+    root down), segment 0 = direct[j]; None past the tree's 12 + ipb + ipb^2 + ipb^3 blocks."""
+    if j < 12:
+        return (0, j)
+    s = j - 12
+    if s < ipb:
+        return (1, s)
+    s -= ipb
+    if s < ipb * ipb:
+        return (2, s // ipb, s % ipb)
+    s -= ipb * ipb
+    if s < ipb ** 3:
+        return (3, s // (ipb * ipb), (s // ipb) % ipb, s % ipb)
+    return None
 
 
 def file_extents(indices, offset_in_first_block: int, nbytes: int, data_size: int) -> np.ndarray:
@@ -717,6 +799,84 @@ class _EngineDevice(IBlockDevice):
         status = np.zeros(len(ext), dtype=np.uint8)
         self._engine.write_extents_host(data, image, np.ascontiguousarray(ext), status)
         return self._extent_errors(ext, status)
+
+    def _file_engine_walk(self, image, file, first: int, count: int):
+        """One engine walk of the tree on the mapped image: (image blocks, path statuses, the corrected blocks'
+        events as (first file block under the index block, level, block))."""
+        eng = self._engine
+        wb = eng.ecc_type in (ECC_REED_SOLOMON, ECC_HAMMING)
+        T = eng.file_tree_blocks(file, first, count)
+        ix, ps = np.zeros(count, dtype=np.uint32), np.zeros(count, dtype=np.uint8)
+        ti, ts = np.zeros(T, dtype=np.uint32), np.zeros(T, dtype=np.uint8)
+        eng.file_blocks_host(image, file, first, count, ix, ps, ti, ts, write_back=wb)
+        # the tree entries in level order (file_plan.hpp) with the first requested file block under each
+        ipb, levels = self._ds // 4, [{}, {}, {}]
+        for j in range(first, first + count):
+            p = file_path_of(j, ipb)
+            for d in range(p[0]):
+                levels[d].setdefault(p[:d + 1], j)
+        under = [(j, d) for d, lv in enumerate(levels) for j in lv.values()]
+        events = [(j, d, int(ti[k])) for k, (j, d) in enumerate(under) if ts[k] == STATUS_CORRECTED]
+        return ix, ps, events
+
+    def _file_image(self, file, first: int, count: int):
+        """The mapped image when the engine walks this range, None when the per-block loop does: no mapped disk, a
+        shortened RS code, or a range the loop refuses partway."""
+        image = self._mapped_image()
+        f = np.asarray(file).reshape(-1)[0]
+        if image is None or count <= 0 or self._ds == 0:
+            return None
+        if first + count > -(-int(f["file_size"]) // self._ds) or file_path_of(first + count - 1, self._ds // 4) is None:
+            return None
+        return image
+
+    def file_blocks(self, file, first: int, count: int) -> Tuple[np.ndarray, Optional[FsError]]:
+        """IBlockDevice.file_blocks in one engine call (EccEngine.file_blocks_host) on the disk image.  The result
+        and the log up to the first failing index block equal the loop's; index blocks after it may additionally
+        have been corrected and logged."""
+        file = np.ascontiguousarray(file, dtype=FILE_DTYPE).reshape(1)
+        image = self._file_image(file, first, count)
+        if image is None:
+            return super().file_blocks(file, first, count)
+        ix, ps, events = self._file_engine_walk(image, file, first, count)
+        for _, _, block in sorted(events, key=lambda e: e[:2]):
+            self._log(block)
+        bad = np.nonzero(ps)[0]
+        if bad.size:
+            return ix[:int(bad[0])].copy(), FsError(int(ps[bad[0]]))
+        return ix, None
+
+    def read_file(self, file, offset: int, bytes_to_read: int) -> Tuple[bytes, Optional[FsError]]:
+        """IBlockDevice.read_file as engine calls on the disk image: the tree walk (EccEngine.file_blocks_host), then
+        the blocks' byte ranges (EccEngine.read_extents_host).  The bytes, the error and the log up to the first
+        failing block equal the loop's; blocks after it may additionally have been corrected and logged."""
+        file = np.ascontiguousarray(file, dtype=FILE_DTYPE).reshape(1)
+        size, ds = int(file["file_size"][0]), self._ds
+        if bytes_to_read <= 0 or ds == 0 or offset >= size:
+            return super().read_file(file, offset, bytes_to_read)
+        n = min(bytes_to_read, size - offset)
+        first, count = offset // ds, (offset % ds + n + ds - 1) // ds
+        image = self._file_image(file, first, count)
+        if image is None:
+            return super().read_file(file, offset, bytes_to_read)
+        ix, ps, events = self._file_engine_walk(image, file, first, count)
+        live = np.nonzero(ps == 0)[0]
+        ext = file_extents(ix, offset % ds, n, ds)
+        out, st = np.zeros(n, dtype=np.uint8), np.zeros(count, dtype=np.uint8)
+        if live.size:
+            st_live = np.zeros(live.size, dtype=np.uint8)
+            wb = self._engine.ecc_type in (ECC_REED_SOLOMON, ECC_HAMMING)
+            self._engine.read_extents_host(image, np.ascontiguousarray(ext[live]), out, st_live, write_back=wb)
+            st[live] = st_live
+        events += [(first + int(k), 3, int(ix[k])) for k in np.nonzero(st == STATUS_CORRECTED)[0]]
+        for _, _, block in sorted(events, key=lambda e: e[:2]):
+            self._log(block)
+        final = np.where(ps != 0, ps, np.where(st == STATUS_CORRECTED, 0, st))
+        bad = np.nonzero(final)[0]
+        if bad.size:
+            k = int(bad[0])
+            return out[:int(ext["pos"][k])].tobytes(), FsError(int(final[k]))
+        return out.tobytes(), None
 
     def readBlock(self, loc: DataLocation, bytes_to_read: int, capacity: Optional[int] = None) -> Expected[bytes]:
         if capacity is not None and capacity < bytes_to_read:

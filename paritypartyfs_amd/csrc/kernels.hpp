@@ -1,14 +1,15 @@
 // kernels.hpp -- the host-callable launchers of the kernel translation units, declared once:
 // rs_kernels.hip (Reed-Solomon and its servers), bit_kernels.hip (CRC, Hamming, parity and the bit
-// server) vote.hip (vote, copy, gather, patch list, inject, flag, block lists) and alloc_scan.hip (bitmap
-// expansion, scrub tally).  The
+// server) vote.hip (vote, copy, gather, patch list, inject, flag, block lists), alloc_scan.hip (bitmap
+// expansion, scrub tally) and file_walk.hip (the file walk's expansion, extents and merge).  The
 // three table-sizing functions are in host_tables.hpp, beside the builders that use them.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/ppfs_ecc.h" // ppfs_ecc_extent
+#include "../../include/ppfs_ecc.h" // ppfs_ecc_extent, ppfs_ecc_file
+#include "file_plan.hpp"
 #include "server_box.hpp"
 
 extern "C" {
@@ -89,4 +90,20 @@ hipError_t ppfs_alloc_expand_launch(const uint8_t* stream, const uint8_t* bstatu
 hipError_t ppfs_alloc_iota_launch(uint32_t* index, uint32_t first, uint64_t n, hipStream_t s);
 hipError_t ppfs_scrub_tally_launch(const uint8_t* st, const uint32_t* index, uint64_t n, uint32_t first, uint8_t* status_out,
     uint64_t out_n, unsigned long long* counts, int slot0, int ncat, hipStream_t s);
+// the read-only file walk (file_path.cpp; file_walk.hip, arithmetic in file_plan.hpp).  file and tree are
+// host pointers, passed to the kernels by value; payload / st / inh: the tree's scratch, fileplan::tree_slots
+// entries (ds bytes, 1 and 1 byte each).
+// expand: entries [k0, k0 + n) of a level -> pointer[i] (4-byte aligned) and inherited[i], either may be null.
+// extents: the ppfs_ecc_extent entries (8-byte aligned) of blocks [i0, i0 + n) of a read of `bytes` bytes that
+// starts at payload byte off0 of its first block; NO_BLOCK where path[i] != 0.
+// merge: status_out[i] = path[i] ? path[i] : read[i] (read null: 0); pointer_out[i] = pointer_in[i]; out's range of
+// a block with path status 5 zero-filled; counts[slot0 + slot] (slot0: fileplan::SLOT_FILE / SLOT_INDEX).
+hipError_t ppfs_file_expand_launch(const ppfs_ecc_file* file, const ppfs::fileplan::Tree* tree, int level, uint64_t k0, uint64_t n,
+    uint64_t ds, const uint8_t* payload, const uint8_t* st, const uint8_t* inh, uint32_t* pointer, uint8_t* inherited,
+    hipStream_t s);
+hipError_t ppfs_file_extents_launch(const uint32_t* pointer, const uint8_t* path, uint64_t i0, uint64_t n, uint64_t off0,
+    uint64_t bytes, uint64_t ds, ppfs_ecc_extent* ext, hipStream_t s);
+hipError_t ppfs_file_merge_launch(const uint8_t* path, const uint8_t* read, uint64_t n, uint8_t* status_out,
+    const uint32_t* pointer_in, uint32_t* pointer_out, uint8_t* out, uint64_t i0, uint64_t off0, uint64_t bytes, uint64_t ds,
+    unsigned long long* counts, int slot0, hipStream_t s);
 }

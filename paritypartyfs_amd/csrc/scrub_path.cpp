@@ -64,11 +64,26 @@ int alloc_args(const ppfs_ecc_ctx* c, const void* image, size_t image_blocks, ui
 
 size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// the host form's view of the decoded bitmap (alloc_plan.hpp Src)
+struct HostSrc {
+    const uint8_t* stream;
+    const uint8_t* bstatus;
+    uint32_t dword(uint64_t w) const
+    {
+        const uint8_t* p = stream + 4u * w;
+        return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+    }
+    uint32_t byte(uint64_t i) const { return stream[i]; }
+    uint32_t status(uint64_t b) const { return bstatus[b]; }
+};
+
+} // namespace
+
 // The context's scrub scratch, at least `bytes` of it, for work queued on s.  It is the context's own
 // memory, like the list staging: made (or replaced by a larger one; the old one stays until destroy,
 // since queued work may still read it) on the context's stream, and shared by all streams, so the call
 // first waits for the previous call that used it.  No call allocates or frees on the caller's stream.
-int scrub_scratch(ppfs_ecc_ctx* c, size_t bytes, hipStream_t s, uint8_t** out)
+int ppfs::scrub_scratch(ppfs_ecc_ctx* c, size_t bytes, hipStream_t s, uint8_t** out)
 {
     if (!c->scrub_ev)
         HIP_TRY(hipEventCreateWithFlags(&c->scrub_ev, hipEventDisableTiming), "scrub event");
@@ -86,7 +101,7 @@ int scrub_scratch(ppfs_ecc_ctx* c, size_t bytes, hipStream_t s, uint8_t** out)
     return 0;
 }
 // after the call's last use of the scratch was queued on s (also after a failure)
-void scrub_scratch_used(ppfs_ecc_ctx* c, hipStream_t s)
+void ppfs::scrub_scratch_used(ppfs_ecc_ctx* c, hipStream_t s)
 {
     if (hipEventRecord(c->scrub_ev, s) == hipSuccess) {
         c->scrub_ev_rec = true;
@@ -96,21 +111,6 @@ void scrub_scratch_used(ppfs_ecc_ctx* c, hipStream_t s)
         c->scrub_ev_rec = false;
     }
 }
-
-// the host form's view of the decoded bitmap (alloc_plan.hpp Src)
-struct HostSrc {
-    const uint8_t* stream;
-    const uint8_t* bstatus;
-    uint32_t dword(uint64_t w) const
-    {
-        const uint8_t* p = stream + 4u * w;
-        return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
-    }
-    uint32_t byte(uint64_t i) const { return stream[i]; }
-    uint32_t status(uint64_t b) const { return bstatus[b]; }
-};
-
-} // namespace
 
 // ---------------------------------------------------------------------------------------
 // List scrub

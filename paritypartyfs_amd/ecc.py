@@ -389,12 +389,126 @@ class EccEngine:
                                                   int(nbits), _ptr(status), _ptr(bitmap_status), byref(rec)))
         return ScrubCounts(*[int(getattr(rec, f)) for f in SCRUB_COUNT_FIELDS])
 
+    # ---------------- read a file from its inode (ppfs_ecc_file_*, ppfs_ecc_read_file_*) ----------------
+    # `file` is the 64-byte record of _native.FILE_DTYPE (direct[12], indirect, doubly_indirect, trebly_indirect,
+    # file_size), always in host memory.  The walk resolves the index-block tree on the GPU: at most three list
+    # decodes with an expansion between them; read_file then reads the range like FileIO::readFile.
+    @staticmethod
+    def _file(file) -> np.ndarray:
+        f = np.ascontiguousarray(file)
+        if f.dtype != _native.FILE_DTYPE or f.size != 1:
+            raise ValueError("file: one record of FILE_DTYPE")
+        return f.reshape(1)
+
+    def file_span(self, file, offset: int, nbytes: int):
+        """(first file block, blocks, bytes delivered) of readFile(offset, nbytes) (ppfs_ecc_file_span)."""
+        f = self._file(file)
+        a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().ppfs_ecc_file_span(self._h, f.ctypes.data, int(offset), int(nbytes), byref(a), byref(b), byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
+    def file_tree_blocks(self, file, first_block: int, nblocks: int) -> int:
+        """Index blocks a walk over [first_block, first_block + nblocks) visits (ppfs_ecc_file_tree_blocks)."""
+        f = self._file(file)
+        t = int(lib().ppfs_ecc_file_tree_blocks(self._h, f.ctypes.data, int(first_block), int(nblocks)))
+        if t < 0:
+            check(t)
+        return t
+
+    def _file_blocks_check(self, kind, image, file, first_block, nblocks, index, path_status, tree_index, tree_status):
+        f = self._file(file)
+        if image is None:
+            raise ValueError("image: required")
+        if first_block < 0 or nblocks < 0:
+            raise ValueError("first_block and nblocks must be >= 0")
+        t = self.file_tree_blocks(f, first_block, nblocks)
+        _need("image", image, 0, kind)
+        _need("path_status", path_status, nblocks, kind)
+        _need("tree_status", tree_status, t, kind)
+        _ptr(image), _ptr(path_status), _ptr(tree_status)  # contiguous uint8
+        for name, x, n in (("index", index, nblocks), ("tree_index", tree_index, t)):
+            if x is None:
+                continue
+            if kind == "device":
+                import torch
+
+                if isinstance(x, np.ndarray) or not getattr(x, "is_cuda", False) or x.dtype != torch.int32 \
+                        or not x.is_contiguous() or x.dim() != 1 or x.numel() < n:
+                    raise ValueError(f"{name}: a contiguous 1-D CUDA torch.int32 tensor of >= {n} elements (read as unsigned)")
+            elif not isinstance(x, np.ndarray) or x.dtype != np.uint32 or not x.flags["C_CONTIGUOUS"] or x.ndim != 1 \
+                    or x.size < n:
+                raise ValueError(f"{name}: a C-contiguous 1-D numpy uint32 array of >= {n} elements")
+        return f, _size(image) // self.raw_block_size
+
+    def file_blocks(self, image, file, first_block: int, nblocks: int, index=None, path_status=None, tree_index=None,
+                    tree_status=None, counts=None, write_back: bool = True, stream=None):
+        """Device walk (ppfs_ecc_file_blocks_device).  counts: None, True (returns a fresh CUDA int64 tensor of the
+        eight fields of FILE_COUNT_FIELDS; read it after synchronising) or such a tensor.  Never synchronises."""
+        f, blocks = self._file_blocks_check("device", image, file, first_block, nblocks, index, path_status, tree_index,
+                                            tree_status)
+        d_counts = self._device_counts(counts)
+        check(lib().ppfs_ecc_file_blocks_device(
+            self._h, _ptr(image), blocks, f.ctypes.data, int(first_block), int(nblocks),
+            None if index is None else self._index_ptr(index), _ptr(path_status),
+            None if tree_index is None else self._index_ptr(tree_index), _ptr(tree_status),
+            None if d_counts is None else d_counts.data_ptr(), int(bool(write_back)), _stream_handle(stream)))
+        return d_counts
+
+    def file_blocks_host(self, image: np.ndarray, file, first_block: int, nblocks: int, index=None, path_status=None,
+                         tree_index=None, tree_status=None, write_back: bool = True) -> "FileCounts":
+        f, blocks = self._file_blocks_check("host", image, file, first_block, nblocks, index, path_status, tree_index,
+                                            tree_status)
+        rec = _native.FileCounts()
+        check(lib().ppfs_ecc_file_blocks_host(
+            self._h, _ptr(image), blocks, f.ctypes.data, int(first_block), int(nblocks),
+            None if index is None else self._index_ptr(index), _ptr(path_status),
+            None if tree_index is None else self._index_ptr(tree_index), _ptr(tree_status), byref(rec),
+            int(bool(write_back))))
+        return FileCounts(*[int(getattr(rec, n)) for n in FILE_COUNT_FIELDS])
+
+    def _read_file_check(self, kind, image, file, offset, nbytes, out, status):
+        f = self._file(file)
+        if image is None:
+            raise ValueError("image: required")
+        if offset < 0 or nbytes < 0:
+            raise ValueError("offset and nbytes must be >= 0")
+        _, nblocks, clamped = self.file_span(f, offset, nbytes)
+        _need("image", image, 0, kind)
+        _need("out", out, clamped, kind)
+        _need("status", status, nblocks, kind)
+        _ptr(image), _ptr(out), _ptr(status)  # contiguous uint8
+        return f, _size(image) // self.raw_block_size, 0 if out is None else _size(out)
+
+    def read_file(self, image, file, offset: int, nbytes: int, out, status=None, counts=None, write_back: bool = True,
+                  stream=None):
+        """Device file read (ppfs_ecc_read_file_device): out[0, clamped) = the file range; status: one byte per file
+        block touched; counts as in file_blocks.  Never synchronises."""
+        f, blocks, out_bytes = self._read_file_check("device", image, file, offset, nbytes, out, status)
+        d_counts = self._device_counts(counts)
+        check(lib().ppfs_ecc_read_file_device(self._h, _ptr(image), blocks, f.ctypes.data, int(offset), int(nbytes), _ptr(out),
+                                              out_bytes, _ptr(status), None if d_counts is None else d_counts.data_ptr(),
+                                              int(bool(write_back)), _stream_handle(stream)))
+        return d_counts
+
+    def read_file_host(self, image: np.ndarray, file, offset: int, nbytes: int, out: Optional[np.ndarray],
+                       status: Optional[np.ndarray] = None, write_back: bool = True) -> "FileCounts":
+        f, blocks, out_bytes = self._read_file_check("host", image, file, offset, nbytes, out, status)
+        rec = _native.FileCounts()
+        check(lib().ppfs_ecc_read_file_host(self._h, _ptr(image), blocks, f.ctypes.data, int(offset), int(nbytes), _ptr(out),
+                                            out_bytes, _ptr(status), byref(rec), int(bool(write_back))))
+        return FileCounts(*[int(getattr(rec, n)) for n in FILE_COUNT_FIELDS])
+
 
 # ppfs_ecc_scrub_counts: the host forms return it as this tuple, the device forms as a CUDA int64 tensor
 # in the same field order (ScrubCounts(*tensor.tolist()) after synchronising)
 SCRUB_COUNT_FIELDS = ("ok", "corrected", "failed", "out_of_range", "not_allocated", "bitmap_ok", "bitmap_corrected",
                       "bitmap_failed")
 ScrubCounts = collections.namedtuple("ScrubCounts", SCRUB_COUNT_FIELDS)
+# ppfs_ecc_file_counts, likewise
+FILE_COUNT_FIELDS = ("ok", "corrected", "failed", "out_of_range", "index_ok", "index_corrected", "index_failed",
+                     "index_out_of_range")
+FileCounts = collections.namedtuple("FileCounts", FILE_COUNT_FIELDS)
+FILE_DTYPE = _native.FILE_DTYPE
 
 
 class EccGroup:
@@ -541,4 +655,4 @@ def crc_implicit_to_explicit(p: int) -> int:
     return int(lib().ppfs_ecc_crc_implicit_to_explicit(ctypes.c_uint64(p)))
 
 
-__all__ = ["EccEngine", "ScrubCounts", "SCRUB_COUNT_FIELDS", "crc_implicit_to_explicit", "device_copy", "inject_bytes", "pinned", "vote3", "vote3_host", "_native"]
+__all__ = ["EccEngine", "ScrubCounts", "SCRUB_COUNT_FIELDS", "FileCounts", "FILE_COUNT_FIELDS", "FILE_DTYPE", "crc_implicit_to_explicit", "device_copy", "inject_bytes", "pinned", "vote3", "vote3_host", "_native"]
