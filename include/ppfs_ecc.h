@@ -474,6 +474,89 @@ int ppfs_ecc_read_file_host(ppfs_ecc_ctx* ctx, uint8_t* image, size_t image_bloc
     int write_back);
 
 /*
+ * Read many files in one call: the walk above over a BATCH of inodes.  A
+ * filesystem is mostly small files -- a directory is one -- and the single-file calls' cost is almost all
+ * fixed.  Level A of all the files is one list, level B one list, level C one list and the data blocks one
+ * extent stream, so a batch of any number of files costs the launches of one file.
+ *
+ * A batch is `nfiles` records (`files`, a HOST pointer in both forms) and `ranges`: NULL, or nfiles
+ * (offset, nbytes) pairs, range f being readFile(offset, nbytes) of file f.  NULL means every file whole,
+ * (0, file_size); an empty file is then a valid empty range.
+ *
+ * ppfs_ecc_files_plan: where each file's results lie.  Pure arithmetic, no GPU.  slots (may be NULL):
+ * nfiles records; totals (may be NULL).
+ *   first_block, blocks, bytes   ppfs_ecc_file_span of the file's range
+ *   block_pos    its entries in the per-block arrays are [block_pos, block_pos + blocks), files back to back
+ *                in batch order
+ *   out_pos      its bytes in `out` are [out_pos, out_pos + bytes), files back to back, no padding
+ *   tree_pos[3], tree_n[3]   its entries of levels A, B, C in the tree arrays, which are LEVEL-MAJOR: all
+ *                files' level A entries in batch order, then all level B, then all level C; within one
+ *                file's level the order is the single-file call's
+ *   totals       blocks, bytes, tree entries per level, and their sum tree_blocks
+ * -EINVAL, with the file's number in ppfs_ecc_last_error, for any range ppfs_ecc_file_span rejects: an
+ * offset at or past the file's end with nbytes > 0, blocks past the tree's capacity.
+ *
+ * ppfs_ecc_files_blocks_*: ppfs_ecc_file_blocks_* of every file's range.  index / path_status: totals.blocks
+ * entries; tree_index / tree_status: totals.tree_blocks entries; counts: ONE record for the whole batch.
+ *   file_flags   (may be NULL, 4-byte aligned) one uint32 per file, an OR over its blocks: bit 0 = some
+ *                data block corrected (1), bit 1 = failed (5), bit 2 = out of range (9); bits 8-10 the
+ *                same for its index blocks.  0 = the file is intact.
+ * Every output may be NULL as in the single-file call.
+ * ppfs_ecc_read_files_*: the same walk, then the read.  out[out_pos, out_pos + bytes) is file f's range;
+ * out_bytes >= totals.bytes (-EINVAL otherwise); status: one byte per file block touched, the path status
+ * where non-zero, else the read's; file_flags from those final statuses.  Per block the single-file rules
+ * hold: the range of a block under a failed index block (5) is zero-filled, its own range only; a block
+ * with status 9 is not written; nothing of `out` outside the files' ranges is written.  A payload above
+ * 65,535 bytes is -EINVAL.
+ *
+ * Semantics: exactly the single-file call applied to each file.  Files whose trees and data blocks are
+ * disjoint -- any consistent filesystem -- get bit for bit what one ppfs_ecc_read_file_* /
+ * ppfs_ecc_file_blocks_* per file gives: bytes, statuses, the image after write-back, and (summed) the
+ * counts.  The same inode listed twice, or trees that share blocks (hard links, a corrupt image), stay
+ * memory-safe; a block named more than once in a merged level falls under the repeated-index rules of
+ * ppfs_ecc_decode_list_* (identical results for every copy of a clean block; with write-back, which copy's
+ * correction lands last is unspecified).
+ * One bad range fails the whole call with -EINVAL before anything touches the GPU, as do a null ctx, files
+ * (nfiles > 0), image or required buffer and a misaligned index array, flags array or counts record.
+ * nfiles == 0, or ranges that are all empty, returns 0 after clearing the counts and the flags.
+ * Device forms: never synchronise `stream`, read nothing back, PPFS_ECC_ENOTSUP on a capturing stream.  The
+ * host-built tables (128 bytes per file and up to four 16-byte rows) are staged in page-locked memory,
+ * copied on `stream` into the call's share of the scrub scratch, and the staging buffer goes back to the
+ * cache only after an event behind that copy has completed (checked at later batch calls and at destroy).
+ * Per level A, B, C over the whole batch: one expansion kernel, one ppfs_ecc_decode_list_device, one merge
+ * kernel; per piece of 32 Ki merged file blocks, cut regardless of file boundaries: expansion, extents,
+ * ppfs_ecc_read_extents_device, merge.  The launch count does not depend on nfiles.
+ * Host forms: the same merged plan on the CPU around three ppfs_ecc_decode_list_host calls and one
+ * ppfs_ecc_read_extents_host.
+ */
+typedef struct ppfs_ecc_file_range {
+    uint64_t offset, nbytes;
+} ppfs_ecc_file_range;
+typedef struct ppfs_ecc_files_slot { /* 88 bytes */
+    uint64_t first_block, blocks, bytes;
+    uint64_t block_pos, out_pos;
+    uint64_t tree_pos[3], tree_n[3];
+} ppfs_ecc_files_slot;
+typedef struct ppfs_ecc_files_totals { /* 48 bytes */
+    uint64_t blocks, bytes, tree_level[3], tree_blocks;
+} ppfs_ecc_files_totals;
+
+int ppfs_ecc_files_plan(const ppfs_ecc_ctx* ctx, const ppfs_ecc_file* files, const ppfs_ecc_file_range* ranges,
+    size_t nfiles, ppfs_ecc_files_slot* slots, ppfs_ecc_files_totals* totals);
+int ppfs_ecc_files_blocks_device(ppfs_ecc_ctx* ctx, uint8_t* d_image, size_t image_blocks, const ppfs_ecc_file* files,
+    const ppfs_ecc_file_range* ranges, size_t nfiles, uint32_t* d_index, uint8_t* d_path_status, uint32_t* d_tree_index,
+    uint8_t* d_tree_status, uint32_t* d_file_flags, ppfs_ecc_file_counts* d_counts, int write_back, void* stream);
+int ppfs_ecc_files_blocks_host(ppfs_ecc_ctx* ctx, uint8_t* image, size_t image_blocks, const ppfs_ecc_file* files,
+    const ppfs_ecc_file_range* ranges, size_t nfiles, uint32_t* index, uint8_t* path_status, uint32_t* tree_index,
+    uint8_t* tree_status, uint32_t* file_flags, ppfs_ecc_file_counts* counts, int write_back);
+int ppfs_ecc_read_files_device(ppfs_ecc_ctx* ctx, uint8_t* d_image, size_t image_blocks, const ppfs_ecc_file* files,
+    const ppfs_ecc_file_range* ranges, size_t nfiles, uint8_t* d_out, size_t out_bytes, uint8_t* d_status,
+    uint32_t* d_file_flags, ppfs_ecc_file_counts* d_counts, int write_back, void* stream);
+int ppfs_ecc_read_files_host(ppfs_ecc_ctx* ctx, uint8_t* image, size_t image_blocks, const ppfs_ecc_file* files,
+    const ppfs_ecc_file_range* ranges, size_t nfiles, uint8_t* out, size_t out_bytes, uint8_t* status,
+    uint32_t* file_flags, ppfs_ecc_file_counts* counts, int write_back);
+
+/*
  * 2-of-3 bitwise majority of nrec replicated records of rec_bytes each, replacing
  * SuperBlockManager::_performBitVoting (lib/super_block_manager/src/super_block_manager.cpp:133-165):
  *   out[i] = majority(a[i], b[i], c[i]) bit by bit;

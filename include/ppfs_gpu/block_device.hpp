@@ -39,6 +39,8 @@
  * in one engine call.
  * fileBlocks / readFile take the 64 bytes of an inode that describe its index-block tree (ppfs_ecc_file)
  * and resolve the tree themselves: FileIO::readFile of any size without the BlockIndexIterator loop.
+ * readFiles does that for a batch of (inode, offset, length) -- a directory scan, a backup -- with all the
+ * files' trees walked in one engine call.
  */
 #include <algorithm>
 #include <cstddef>
@@ -833,6 +835,32 @@ public:
         }
         return n;
     }
+
+    // Batch extension (ppfs_ecc.h ppfs_ecc_files_blocks_* / ppfs_ecc_read_files_*): many (inode, offset, length)
+    // in one call -- a directory scan, a backup.  By definition the loop over readFile, in batch order; the
+    // codecs walk all the files' trees in one engine call.  Per read: ok and `bytes` (the value readFile
+    // returns) or `error`, and `delivered` as readFile reports it.
+    struct FileRead {
+        ppfs_ecc_file file;
+        size_t offset, bytes_to_read;
+        uint8_t* out; // room for min(bytes_to_read, file_size - offset) bytes
+        bool ok;
+        FsError error;
+        size_t bytes, delivered;
+    };
+    virtual void readFiles(FileRead* reads, size_t n)
+    {
+        for (size_t i = 0; i < n; ++i)
+            read_one(reads[i], readFile(reads[i].file, reads[i].offset, reads[i].bytes_to_read, reads[i].out, &reads[i].delivered));
+    }
+
+protected:
+    static void read_one(FileRead& r, const expected<size_t>& got)
+    {
+        r.ok = (bool)got;
+        r.error = got ? FsError {} : got.error();
+        r.bytes = got ? *got : 0;
+    }
 };
 
 // The entries of a FileIO::readFile / writeFile walk (file_io.cpp:24-42, 50-88) over the blocks
@@ -1553,6 +1581,117 @@ public:
         return n;
     }
 
+    // readFiles as two engine calls on a mapped disk image: one ppfs_ecc_files_blocks_host over all the files'
+    // trees (at most three list decodes whatever the number of files), one ppfs_ecc_read_extents_host over the
+    // blocks whose path held.  Per file the result, the bytes and the log are readFile's, stop-at-first-failure
+    // included; files are logged in batch order; blocks after a file's failing one may additionally have been
+    // corrected and logged (readFile's one deviation).  Elsewhere, for a shortened RS code and when any range is
+    // one the loop refuses partway, the loop over readFile.
+    void readFiles(FileRead* reads, size_t n) override
+    {
+        struct Span {
+            size_t at, nbytes, count; // the read's number, its clamped bytes and its blocks
+            uint64_t first;
+        };
+        uint8_t* img = _disk.mapped();
+        bool engine = img && !has_spill() && _raw && _ds;
+        std::vector<Span> sel;
+        for (size_t i = 0; i < n && engine; ++i) {
+            const FileRead& r = reads[i];
+            if (r.bytes_to_read == 0 || r.offset >= r.file.file_size)
+                continue; // answered from the range alone
+            const size_t nbytes = std::min<size_t>(r.bytes_to_read, r.file.file_size - r.offset);
+            const Span s { i, nbytes, (r.offset % _ds + nbytes + _ds - 1) / _ds, r.offset / _ds };
+            engine = file_image(r.file, s.first, s.count) != nullptr;
+            sel.push_back(s);
+        }
+        if (!engine || sel.empty())
+            return IBlockDevice::readFiles(reads, n);
+        for (size_t i = 0; i < n; ++i)
+            if (reads[i].bytes_to_read == 0 || reads[i].offset >= reads[i].file.file_size)
+                read_one(reads[i],
+                    IBlockDevice::readFile(reads[i].file, reads[i].offset, reads[i].bytes_to_read, reads[i].out, &reads[i].delivered));
+        auto fail_all = [&]() {
+            for (const Span& s : sel) {
+                reads[s.at].delivered = 0;
+                read_one(reads[s.at], expected<size_t>(unexpected(FsError::Disk_IOError)));
+            }
+        };
+        const size_t m = sel.size(), image_blocks = _disk.size() / _raw;
+        std::vector<ppfs_ecc_file> files(m);
+        std::vector<ppfs_ecc_file_range> ranges(m);
+        for (size_t k = 0; k < m; ++k) {
+            files[k] = reads[sel[k].at].file;
+            ranges[k] = ppfs_ecc_file_range { reads[sel[k].at].offset, sel[k].nbytes };
+        }
+        std::vector<ppfs_ecc_files_slot> slots(m);
+        ppfs_ecc_files_totals tot {};
+        if (!EccEngine::ok(ppfs_ecc_files_plan(_eng.ctx(), files.data(), ranges.data(), m, slots.data(), &tot), "files plan"))
+            return fail_all();
+        std::vector<block_index_t> idx(tot.blocks), tidx(tot.tree_blocks);
+        std::vector<uint8_t> path(tot.blocks), status(tot.blocks, 0), tst(tot.tree_blocks), buf(tot.bytes);
+        const int wb = (_type == PPFS_ECC_REED_SOLOMON || _type == PPFS_ECC_HAMMING) ? 1 : 0;
+        if (!EccEngine::ok(ppfs_ecc_files_blocks_host(_eng.ctx(), img, image_blocks, files.data(), ranges.data(), m, idx.data(),
+                               path.data(), tidx.data(), tst.data(), nullptr, nullptr, wb),
+                "files blocks"))
+            return fail_all();
+        std::vector<ppfs_ecc_extent> all, live;
+        std::vector<size_t> live_at;
+        for (size_t k = 0; k < m; ++k) {
+            const FileRead& r = reads[sel[k].at];
+            std::vector<ppfs_ecc_extent> own = file_extents(idx.data() + slots[k].block_pos, sel[k].count, r.offset % _ds, sel[k].nbytes, _ds);
+            std::memcpy(buf.data() + slots[k].out_pos, r.out, sel[k].nbytes); // what no block writes stays the caller's
+            for (ppfs_ecc_extent& e : own) {
+                e.pos += slots[k].out_pos;
+                all.push_back(e);
+            }
+        }
+        if (all.size() != tot.blocks)
+            return fail_all();
+        for (size_t i = 0; i < all.size(); ++i)
+            if (!path[i]) {
+                live.push_back(all[i]);
+                live_at.push_back(i);
+            }
+        if (!live.empty()) {
+            std::vector<uint8_t> st(live.size());
+            if (!EccEngine::ok(ppfs_ecc_read_extents_host(_eng.ctx(), img, image_blocks, live.data(), live.size(), buf.data(),
+                                   buf.size(), st.data(), wb),
+                    "read files extents"))
+                return fail_all();
+            for (size_t k = 0; k < live.size(); ++k)
+                status[live_at[k]] = st[k];
+        }
+        for (size_t k = 0; k < m; ++k) {
+            FileRead& r = reads[sel[k].at];
+            const ppfs_ecc_files_slot& s = slots[k];
+            std::vector<FileEvent> events;
+            std::vector<uint64_t> under[3];
+            file_tree_under(sel[k].first, sel[k].count, under);
+            for (int d = 0; d < 3; ++d)
+                for (size_t i = 0; i < under[d].size() && i < s.tree_n[d]; ++i)
+                    if (tst[s.tree_pos[d] + i] == PPFS_ECC_CORRECTED)
+                        events.push_back(FileEvent { under[d][i], d, tidx[s.tree_pos[d] + i] });
+            for (size_t i = 0; i < sel[k].count; ++i)
+                if (status[s.block_pos + i] == PPFS_ECC_CORRECTED)
+                    events.push_back(FileEvent { sel[k].first + i, 3, idx[s.block_pos + i] });
+            log_in_order(events);
+            std::memcpy(r.out, buf.data() + s.out_pos, sel[k].nbytes);
+            r.delivered = sel[k].nbytes;
+            expected<size_t> got(sel[k].nbytes);
+            for (size_t i = 0; i < sel[k].count; ++i) {
+                const uint8_t p = path[s.block_pos + i], st = status[s.block_pos + i];
+                const uint8_t e = p ? p : st == PPFS_ECC_CORRECTED ? 0 : st;
+                if (e) {
+                    r.delivered = (size_t)(all[s.block_pos + i].pos - s.out_pos);
+                    got = expected<size_t>(unexpected((FsError)e));
+                    break;
+                }
+            }
+            read_one(r, got);
+        }
+    }
+
 protected:
     // a corrected block of a file call: the file block it is read before (itself, for a data block), its level
     // (0-2: the tree's, 3: data) and its image block
@@ -1561,6 +1700,24 @@ protected:
         int level;
         block_index_t block;
     };
+    // the tree's entries of a walk over [first, first + count), per level in level order (ppfs_ecc.h), as the first
+    // requested file block under each: a new index block at depth d starts where the slots above the block's own change
+    void file_tree_under(uint64_t first, size_t count, std::vector<uint64_t> (&under)[3]) const
+    {
+        const uint64_t ipb = _ds / 4;
+        FilePath prev { 4, { 0, 0, 0 } };
+        for (uint64_t j = first; j < first + count; ++j) {
+            const FilePath p = file_path(j, ipb);
+            bool fresh = p.segment != prev.segment;
+            for (unsigned d = 0; d < p.segment; ++d) {
+                if (d > 0)
+                    fresh = fresh || p.slot[d - 1] != prev.slot[d - 1];
+                if (fresh)
+                    under[d].push_back(j);
+            }
+            prev = p;
+        }
+    }
     void log_in_order(std::vector<FileEvent>& events)
     {
         std::stable_sort(events.begin(), events.end(),
@@ -1592,22 +1749,8 @@ protected:
                                tidx.data(), tst.data(), nullptr, wb),
                 "file blocks"))
             return false;
-        // the tree's entries in level order (ppfs_ecc.h) with the first requested file block under each: a new
-        // index block at depth d starts where the slots above the block's own change
         std::vector<uint64_t> under[3];
-        const uint64_t ipb = _ds / 4;
-        FilePath prev { 4, { 0, 0, 0 } };
-        for (uint64_t j = first; j < first + count; ++j) {
-            const FilePath p = file_path(j, ipb);
-            bool fresh = p.segment != prev.segment;
-            for (unsigned d = 0; d < p.segment; ++d) {
-                if (d > 0)
-                    fresh = fresh || p.slot[d - 1] != prev.slot[d - 1];
-                if (fresh)
-                    under[d].push_back(j);
-            }
-            prev = p;
-        }
+        file_tree_under(first, count, under);
         size_t k = 0;
         for (int d = 0; d < 3; ++d)
             for (uint64_t j : under[d]) {

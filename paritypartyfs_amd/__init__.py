@@ -12,11 +12,12 @@ loaded from the in-tree libppfs_ecc.so.  Python pieces:
   - block_device.*           IBlockDevice mirror (ReedSolomon/Crc/Hamming/Parity/Raw devices)
 """
 from ._native import (ECC_CRC, ECC_HAMMING, ECC_NONE, ECC_PARITY, ECC_REED_SOLOMON, STATUS_CORRECTED,
-                      STATUS_CORRECTION_ERROR, STATUS_NOT_ALLOCATED, STATUS_OK, STATUS_OUT_OF_BOUNDS, FILE_DTYPE, NativeLibraryMissing)
+                      STATUS_CORRECTION_ERROR, STATUS_NOT_ALLOCATED, STATUS_OK, STATUS_OUT_OF_BOUNDS, FILE_DTYPE, FILES_SLOT_DTYPE, FILES_TOTALS_DTYPE,
+                      NativeLibraryMissing)
 from .ecc import EccEngine, EccGroup, FileCounts, ScrubCounts, crc_implicit_to_explicit, device_copy, inject_bytes, pinned, vote3, vote3_host
 
 __all__ = [
-    "EccEngine", "EccGroup", "ScrubCounts", "FileCounts", "FILE_DTYPE", "crc_implicit_to_explicit", "device_copy", "inject_bytes", "pinned", "vote3", "vote3_host", "NativeLibraryMissing",
+    "EccEngine", "EccGroup", "ScrubCounts", "FileCounts", "FILE_DTYPE", "FILES_SLOT_DTYPE", "FILES_TOTALS_DTYPE", "crc_implicit_to_explicit", "device_copy", "inject_bytes", "pinned", "vote3", "vote3_host", "NativeLibraryMissing",
     "ECC_NONE", "ECC_CRC", "ECC_HAMMING", "ECC_PARITY", "ECC_REED_SOLOMON",
     "STATUS_OK", "STATUS_CORRECTED", "STATUS_CORRECTION_ERROR", "STATUS_OUT_OF_BOUNDS", "STATUS_NOT_ALLOCATED",
 ]

@@ -63,6 +63,11 @@ EXPORTED_SYMBOLS = (
     "ppfs_ecc_file_blocks_host",
     "ppfs_ecc_read_file_device",
     "ppfs_ecc_read_file_host",
+    "ppfs_ecc_files_plan",
+    "ppfs_ecc_files_blocks_device",
+    "ppfs_ecc_files_blocks_host",
+    "ppfs_ecc_read_files_device",
+    "ppfs_ecc_read_files_host",
     "ppfs_vote3_device",
     "ppfs_vote3_host",
     "ppfs_copy_device",
@@ -92,6 +97,12 @@ EXTENT_DTYPE = np.dtype([("pos", "<u8"), ("block", "<u4"), ("offset", "<u2"), ("
 # ppfs_ecc_file: the 64 bytes of an Inode that the read-only file walk reads
 FILE_DTYPE = np.dtype([("direct", "<u4", (12,)), ("indirect", "<u4"), ("doubly_indirect", "<u4"),
                        ("trebly_indirect", "<u4"), ("file_size", "<u4")])
+
+# ppfs_ecc_files_slot: where one file of a batch lies in the batch's arrays (88 bytes), and
+# ppfs_ecc_files_totals: the batch's sizes (48 bytes)
+FILES_SLOT_DTYPE = np.dtype([("first_block", "<u8"), ("blocks", "<u8"), ("bytes", "<u8"), ("block_pos", "<u8"),
+                             ("out_pos", "<u8"), ("tree_pos", "<u8", (3,)), ("tree_n", "<u8", (3,))])
+FILES_TOTALS_DTYPE = np.dtype([("blocks", "<u8"), ("bytes", "<u8"), ("tree_level", "<u8", (3,)), ("tree_blocks", "<u8")])
 
 
 class EccParams(ctypes.Structure):
@@ -254,6 +265,23 @@ def lib() -> ctypes.CDLL:
     L.ppfs_ecc_read_file_host.restype = c_int
     L.ppfs_ecc_read_file_host.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_uint64, c_uint64, c_void_p, c_size_t,
                                           c_void_p, c_void_p, c_int]
+    # batches of files: plan (ctx, files, ranges, nfiles, slots, totals); blocks (ctx, image, image_blocks, files, ranges,
+    # nfiles, index, path_status, tree_index, tree_status, file_flags, counts, write_back[, stream]); read (ctx, image,
+    # image_blocks, files, ranges, nfiles, out, out_bytes, status, file_flags, counts, write_back[, stream])
+    L.ppfs_ecc_files_plan.restype = c_int
+    L.ppfs_ecc_files_plan.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
+    L.ppfs_ecc_files_blocks_device.restype = c_int
+    L.ppfs_ecc_files_blocks_device.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]
+    L.ppfs_ecc_files_blocks_host.restype = c_int
+    L.ppfs_ecc_files_blocks_host.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_int]
+    L.ppfs_ecc_read_files_device.restype = c_int
+    L.ppfs_ecc_read_files_device.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
+                                             c_void_p, c_void_p, c_void_p, c_int, c_void_p]
+    L.ppfs_ecc_read_files_host.restype = c_int
+    L.ppfs_ecc_read_files_host.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
+                                           c_void_p, c_void_p, c_void_p, c_int]
     L.ppfs_vote3_device.restype = c_int
     L.ppfs_vote3_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]
     L.ppfs_copy_device.restype = c_int

@@ -403,6 +403,12 @@ class IBlockDevice:
             out += r.value()
         return bytes(out), None
 
+    def read_files(self, files, ranges) -> List[Tuple[bytes, Optional[FsError]]]:
+        """A batch of (inode, offset, length): == read_file(files[f], *ranges[f]) per file, in batch order (a directory
+        scan, a backup).  The codecs override it with one engine walk over all the files' trees."""
+        files = np.asarray(files).reshape(-1)
+        return [self.read_file(files[f:f + 1], int(off), int(n)) for f, (off, n) in enumerate(ranges)]
+
 
 def file_path_of(j: int, ipb: int):
     """Where file block j lies in an inode's tree (inode.hpp:18-41): (segment, slot at each index block from the
@@ -877,6 +883,75 @@ class _EngineDevice(IBlockDevice):
             k = int(bad[0])
             return out[:int(ext["pos"][k])].tobytes(), FsError(int(final[k]))
         return out.tobytes(), None
+
+    def read_files(self, files, ranges) -> List[Tuple[bytes, Optional[FsError]]]:
+        """IBlockDevice.read_files as two engine calls on the disk image: one walk over all the files' trees
+        (EccEngine.files_blocks_host), then the byte ranges of every block whose path held (EccEngine.read_extents_host).
+        Per file the bytes, the error and the log up to the first failing block equal read_file's; files are logged in
+        batch order; blocks after a file's failure may additionally have been corrected and logged."""
+        files = np.ascontiguousarray(files, dtype=FILE_DTYPE).reshape(-1)
+        ranges = [(int(off), int(n)) for off, n in ranges]
+        image, ds = self._mapped_image(), self._ds
+        if image is None or ds == 0 or len(ranges) != files.size:
+            return super().read_files(files, ranges)
+        results: List = [None] * files.size
+        sel, spans = [], []
+        for f, (off, want) in enumerate(ranges):
+            size = int(files["file_size"][f])
+            if want <= 0 or off >= size:  # answered from the range alone: no block is read
+                results[f] = IBlockDevice.read_file(self, files[f:f + 1], off, want)
+                continue
+            n = min(want, size - off)
+            first, count = off // ds, (off % ds + n + ds - 1) // ds
+            if self._file_image(files[f:f + 1], first, count) is None:
+                return super().read_files(files, ranges)  # a range the loop refuses partway: the loop is the definition
+            sel.append(f)
+            spans.append((off, n, first, count))
+        if not sel:
+            return results
+        eng = self._engine
+        wb = eng.ecc_type in (ECC_REED_SOLOMON, ECC_HAMMING)
+        batch = np.ascontiguousarray(files[sel])
+        byte_ranges = np.array([(off, n) for off, n, _, _ in spans], dtype=np.uint64).reshape(len(sel), 2)
+        slots, totals = eng.files_plan(batch, byte_ranges)
+        nb, T = int(totals["blocks"]), int(totals["tree_blocks"])
+        ix, ps = np.zeros(nb, dtype=np.uint32), np.zeros(nb, dtype=np.uint8)
+        ti, ts = np.zeros(T, dtype=np.uint32), np.zeros(T, dtype=np.uint8)
+        eng.files_blocks_host(image, batch, byte_ranges, ix, ps, ti, ts, write_back=wb)
+        ext = np.zeros(nb, dtype=EXTENT_DTYPE)
+        for s, (off, n, _, count) in zip(slots, spans):
+            at = int(s["block_pos"])
+            e = file_extents(ix[at:at + count], off % ds, n, ds)
+            e["pos"] += np.uint64(int(s["out_pos"]))
+            ext[at:at + count] = e
+        out, st = np.zeros(int(totals["bytes"]), dtype=np.uint8), np.zeros(nb, dtype=np.uint8)
+        live = np.nonzero(ps == 0)[0]
+        if live.size:
+            st_live = np.zeros(live.size, dtype=np.uint8)
+            eng.read_extents_host(image, np.ascontiguousarray(ext[live]), out, st_live, write_back=wb)
+            st[live] = st_live
+        ipb = ds // 4
+        for f, s, (off, n, first, count) in zip(sel, slots, spans):
+            at, pos = int(s["block_pos"]), int(s["out_pos"])
+            levels = [{}, {}, {}]  # the tree entries in level order with the first requested file block under each
+            for j in range(first, first + count):
+                p = file_path_of(j, ipb)
+                for d in range(p[0]):
+                    levels[d].setdefault(p[:d + 1], j)
+            events = [(j, d, int(ti[int(s["tree_pos"][d]) + k])) for d, lv in enumerate(levels) for k, j in enumerate(lv.values())
+                      if ts[int(s["tree_pos"][d]) + k] == STATUS_CORRECTED]
+            f_ps, f_st = ps[at:at + count], st[at:at + count]
+            events += [(first + int(k), 3, int(ix[at + k])) for k in np.nonzero(f_st == STATUS_CORRECTED)[0]]
+            for _, _, block in sorted(events, key=lambda e: e[:2]):
+                self._log(block)
+            final = np.where(f_ps != 0, f_ps, np.where(f_st == STATUS_CORRECTED, 0, f_st))
+            bad = np.nonzero(final)[0]
+            if bad.size:
+                k = int(bad[0])
+                results[f] = (out[pos:int(ext["pos"][at + k])].tobytes(), FsError(int(final[k])))
+            else:
+                results[f] = (out[pos:pos + n].tobytes(), None)
+        return results
 
     def readBlock(self, loc: DataLocation, bytes_to_read: int, capacity: Optional[int] = None) -> Expected[bytes]:
         if capacity is not None and capacity < bytes_to_read:

@@ -539,6 +539,11 @@ extern "C" void ppfs_ecc_destroy(ppfs_ecc_ctx* c)
     mem_free(c, c->d_scrub); // ... and the scrub calls
     for (void* p : c->scrub_old)
         mem_free(c, p);
+    for (const ppfs_ecc_ctx::FilesStage& st : c->files_stage) { // the batch calls' table uploads: waited for above
+        (void)hipEventSynchronize(st.done);
+        (void)hipEventDestroy(st.done);
+        pin_free(st.buf, st.bytes, kPinStage);
+    }
     if (c->scrub_ev)
         (void)hipEventDestroy(c->scrub_ev);
     if (c->list_ev)
@@ -568,7 +573,7 @@ extern "C" const char* ppfs_ecc_list_encode_kernel_name(const ppfs_ecc_ctx* c)
 #define PPFS_DBG_UNITS(X) X(ppfs_dbg_faults_rs_t2) X(ppfs_dbg_faults_rs_t4) X(ppfs_dbg_faults_rs_t6) \
     X(ppfs_dbg_faults_rs_t8) X(ppfs_dbg_faults_rs_t10) X(ppfs_dbg_faults_rs_t16) X(ppfs_dbg_faults_rs_t32)   \
     X(ppfs_dbg_faults_rs_generic) X(ppfs_dbg_faults_bit) X(ppfs_dbg_faults_bitfast) X(ppfs_dbg_faults_vote) \
-    X(ppfs_dbg_alloc_faults) X(ppfs_dbg_file_faults)
+    X(ppfs_dbg_alloc_faults) X(ppfs_dbg_file_faults) X(ppfs_dbg_files_faults)
 #define PPFS_DBG_DECL(f) extern "C" long long f(void);
 PPFS_DBG_UNITS(PPFS_DBG_DECL)
 extern "C" long long ppfs_ecc_debug_faults(void)

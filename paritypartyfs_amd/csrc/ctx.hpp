@@ -157,6 +157,15 @@ struct ppfs_ecc_ctx {
     std::vector<void*> scrub_old;
     hipEvent_t scrub_ev = nullptr;
     bool scrub_ev_rec = false;
+    // batch file calls (files_path.cpp): the page-locked buffers whose host-built tables a queued copy may
+    // still read, each with the event recorded behind that copy; a buffer returns to the cache once its
+    // event has completed (looked at by later batch calls, drained at destroy)
+    struct FilesStage {
+        void* buf;
+        size_t bytes;
+        hipEvent_t done;
+    };
+    std::vector<FilesStage> files_stage;
 };
 
 #pragma GCC visibility push(hidden)

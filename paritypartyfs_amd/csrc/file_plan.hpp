@@ -248,13 +248,17 @@ struct Expanded {
     uint32_t pointer;
     uint8_t inherited;
 };
+// expand_at: the same with the scratch positions of this file's levels A, B, C given (base_a, base_b,
+// base_c) -- a batch of files keeps every level of all its files in one merged list (files_plan.hpp);
+// expand: one file, whose levels start at slot_base.
 template <class Src>
-PPFS_HD inline Expanded expand(const Tree& t, int level, uint64_t k, uint64_t ds, const Src& src)
+PPFS_HD inline Expanded expand_at(const Tree& t, int level, uint64_t k, uint64_t ds, const Src& src, uint64_t base_a,
+    uint64_t base_b, uint64_t base_c)
 {
     const Ref r = ref_of(t, level, k);
     if (r.level == LEVEL_INODE)
         return Expanded { src.inode(r.slot), 0 };
-    const uint64_t p = slot_base(t, r.level) + r.parent_k;
+    const uint64_t p = (r.level == LEVEL_A ? base_a : r.level == LEVEL_B ? base_b : base_c) + r.parent_k;
     uint32_t ps = src.inherited(p);
     if (!ps)
         ps = src.status(p);
@@ -264,6 +268,11 @@ PPFS_HD inline Expanded expand(const Tree& t, int level, uint64_t k, uint64_t ds
     const uint32_t v = src.payload_byte(at) | src.payload_byte(at + 1u) << 8 | src.payload_byte(at + 2u) << 16
         | src.payload_byte(at + 3u) << 24;
     return Expanded { v, 0 };
+}
+template <class Src>
+PPFS_HD inline Expanded expand(const Tree& t, int level, uint64_t k, uint64_t ds, const Src& src)
+{
+    return expand_at(t, level, k, ds, src, slot_base(t, LEVEL_A), slot_base(t, LEVEL_B), slot_base(t, LEVEL_C));
 }
 
 // where a status lands in either half of ppfs_ecc_file_counts (four 64-bit words: ok, corrected, failed,

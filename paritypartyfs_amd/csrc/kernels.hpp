@@ -1,7 +1,8 @@
 // kernels.hpp -- the host-callable launchers of the kernel translation units, declared once:
 // rs_kernels.hip (Reed-Solomon and its servers), bit_kernels.hip (CRC, Hamming, parity and the bit
 // server) vote.hip (vote, copy, gather, patch list, inject, flag, block lists), alloc_scan.hip (bitmap
-// expansion, scrub tally) and file_walk.hip (the file walk's expansion, extents and merge).  The
+// expansion, scrub tally), file_walk.hip (the file walk's expansion, extents and merge) and files_walk.hip
+// (the same for a batch of files).  The
 // three table-sizing functions are in host_tables.hpp, beside the builders that use them.
 #pragma once
 
@@ -106,4 +107,19 @@ hipError_t ppfs_file_extents_launch(const uint32_t* pointer, const uint8_t* path
 hipError_t ppfs_file_merge_launch(const uint8_t* path, const uint8_t* read, uint64_t n, uint8_t* status_out,
     const uint32_t* pointer_in, uint32_t* pointer_out, uint8_t* out, uint64_t i0, uint64_t off0, uint64_t bytes, uint64_t ds,
     unsigned long long* counts, int slot0, hipStream_t s);
+// the walk over a batch of files (files_path.cpp; files_walk.hip, arithmetic in files_plan.hpp).  recs: the
+// batch's nfiles filesplan::FileRec; rows: the nrows filesplan::Row of the level the launch works on (sentinel
+// not counted); both in device memory, 8-byte aligned.  e0: the merged entry of element 0 of the launch's
+// arrays.  Otherwise as the three launchers above, with
+// payload / st / inh the merged scratch of `slots` entries, out the batch's buffer of out_bytes bytes and
+// flags[file] |= filesplan::flag_of(final status) << flag_shift.
+hipError_t ppfs_files_expand_launch(const void* recs, uint64_t nfiles, const void* rows, uint64_t nrows, int level, uint64_t e0,
+    uint64_t n, uint64_t ds, const uint8_t* payload, const uint8_t* st, const uint8_t* inh, uint64_t slots, uint32_t* pointer,
+    uint8_t* inherited, hipStream_t s);
+hipError_t ppfs_files_extents_launch(const void* recs, uint64_t nfiles, const void* rows, uint64_t nrows, const uint32_t* pointer,
+    const uint8_t* path, uint64_t e0, uint64_t n, uint64_t ds, ppfs_ecc_extent* ext, hipStream_t s);
+hipError_t ppfs_files_merge_launch(const void* recs, uint64_t nfiles, const void* rows, uint64_t nrows, const uint8_t* path,
+    const uint8_t* read, uint64_t e0, uint64_t n, uint8_t* status_out, const uint32_t* pointer_in, uint32_t* pointer_out,
+    uint8_t* out, uint64_t out_bytes, uint64_t ds, uint32_t* flags, uint32_t flag_shift, unsigned long long* counts, int slot0,
+    hipStream_t s);
 }

@@ -498,6 +498,111 @@ class EccEngine:
                                             out_bytes, _ptr(status), byref(rec), int(bool(write_back))))
         return FileCounts(*[int(getattr(rec, n)) for n in FILE_COUNT_FIELDS])
 
+    # ---------------- read many files in one call (ppfs_ecc_files_*, ppfs_ecc_read_files_*) ----------------
+    # `files` is a FILE_DTYPE array of any length in host memory, `ranges` None (every file whole) or an (n, 2) uint64
+    # array of (offset, nbytes).  files_plan says where each file's results lie in the batch's arrays: per-block arrays
+    # and out hold the files back to back, the tree arrays are level-major.  file_flags: one uint32 per file.
+    @staticmethod
+    def _files(files, ranges):
+        f = np.ascontiguousarray(files)
+        if f.dtype != _native.FILE_DTYPE or f.ndim > 1:
+            raise ValueError("files: a 1-D array of FILE_DTYPE records")
+        f = f.reshape(-1)
+        if ranges is None:
+            return f, None
+        r = np.ascontiguousarray(ranges)
+        if r.dtype != np.uint64 or r.shape != (f.size, 2):
+            raise ValueError(f"ranges: None or a ({f.size}, 2) numpy uint64 array of (offset, nbytes)")
+        return f, r
+
+    def files_plan(self, files, ranges=None):
+        """(slots, totals) of a batch (ppfs_ecc_files_plan): one FILES_SLOT_DTYPE record per file and one
+        FILES_TOTALS_DTYPE record.  No GPU work."""
+        f, r = self._files(files, ranges)
+        slots, totals = np.zeros(f.size, _native.FILES_SLOT_DTYPE), np.zeros(1, _native.FILES_TOTALS_DTYPE)
+        check(lib().ppfs_ecc_files_plan(self._h, f.ctypes.data if f.size else None, None if r is None else r.ctypes.data,
+                                        f.size, slots.ctypes.data if f.size else None, totals.ctypes.data))
+        return slots, totals[0]
+
+    def _files_check(self, kind, image, files, ranges, index=None, path_status=None, tree_index=None, tree_status=None,
+                     file_flags=None, out=None, status=None, read=False):
+        f, r = self._files(files, ranges)
+        if image is None:
+            raise ValueError("image: required")
+        _, totals = self.files_plan(f, r)
+        nblocks, t = int(totals["blocks"]), int(totals["tree_blocks"])
+        _need("image", image, 0, kind)
+        _need("path_status", path_status, nblocks, kind)
+        _need("tree_status", tree_status, t, kind)
+        _need("status", status, nblocks, kind)
+        if read:
+            _need("out", out, int(totals["bytes"]), kind)
+        _ptr(image), _ptr(path_status), _ptr(tree_status), _ptr(status), _ptr(out)  # contiguous uint8
+        for name, x, n in (("index", index, nblocks), ("tree_index", tree_index, t), ("file_flags", file_flags, f.size)):
+            if x is None:
+                continue
+            if kind == "device":
+                import torch
+
+                if isinstance(x, np.ndarray) or not getattr(x, "is_cuda", False) or x.dtype != torch.int32 \
+                        or not x.is_contiguous() or x.dim() != 1 or x.numel() < n:
+                    raise ValueError(f"{name}: a contiguous 1-D CUDA torch.int32 tensor of >= {n} elements (read as unsigned)")
+            elif not isinstance(x, np.ndarray) or x.dtype != np.uint32 or not x.flags["C_CONTIGUOUS"] or x.ndim != 1 \
+                    or x.size < n:
+                raise ValueError(f"{name}: a C-contiguous 1-D numpy uint32 array of >= {n} elements")
+        return (f.ctypes.data if f.size else None, None if r is None else r.ctypes.data, f.size, f, r,
+                _size(image) // self.raw_block_size)
+
+    def _u32_ptr(self, x):
+        return None if x is None else self._index_ptr(x)
+
+    def files_blocks(self, image, files, ranges=None, index=None, path_status=None, tree_index=None, tree_status=None,
+                     file_flags=None, counts=None, write_back: bool = True, stream=None):
+        """Device walk over a batch (ppfs_ecc_files_blocks_device); counts as in file_blocks, one record for the
+        batch.  Never synchronises."""
+        fp, rp, n, f, r, blocks = self._files_check("device", image, files, ranges, index, path_status, tree_index,
+                                                    tree_status, file_flags)
+        d_counts = self._device_counts(counts)
+        check(lib().ppfs_ecc_files_blocks_device(
+            self._h, _ptr(image), blocks, fp, rp, n, self._u32_ptr(index), _ptr(path_status), self._u32_ptr(tree_index),
+            _ptr(tree_status), self._u32_ptr(file_flags), None if d_counts is None else d_counts.data_ptr(),
+            int(bool(write_back)), _stream_handle(stream)))
+        return d_counts
+
+    def files_blocks_host(self, image: np.ndarray, files, ranges=None, index=None, path_status=None, tree_index=None,
+                          tree_status=None, file_flags=None, write_back: bool = True) -> "FileCounts":
+        fp, rp, n, f, r, blocks = self._files_check("host", image, files, ranges, index, path_status, tree_index,
+                                                    tree_status, file_flags)
+        rec = _native.FileCounts()
+        check(lib().ppfs_ecc_files_blocks_host(
+            self._h, _ptr(image), blocks, fp, rp, n, self._u32_ptr(index), _ptr(path_status), self._u32_ptr(tree_index),
+            _ptr(tree_status), self._u32_ptr(file_flags), byref(rec), int(bool(write_back))))
+        return FileCounts(*[int(getattr(rec, k)) for k in FILE_COUNT_FIELDS])
+
+    def read_files(self, image, files, ranges, out, status=None, file_flags=None, counts=None, write_back: bool = True,
+                   stream=None):
+        """Device read of a batch (ppfs_ecc_read_files_device): out[slot.out_pos, + slot.bytes) = file f's range;
+        status: one byte per file block touched, files back to back.  Never synchronises."""
+        fp, rp, n, f, r, blocks = self._files_check("device", image, files, ranges, file_flags=file_flags, out=out,
+                                                    status=status, read=True)
+        d_counts = self._device_counts(counts)
+        check(lib().ppfs_ecc_read_files_device(
+            self._h, _ptr(image), blocks, fp, rp, n, _ptr(out), 0 if out is None else _size(out), _ptr(status),
+            self._u32_ptr(file_flags), None if d_counts is None else d_counts.data_ptr(), int(bool(write_back)),
+            _stream_handle(stream)))
+        return d_counts
+
+    def read_files_host(self, image: np.ndarray, files, ranges, out: Optional[np.ndarray],
+                        status: Optional[np.ndarray] = None, file_flags: Optional[np.ndarray] = None,
+                        write_back: bool = True) -> "FileCounts":
+        fp, rp, n, f, r, blocks = self._files_check("host", image, files, ranges, file_flags=file_flags, out=out,
+                                                    status=status, read=True)
+        rec = _native.FileCounts()
+        check(lib().ppfs_ecc_read_files_host(
+            self._h, _ptr(image), blocks, fp, rp, n, _ptr(out), 0 if out is None else _size(out), _ptr(status),
+            self._u32_ptr(file_flags), byref(rec), int(bool(write_back))))
+        return FileCounts(*[int(getattr(rec, k)) for k in FILE_COUNT_FIELDS])
+
 
 # ppfs_ecc_scrub_counts: the host forms return it as this tuple, the device forms as a CUDA int64 tensor
 # in the same field order (ScrubCounts(*tensor.tolist()) after synchronising)
