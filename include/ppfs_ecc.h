@@ -557,6 +557,72 @@ int ppfs_ecc_read_files_host(ppfs_ecc_ctx* ctx, uint8_t* image, size_t image_blo
     uint32_t* file_flags, ppfs_ecc_file_counts* counts, int write_back);
 
 /*
+ * Write a file range from its inode: the other half of FileIO's call into the block device (DESIGN.md
+ * section 4.12).  FileIO::writeFile (lib/file_io/src/file_io.cpp:46-104) walks the same BlockIndexIterator as
+ * readFile, one readBlock per index block, and then issues one writeBlock(bytes, {block, offset}) per data
+ * block: offset % dataSize() in the first block, a short last block.  ppfs_ecc_write_file_* is that over ONE
+ * existing range, ppfs_ecc_write_files_* over a batch of (file, range).  They write INSIDE the file as the
+ * inode describes it: nothing allocates, nothing grows, no inode is updated (PPFS's resizeFile comes first).
+ *
+ * Range.  offset + nbytes <= file_size, else -EINVAL before anything touches the GPU (the batch call puts the
+ * file's number in ppfs_ecc_last_error).  Nothing is clamped, unlike the read: a write that runs past the end
+ * would have to grow the file.  Blocks past the tree's capacity and a payload above 65,535 bytes are rejected
+ * as by the read calls.  nbytes == 0 is a no-op: 0, zeroed counts, written = 0.  DEVIATION: the reference
+ * checks and re-encodes one block for an empty write.  An empty write (the single call with nbytes == 0, a
+ * batch whose ranges are all empty) needs neither image nor `in` -- both may be NULL -- in either form; the
+ * context, the file records and the alignment of written, flags and counts are still checked, and the device
+ * forms still clear counts and flags and set written on `stream`.  ranges == NULL: every file whole.
+ * Input.  The single-file call takes in[0, nbytes).  The batch call takes file f's bytes at in[out_pos,
+ * out_pos + bytes) of ppfs_ecc_files_plan, files back to back; its slots hold unchanged for every batch the
+ * write accepts (only the range rule is stricter).  in_bytes below the total is -EINVAL.
+ * Walk.  Exactly the read calls': each needed index block is decoded once; write_back applies to the index
+ * blocks only; an index block with status 5 / 9 hands that down and the pointer becomes 0xFFFFFFFF.
+ * Write.  Per file block one writeBlock(bytes, {block, offset}) of the reference through
+ * ppfs_ecc_write_extents_*, entry i being the read's extent with pos pointing into `in`.
+ *   status       (may be NULL) one byte per file block touched: the path status where that is non-zero, else
+ *                the write's 0 / 1 / 5 / 9.  A block whose final status is 5 or 9 is NOT TOUCHED: its own old
+ *                contents failed, an index block above it failed, or its pointer lies past the image
+ *   written      (may be NULL, 8-byte aligned) one uint64 per file (a scalar for the single call): the bytes
+ *                of the range that precede the first block whose final status is 5 or 9, or the range's byte
+ *                count when there is none -- what FileIO::writeFile had written when it failed
+ *   file_flags, counts   as in the read calls, over the final statuses; counts is one record per call and
+ *                index_* count the tree blocks
+ * Nothing outside the named blocks changes; within a block only the codec's re-encoding of the new payload
+ * changes, and the bits the codec leaves undefined keep their contents as in ppfs_ecc_write_extents_*.
+ * Batch semantics.  Every block of every range is attempted.  DEVIATION: the reference stops at the first
+ * failure, so blocks after a failed one have been written here; `written` and the adapters restore the
+ * reference's return value.
+ * Repeats.  Device writes need distinct blocks (ppfs_ecc_write_extents_device).  ppfs_ecc_write_files_device
+ * therefore refuses, with -EINVAL naming the later file and before anything touches the GPU, two ranges of
+ * byte-identical inode records whose file-block spans intersect (found on the host from the plan alone, in
+ * O(n log n)); spans that only touch are fine.  ppfs_ecc_write_files_host does not refuse:
+ * ppfs_ecc_write_extents_host cuts where a block repeats, so ranges apply in batch order and both land.
+ * Different inodes that share blocks (a corrupt image) stay memory-safe; which write lands is unspecified,
+ * as for ppfs_ecc_write_list_device.
+ * Errors: -EINVAL, before anything touches the GPU, for a null ctx, file(s), image or `in`, a misaligned
+ * written, flags or counts.  Device forms: PPFS_ECC_ENOTSUP on a capturing stream; `stream` is never
+ * synchronised and nothing is read back; the scratch is the scrub scratch with the read's per-piece layout,
+ * 32 Ki file blocks a piece, cut regardless of file boundaries; the batch tables go through the same
+ * page-locked staging.  `written` is set on the GPU: one lane per file stores the range's bytes, then the
+ * merge kernel lowers it with a 64-bit atomic minimum for failing blocks.  Per piece: expansion, extents,
+ * ppfs_ecc_write_extents_device, merge.
+ * Host forms: the same plan on the CPU around ppfs_ecc_decode_list_host per level and one
+ * ppfs_ecc_write_extents_host.
+ */
+int ppfs_ecc_write_file_device(ppfs_ecc_ctx* ctx, const uint8_t* d_in, size_t in_bytes, uint8_t* d_image, size_t image_blocks,
+    const ppfs_ecc_file* file, uint64_t offset, uint64_t nbytes, uint8_t* d_status, uint64_t* d_written,
+    ppfs_ecc_file_counts* d_counts, int write_back, void* stream);
+int ppfs_ecc_write_file_host(ppfs_ecc_ctx* ctx, const uint8_t* in, size_t in_bytes, uint8_t* image, size_t image_blocks,
+    const ppfs_ecc_file* file, uint64_t offset, uint64_t nbytes, uint8_t* status, uint64_t* written,
+    ppfs_ecc_file_counts* counts, int write_back);
+int ppfs_ecc_write_files_device(ppfs_ecc_ctx* ctx, const uint8_t* d_in, size_t in_bytes, uint8_t* d_image, size_t image_blocks,
+    const ppfs_ecc_file* files, const ppfs_ecc_file_range* ranges, size_t nfiles, uint8_t* d_status, uint32_t* d_file_flags,
+    uint64_t* d_written, ppfs_ecc_file_counts* d_counts, int write_back, void* stream);
+int ppfs_ecc_write_files_host(ppfs_ecc_ctx* ctx, const uint8_t* in, size_t in_bytes, uint8_t* image, size_t image_blocks,
+    const ppfs_ecc_file* files, const ppfs_ecc_file_range* ranges, size_t nfiles, uint8_t* status, uint32_t* file_flags,
+    uint64_t* written, ppfs_ecc_file_counts* counts, int write_back);
+
+/*
  * 2-of-3 bitwise majority of nrec replicated records of rec_bytes each, replacing
  * SuperBlockManager::_performBitVoting (lib/super_block_manager/src/super_block_manager.cpp:133-165):
  *   out[i] = majority(a[i], b[i], c[i]) bit by bit;

@@ -41,6 +41,8 @@
  * and resolve the tree themselves: FileIO::readFile of any size without the BlockIndexIterator loop.
  * readFiles does that for a batch of (inode, offset, length) -- a directory scan, a backup -- with all the
  * files' trees walked in one engine call.
+ * writeFile / writeFiles are the in-place case of FileIO::writeFile from the same 64 bytes: a range inside the
+ * file, or a batch of them, written without the iterator loop; nothing is allocated and no inode is updated.
  */
 #include <algorithm>
 #include <cstddef>
@@ -854,12 +856,68 @@ public:
             read_one(reads[i], readFile(reads[i].file, reads[i].offset, reads[i].bytes_to_read, reads[i].out, &reads[i].delivered));
     }
 
+    // Write extension (ppfs_ecc.h ppfs_ecc_write_file_* / ppfs_ecc_write_files_*): the in-place case of
+    // FileIO::writeFile (file_io.cpp:46-104).  The range must lie inside the file as the inode describes it --
+    // offset + n <= file_size, else FileIO_OutOfBounds as readFile reports a range past the end; nothing is
+    // allocated, nothing grows, no inode is updated.  The per-block loop is the definition: the walk above, one
+    // writeBlock per data block, the first error ends it.  The value returned is n; on an error the call returns
+    // it and *written (may be null) says how many bytes were written before the failing block.  n == 0 touches
+    // nothing.  The codecs write the whole range, or a batch of them, in engine calls.
+    virtual expected<size_t> writeFile(const ppfs_ecc_file& file, size_t offset, const uint8_t* in, size_t n, size_t* written = nullptr)
+    {
+        const size_t ds = dataSize();
+        if (written)
+            *written = 0;
+        if (n == 0)
+            return (size_t)0;
+        if (ds == 0 || offset + n < offset || offset + n > file.file_size)
+            return unexpected(FsError::FileIO_OutOfBounds);
+        FileWalk walk(*this, file);
+        size_t done = 0;
+        for (uint64_t j = offset / ds; done < n; ++j) {
+            auto b = walk.block(j);
+            if (!b)
+                return unexpected(b.error());
+            const size_t off = done == 0 ? offset % ds : 0, len = std::min(ds - off, n - done);
+            static_vector<uint8_t> v(const_cast<uint8_t*>(in) + done, len, len);
+            auto r = writeBlock(v, DataLocation((int)*b, (int)off));
+            if (!r)
+                return unexpected(r.error());
+            done += len;
+            if (written)
+                *written = done;
+        }
+        return n;
+    }
+    // By definition the loop over writeFile, in batch order.  Per write: ok and `bytes` (the value writeFile
+    // returns) or `error`, and `written` as writeFile reports it.
+    struct FileWrite {
+        ppfs_ecc_file file;
+        size_t offset;
+        const uint8_t* in;
+        size_t n;
+        bool ok;
+        FsError error;
+        size_t bytes, written;
+    };
+    virtual void writeFiles(FileWrite* writes, size_t n)
+    {
+        for (size_t i = 0; i < n; ++i)
+            write_one(writes[i], writeFile(writes[i].file, writes[i].offset, writes[i].in, writes[i].n, &writes[i].written));
+    }
+
 protected:
     static void read_one(FileRead& r, const expected<size_t>& got)
     {
         r.ok = (bool)got;
         r.error = got ? FsError {} : got.error();
         r.bytes = got ? *got : 0;
+    }
+    static void write_one(FileWrite& w, const expected<size_t>& got)
+    {
+        w.ok = (bool)got;
+        w.error = got ? FsError {} : got.error();
+        w.bytes = got ? *got : 0;
     }
 };
 
@@ -1689,6 +1747,108 @@ public:
                 }
             }
             read_one(r, got);
+        }
+    }
+
+    // writeFile / writeFiles as engine calls on a mapped disk image: one ppfs_ecc_files_blocks_host over all the
+    // files' trees -- the write call reports the tree only as counts, and the log needs to know WHICH index blocks
+    // were corrected -- then ONE ppfs_ecc_write_files_host.  Per file the result, `written` and the log up to the
+    // first failing block are the loop's; files are logged in batch order, index blocks in readFile's order.
+    // Every block of every range is attempted, so blocks after a file's failing one have been written (and
+    // logged) as well: the one deviation.  Elsewhere, for a shortened RS code and when any range is one the loop
+    // refuses partway, the per-block loop.
+    expected<size_t> writeFile(const ppfs_ecc_file& file, size_t offset, const uint8_t* in, size_t n, size_t* written = nullptr) override
+    {
+        FileWrite w { file, offset, in, n, false, FsError {}, 0, 0 };
+        writeFiles(&w, 1);
+        if (written)
+            *written = w.written;
+        if (!w.ok)
+            return unexpected(w.error);
+        return w.bytes;
+    }
+    void writeFiles(FileWrite* writes, size_t n) override
+    {
+        struct Span {
+            size_t at, count; // the write's number and its blocks
+            uint64_t first;
+        };
+        auto by_range = [](const FileWrite& w) { return w.n == 0 || w.offset + w.n < w.offset || w.offset + w.n > w.file.file_size; };
+        auto loop_one = [&](FileWrite& w) { write_one(w, IBlockDevice::writeFile(w.file, w.offset, w.in, w.n, &w.written)); };
+        uint8_t* img = _disk.mapped();
+        bool engine = img && !has_spill() && _raw && _ds;
+        std::vector<Span> sel;
+        for (size_t i = 0; i < n && engine; ++i) {
+            const FileWrite& w = writes[i];
+            if (by_range(w))
+                continue; // answered from the range alone
+            const Span s { i, (w.offset % _ds + w.n + _ds - 1) / _ds, w.offset / _ds };
+            engine = file_image(w.file, s.first, s.count) != nullptr;
+            sel.push_back(s);
+        }
+        if (!engine || sel.empty()) {
+            for (size_t i = 0; i < n; ++i)
+                loop_one(writes[i]);
+            return;
+        }
+        for (size_t i = 0; i < n; ++i)
+            if (by_range(writes[i]))
+                loop_one(writes[i]);
+        auto fail_all = [&]() {
+            for (const Span& s : sel) {
+                writes[s.at].written = 0;
+                write_one(writes[s.at], expected<size_t>(unexpected(FsError::Disk_IOError)));
+            }
+        };
+        const size_t m = sel.size(), image_blocks = _disk.size() / _raw;
+        std::vector<ppfs_ecc_file> files(m);
+        std::vector<ppfs_ecc_file_range> ranges(m);
+        for (size_t k = 0; k < m; ++k) {
+            files[k] = writes[sel[k].at].file;
+            ranges[k] = ppfs_ecc_file_range { writes[sel[k].at].offset, writes[sel[k].at].n };
+        }
+        std::vector<ppfs_ecc_files_slot> slots(m);
+        ppfs_ecc_files_totals tot {};
+        if (!EccEngine::ok(ppfs_ecc_files_plan(_eng.ctx(), files.data(), ranges.data(), m, slots.data(), &tot), "files plan"))
+            return fail_all();
+        std::vector<block_index_t> idx(tot.blocks), tidx(tot.tree_blocks);
+        std::vector<uint8_t> status(tot.blocks, 0), tst(tot.tree_blocks), buf(tot.bytes);
+        std::vector<uint64_t> done(m, 0);
+        const int wb = (_type == PPFS_ECC_REED_SOLOMON || _type == PPFS_ECC_HAMMING) ? 1 : 0;
+        if (!EccEngine::ok(ppfs_ecc_files_blocks_host(_eng.ctx(), img, image_blocks, files.data(), ranges.data(), m, idx.data(),
+                               nullptr, tidx.data(), tst.data(), nullptr, nullptr, wb),
+                "files blocks"))
+            return fail_all();
+        for (size_t k = 0; k < m; ++k)
+            std::memcpy(buf.data() + slots[k].out_pos, writes[sel[k].at].in, writes[sel[k].at].n);
+        if (!EccEngine::ok(ppfs_ecc_write_files_host(_eng.ctx(), buf.data(), buf.size(), img, image_blocks, files.data(),
+                               ranges.data(), m, status.data(), nullptr, done.data(), nullptr, wb),
+                "write files"))
+            return fail_all();
+        for (size_t k = 0; k < m; ++k) {
+            FileWrite& w = writes[sel[k].at];
+            const ppfs_ecc_files_slot& s = slots[k];
+            std::vector<FileEvent> events;
+            std::vector<uint64_t> under[3];
+            file_tree_under(sel[k].first, sel[k].count, under);
+            for (int d = 0; d < 3; ++d)
+                for (size_t i = 0; i < under[d].size() && i < s.tree_n[d]; ++i)
+                    if (tst[s.tree_pos[d] + i] == PPFS_ECC_CORRECTED)
+                        events.push_back(FileEvent { under[d][i], d, tidx[s.tree_pos[d] + i] });
+            for (size_t i = 0; i < sel[k].count; ++i)
+                if (status[s.block_pos + i] == PPFS_ECC_CORRECTED)
+                    events.push_back(FileEvent { sel[k].first + i, 3, idx[s.block_pos + i] });
+            log_in_order(events);
+            w.written = (size_t)done[k];
+            expected<size_t> got(w.n);
+            for (size_t i = 0; i < sel[k].count; ++i) {
+                const uint8_t st = status[s.block_pos + i];
+                if (st != 0 && st != PPFS_ECC_CORRECTED) {
+                    got = expected<size_t>(unexpected((FsError)st)); // 5 and 9 are BlockDevice_CorrectionError and Disk_OutOfBounds
+                    break;
+                }
+            }
+            write_one(w, got);
         }
     }
 

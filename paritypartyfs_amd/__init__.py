@@ -6,7 +6,8 @@ loaded from the in-tree libppfs_ecc.so.  Python pieces:
                              ranges, block lists or byte extents (block, offset, length); scrub of a
                              block list or of the blocks an on-disk allocation bitmap marks; a file read
                              from the 64 bytes of its inode (file_blocks / read_file: the index-block tree
-                             is resolved on the GPU)
+                             is resolved on the GPU), a batch of files (files_blocks / read_files), and the
+                             in-place write of a file range or a batch of them (write_file / write_files)
   - ecc.EccGroup             the host calls sharded over several GPUs (one thread per device)
   - ecc.vote3 / vote3_host   2-of-3 bitwise voting of replicated records (superblock copies)
   - block_device.*           IBlockDevice mirror (ReedSolomon/Crc/Hamming/Parity/Raw devices)

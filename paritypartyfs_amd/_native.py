@@ -68,6 +68,10 @@ EXPORTED_SYMBOLS = (
     "ppfs_ecc_files_blocks_host",
     "ppfs_ecc_read_files_device",
     "ppfs_ecc_read_files_host",
+    "ppfs_ecc_write_file_device",
+    "ppfs_ecc_write_file_host",
+    "ppfs_ecc_write_files_device",
+    "ppfs_ecc_write_files_host",
     "ppfs_vote3_device",
     "ppfs_vote3_host",
     "ppfs_copy_device",
@@ -282,6 +286,21 @@ def lib() -> ctypes.CDLL:
     L.ppfs_ecc_read_files_host.restype = c_int
     L.ppfs_ecc_read_files_host.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
                                            c_void_p, c_void_p, c_void_p, c_int]
+    # file writes: (ctx, in, in_bytes, image, image_blocks, file, offset, nbytes, status, written, counts, write_back
+    # [, stream]) and (ctx, in, in_bytes, image, image_blocks, files, ranges, nfiles, status, file_flags, written, counts,
+    # write_back[, stream])
+    L.ppfs_ecc_write_file_device.restype = c_int
+    L.ppfs_ecc_write_file_device.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_uint64, c_uint64,
+                                             c_void_p, c_void_p, c_void_p, c_int, c_void_p]
+    L.ppfs_ecc_write_file_host.restype = c_int
+    L.ppfs_ecc_write_file_host.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_uint64, c_uint64,
+                                           c_void_p, c_void_p, c_void_p, c_int]
+    L.ppfs_ecc_write_files_device.restype = c_int
+    L.ppfs_ecc_write_files_device.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]
+    L.ppfs_ecc_write_files_host.restype = c_int
+    L.ppfs_ecc_write_files_host.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_int]
     L.ppfs_vote3_device.restype = c_int
     L.ppfs_vote3_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]
     L.ppfs_copy_device.restype = c_int

@@ -409,6 +409,38 @@ class IBlockDevice:
         files = np.asarray(files).reshape(-1)
         return [self.read_file(files[f:f + 1], int(off), int(n)) for f, (off, n) in enumerate(ranges)]
 
+    # write a file range from its inode (include/ppfs_ecc.h ppfs_ecc_write_file_* / ppfs_ecc_write_files_*): the in-place
+    # case of FileIO::writeFile (file_io.cpp:46-104).  The range must lie inside the file; nothing is allocated and no
+    # inode is updated.  The per-block loop is the definition: the walk above, one writeBlock per data block, the first
+    # error ends it.  The codecs override both with one engine call.
+    def write_file(self, file, offset: int, data) -> Tuple[int, Optional[FsError]]:
+        """(the bytes written before the first error, that error or None)."""
+        f = np.asarray(file).reshape(-1)[0]
+        data = bytes(data)
+        size, ds, n = int(f["file_size"]), self.dataSize(), len(data)
+        if n == 0:
+            return 0, None
+        if ds == 0 or offset < 0 or offset + n > size:
+            return 0, FsError.FileIO_OutOfBounds
+        first, count = offset // ds, (offset % ds + n + ds - 1) // ds
+        written = 0
+        for k, v in enumerate(self._file_walk(file, first, count)):
+            if isinstance(v, FsError):
+                return written, v
+            off = offset % ds if k == 0 else 0
+            ln = min(ds - off, n - written)
+            r = self.writeBlock(data[written:written + ln], DataLocation(v, off))
+            if not r:
+                return written, r.error()
+            written += ln
+        return written, None
+
+    def write_files(self, files, ranges, datas) -> List[Tuple[int, Optional[FsError]]]:
+        """A batch of (inode, offset, bytes): == write_file(files[f], ranges[f][0], datas[f][:ranges[f][1]]) per file, in
+        batch order."""
+        files = np.asarray(files).reshape(-1)
+        return [self.write_file(files[f:f + 1], int(off), bytes(datas[f])[:max(int(n), 0)]) for f, (off, n) in enumerate(ranges)]
+
 
 def file_path_of(j: int, ipb: int):
     """Where file block j lies in an inode's tree (inode.hpp:18-41): (segment, slot at each index block from the
@@ -951,6 +983,68 @@ class _EngineDevice(IBlockDevice):
                 results[f] = (out[pos:int(ext["pos"][at + k])].tobytes(), FsError(int(final[k])))
             else:
                 results[f] = (out[pos:pos + n].tobytes(), None)
+        return results
+
+    def write_file(self, file, offset: int, data) -> Tuple[int, Optional[FsError]]:
+        """IBlockDevice.write_file as write_files of one file."""
+        file = np.ascontiguousarray(file, dtype=FILE_DTYPE).reshape(1)
+        data = bytes(data)
+        return self.write_files(file, [(offset, len(data))], [data])[0]
+
+    def write_files(self, files, ranges, datas) -> List[Tuple[int, Optional[FsError]]]:
+        """IBlockDevice.write_files as engine calls on the disk image: one walk over all the files' trees
+        (EccEngine.files_blocks_host: which index blocks were corrected, for the log), then ONE
+        EccEngine.write_files_host.  Per file `written`, the error and the log up to the first failing block equal
+        write_file's; files are logged in batch order, index blocks in the order read_file uses.  Every block of every
+        range is attempted: blocks after a file's failing block have been written (and logged) as well."""
+        files = np.ascontiguousarray(files, dtype=FILE_DTYPE).reshape(-1)
+        ranges = [(int(off), int(n)) for off, n in ranges]
+        datas = [bytes(d) for d in datas]
+        image, ds = self._mapped_image(), self._ds
+        loop = lambda: [IBlockDevice.write_file(self, files[f:f + 1], off, datas[f][:max(n, 0)]) for f, (off, n) in enumerate(ranges)]
+        if image is None or ds == 0 or len(ranges) != files.size or len(datas) != files.size:
+            return loop()
+        results: List = [None] * files.size
+        sel, spans = [], []
+        for f, (off, want) in enumerate(ranges):
+            n = min(max(want, 0), len(datas[f]))
+            if n == 0 or off < 0 or off + n > int(files["file_size"][f]):  # answered from the range alone: no block is touched
+                results[f] = IBlockDevice.write_file(self, files[f:f + 1], off, datas[f][:n])
+                continue
+            first, count = off // ds, (off % ds + n + ds - 1) // ds
+            if self._file_image(files[f:f + 1], first, count) is None:
+                return loop()  # a range the loop refuses partway: the loop is the definition
+            sel.append(f)
+            spans.append((off, n, first, count))
+        if not sel:
+            return results
+        eng = self._engine
+        wb = eng.ecc_type in (ECC_REED_SOLOMON, ECC_HAMMING)
+        batch = np.ascontiguousarray(files[sel])
+        byte_ranges = np.array([(off, n) for off, n, _, _ in spans], dtype=np.uint64).reshape(len(sel), 2)
+        slots, totals = eng.files_plan(batch, byte_ranges)
+        nb, T = int(totals["blocks"]), int(totals["tree_blocks"])
+        ix, ti, ts = np.zeros(nb, dtype=np.uint32), np.zeros(T, dtype=np.uint32), np.zeros(T, dtype=np.uint8)
+        eng.files_blocks_host(image, batch, byte_ranges, ix, None, ti, ts, write_back=wb)
+        src = np.frombuffer(b"".join(datas[f][:n] for f, (_, n, _, _) in zip(sel, spans)), dtype=np.uint8)
+        st = np.zeros(nb, dtype=np.uint8)
+        _, written = eng.write_files_host(src, image, batch, byte_ranges, st, write_back=wb)
+        ipb = ds // 4
+        for k, (f, s, (off, n, first, count)) in enumerate(zip(sel, slots, spans)):
+            at = int(s["block_pos"])
+            levels = [{}, {}, {}]  # the tree entries in level order with the first requested file block under each
+            for j in range(first, first + count):
+                p = file_path_of(j, ipb)
+                for d in range(p[0]):
+                    levels[d].setdefault(p[:d + 1], j)
+            events = [(j, d, int(ti[int(s["tree_pos"][d]) + q])) for d, lv in enumerate(levels) for q, j in enumerate(lv.values())
+                      if ts[int(s["tree_pos"][d]) + q] == STATUS_CORRECTED]
+            f_st = st[at:at + count]
+            events += [(first + int(q), 3, int(ix[at + q])) for q in np.nonzero(f_st == STATUS_CORRECTED)[0]]
+            for _, _, block in sorted(events, key=lambda e: e[:2]):
+                self._log(block)
+            bad = np.nonzero((f_st == STATUS_CORRECTION_ERROR) | (f_st == STATUS_OUT_OF_BOUNDS))[0]
+            results[f] = (int(written[k]), FsError(int(f_st[bad[0]])) if bad.size else None)
         return results
 
     def readBlock(self, loc: DataLocation, bytes_to_read: int, capacity: Optional[int] = None) -> Expected[bytes]:

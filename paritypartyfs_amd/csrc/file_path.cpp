@@ -12,6 +12,9 @@
 //   blocks  per piece of fileplan::PIECE_BLOCKS file blocks: expand the data pointers and path statuses
 //   read    per piece: the same, the extents in closed form, ppfs_ecc_read_extents_*, then path status
 //           over read status, the zero fill under a failed index block and the tally
+//   write   ppfs_ecc_write_file_* (FileIO::writeFile over an existing range, file_io.cpp:46-104): per piece the
+//           same expansion and extents, pos pointing into the caller's bytes, ppfs_ecc_write_extents_*, then
+//           path status over write status, the tally and `written`; no payload byte is filled in
 // The device forms queue all of it on the caller's stream and read nothing back; their scratch is the
 // context's scrub scratch (scrub_path.cpp), so no call allocates or frees on the caller's stream.  The
 // host forms run the same plan on the CPU around the *_host list and extent calls.
@@ -73,6 +76,33 @@ int read_args(const ppfs_ecc_ctx* c, const void* image, const ppfs_ecc_file* fil
         return r;
     if (!out || out_bytes < sp.bytes)
         return fail(PPFS_ECC_EINVAL, "read file: the out buffer is null or shorter than the bytes to deliver");
+    return 0;
+}
+
+// The checks of an in-place writeFile(offset, nbytes): the range must lie inside the file (nothing is clamped,
+// nothing grows), then the walk's
+int write_args(const ppfs_ecc_ctx* c, const void* image, const ppfs_ecc_file* file, uint64_t offset, uint64_t nbytes,
+    const void* in, uint64_t in_bytes, const void* written, const void* counts, Span& sp)
+{
+    sp = Span { 0, 0, 0, true };
+    if (!c || !file)
+        return fail(PPFS_ECC_EINVAL, "write file: null context or file record");
+    if (((uintptr_t)written | (uintptr_t)counts) & 7u)
+        return fail(PPFS_ECC_EINVAL, "write file: the written word and the counts record are 8-byte aligned");
+    if (nbytes == 0)
+        return 0;
+    if (offset + nbytes < offset || offset + nbytes > file->file_size)
+        return fail(PPFS_ECC_EINVAL, "write file: the range runs past the file's end (a write does not grow the file)");
+    sp = span(file->file_size, c->data, offset, nbytes);
+    if (!sp.ok)
+        return fail(PPFS_ECC_EINVAL, "write file: a codec without payload holds no file");
+    if (c->data > 0xFFFFu)
+        return fail(PPFS_ECC_EINVAL, "write file: payloads past 65,535 bytes do not fit an extent");
+    const int r = walk_args(c, image, true, file, sp.first, sp.count, nullptr, nullptr, counts, "write file");
+    if (r)
+        return r;
+    if (!in || in_bytes < sp.bytes)
+        return fail(PPFS_ECC_EINVAL, "write file: the in buffer is null or shorter than the bytes to write");
     return 0;
 }
 
@@ -246,6 +276,46 @@ extern "C" int ppfs_ecc_read_file_device(ppfs_ecc_ctx* c, uint8_t* d_image, size
     return call_queued(c, r, sp.count, stream, "read file (async)");
 }
 
+// FileIO::writeFile over an existing range (file_io.cpp:46-104): the read's walk and extents with pos pointing
+// into `in`, ppfs_ecc_write_extents_device, then path status over write status and `written`
+extern "C" int ppfs_ecc_write_file_device(ppfs_ecc_ctx* c, const uint8_t* d_in, size_t in_bytes, uint8_t* d_image,
+    size_t image_blocks, const ppfs_ecc_file* file, uint64_t offset, uint64_t nbytes, uint8_t* d_status, uint64_t* d_written,
+    ppfs_ecc_file_counts* d_counts, int write_back, void* stream)
+{
+    Span sp;
+    int r = write_args(c, d_image, file, offset, nbytes, d_in, in_bytes, d_written, d_counts, sp);
+    if (r)
+        return r;
+    hipStream_t s = (hipStream_t)stream;
+    if (stream_capturing(s))
+        return fail(PPFS_ECC_ENOTSUP, "file calls cannot be captured into a graph (shared scratch and staging)");
+    unsigned long long *counts = (unsigned long long*)d_counts, *written = (unsigned long long*)d_written;
+    if (counts)
+        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(*d_counts), s), "file counts clear");
+    if ((r = check_hip(ppfs_file_written_init_launch(written, sp.bytes, s), "file written init")) || sp.count == 0)
+        return r;
+    DeviceWalk w { c, d_image, blocks_seen(image_blocks), file, tree_of(sp.first, sp.count, ipb_of(c->data)), c->data, {},
+        write_back ? 1 : 0, stream };
+    const size_t piece = std::min<uint64_t>(sp.count, PIECE_BLOCKS);
+    const uint64_t off0 = offset % w.ds;
+    uint8_t* scratch = nullptr;
+    if ((r = scrub_scratch(c, scratch_layout(w.tree, w.ds, piece, true, nullptr, nullptr), s, &scratch)))
+        return r;
+    scratch_layout(w.tree, w.ds, piece, true, scratch, &w.x);
+    r = w.levels(nullptr, nullptr, counts);
+    for (uint64_t off = 0; off < sp.count && !r; off += piece) {
+        const uint64_t nb = std::min<uint64_t>(piece, sp.count - off);
+        (void)((r = w.expand(LEVEL_DATA, off, nb, w.x.idx, w.x.path))
+            || (r = check_hip(ppfs_file_extents_launch(w.x.idx, w.x.path, off, nb, off0, sp.bytes, w.ds, w.x.ext, s), "file extents"))
+            || (r = ppfs_ecc_write_extents_device(c, d_in, sp.bytes, d_image, image_blocks, w.x.ext, nb, w.x.rst, stream))
+            || (r = check_hip(ppfs_file_write_merge_launch(w.x.path, w.x.rst, nb, d_status ? d_status + off : nullptr, off, off0,
+                                  sp.bytes, w.ds, written, counts, s),
+                    "file write merge")));
+    }
+    scrub_scratch_used(c, s);
+    return call_queued(c, r, sp.count, stream, "write file (async)");
+}
+
 // ------------------------------------------------------------------------------------------------------
 // Host side: the same plan on the CPU
 // ------------------------------------------------------------------------------------------------------
@@ -374,6 +444,47 @@ extern "C" int ppfs_ecc_read_file_host(ppfs_ecc_ctx* c, uint8_t* image, size_t i
             status[k] = st;
         if (path[k] == STATUS_FAILED)
             std::memset(out + ext[k].pos, 0, ext[k].length);
+        count_host(counts, st, SLOT_FILE);
+    }
+    return 0;
+}
+
+extern "C" int ppfs_ecc_write_file_host(ppfs_ecc_ctx* c, const uint8_t* in, size_t in_bytes, uint8_t* image, size_t image_blocks,
+    const ppfs_ecc_file* file, uint64_t offset, uint64_t nbytes, uint8_t* status, uint64_t* written, ppfs_ecc_file_counts* counts,
+    int write_back)
+{
+    Span sp;
+    int r = write_args(c, image, file, offset, nbytes, in, in_bytes, written, counts, sp);
+    if (r)
+        return r;
+    if (counts)
+        *counts = ppfs_ecc_file_counts {};
+    if (written)
+        *written = sp.bytes;
+    if (sp.count == 0)
+        return 0;
+    HostWalk w { c, image, blocks_seen(image_blocks), file, tree_of(sp.first, sp.count, ipb_of(c->data)), c->data, write_back ? 1 : 0,
+        {}, {}, {}, {} };
+    if ((r = w.levels(nullptr, nullptr, counts)))
+        return r;
+    const HostSrc src = w.src();
+    const uint64_t off0 = offset % w.ds;
+    std::vector<ppfs_ecc_extent> ext(sp.count);
+    std::vector<uint8_t> path(sp.count), wst(sp.count);
+    for (uint64_t k = 0; k < sp.count; ++k) {
+        const Expanded e = expand(w.tree, LEVEL_DATA, k, w.ds, src);
+        const Extent x = extent_of(k, off0, sp.bytes, w.ds);
+        path[k] = e.inherited;
+        ext[k] = ppfs_ecc_extent { x.pos, e.inherited ? NO_BLOCK : e.pointer, (uint16_t)x.offset, (uint16_t)x.length };
+    }
+    if ((r = ppfs_ecc_write_extents_host(c, in, sp.bytes, image, image_blocks, ext.data(), sp.count, wst.data())))
+        return r;
+    for (uint64_t k = sp.count; k-- > 0;) {
+        const uint8_t st = path[k] ? path[k] : wst[k];
+        if (status)
+            status[k] = st;
+        if (written && (st == STATUS_FAILED || st == STATUS_OUT))
+            *written = ext[k].pos;
         count_host(counts, st, SLOT_FILE);
     }
     return 0;

@@ -9,6 +9,10 @@
 //   file_extents_kernel  a piece of file blocks: the ppfs_ecc_extent entries of the read, closed form
 //   file_merge_kernel    path status over read status, zero fill under a failed index block, the counts;
 //                        for a level of the tree also its pointers and statuses into the caller's arrays
+// and of the file write (ppfs_ecc_write_file_*), which reuses the expansion and the extents:
+//   file_written_init_kernel  written = the range's bytes
+//   file_write_merge_kernel   path status over write status, the counts, written lowered to the first
+//                             failing block's position; no payload byte is read or written
 // One lane per output element, 256 lanes a workgroup; consecutive lanes store consecutive elements.
 #include <hip/hip_runtime.h>
 
@@ -125,6 +129,61 @@ __global__ __launch_bounds__(256) void file_merge_kernel(const uint8_t* __restri
     }
 }
 
+// *written = bytes: what a file write reports when no block of its range fails (the write merge lowers it)
+__global__ __launch_bounds__(64) void file_written_init_kernel(unsigned long long* __restrict__ written, uint64_t bytes)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0 && PPFS_DBG_OK(written, 8, written, 8))
+        *written = bytes;
+}
+
+// The merge of a file WRITE over the blocks i0 + i, i < n, of a range of `bytes` bytes: the final status is
+// path[i] where that is non-zero, else wst[i], the write's.  It reads and writes no payload byte.
+//   status_out (may be null)   the final statuses
+//   written (may be null)      lowered to the pos of the first block whose final status is 5 or 9.  pos grows
+//                              with i, so of a wave only its first such lane issues the 64-bit atomicMin
+//   counts (may be null)       file_merge_kernel's tally into the file half
+__global__ __launch_bounds__(256) void file_write_merge_kernel(const uint8_t* __restrict__ path, const uint8_t* __restrict__ wst,
+    uint64_t n, uint8_t* __restrict__ status_out, uint64_t i0, uint64_t off0, uint64_t bytes, uint64_t ds,
+    unsigned long long* __restrict__ written, unsigned long long* __restrict__ counts)
+{
+    __shared__ uint32_t part[4][4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t c[4] = { 0, 0, 0, 0 };
+    for (uint64_t k0 = (uint64_t)blockIdx.x * 256u; k0 < n; k0 += (uint64_t)gridDim.x * 256u) {
+        const uint64_t i = k0 + threadIdx.x;
+        int slot = -1;
+        if (i < n && PPFS_DBG_OK(path + i, 1, path, n)) {
+            const uint32_t p = path[i];
+            const uint32_t s = p ? p : (wst && PPFS_DBG_OK(wst + i, 1, wst, n) ? wst[i] : 0u);
+            slot = fileplan::count_slot(s);
+            if (status_out && PPFS_DBG_OK(status_out + i, 1, status_out, n))
+                status_out[i] = (uint8_t)s;
+        }
+        const unsigned long long stopped = __builtin_amdgcn_ballot_w64(slot == 2 || slot == 3);
+        if (written && stopped && lane == (uint32_t)__builtin_ctzll(stopped) && PPFS_DBG_OK(written, 8, written, 8)) {
+            const uint64_t pos = fileplan::extent_of(i0 + i, off0, bytes, ds).pos;
+            atomicMin(written, (unsigned long long)(pos < bytes ? pos : bytes));
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            c[q] += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(slot == q));
+    }
+    if (!counts)
+        return;
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            part[wave][q] = c[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < 4u) {
+        const uint32_t q = threadIdx.x;
+        const unsigned long long sum = (unsigned long long)part[0][q] + part[1][q] + part[2][q] + part[3][q];
+        if (sum && PPFS_DBG_OK(counts + fileplan::SLOT_FILE + q, 8, counts, 64))
+            atomicAdd(counts + fileplan::SLOT_FILE + q, sum);
+    }
+}
+
 static bool grid_of(uint64_t n, uint32_t& grid)
 {
     const uint64_t g = (n + 255u) / 256u;
@@ -178,6 +237,30 @@ extern "C" hipError_t ppfs_file_merge_launch(const uint8_t* path, const uint8_t*
     const uint32_t grid = (uint32_t)(want < 2048u ? want : 2048u);
     hipLaunchKernelGGL(file_merge_kernel, dim3(grid), dim3(256), 0, s, path, read, n, status_out, pointer_out ? pointer_in : nullptr,
         pointer_out, out, i0, off0, bytes, ds, counts, slot0);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t ppfs_file_written_init_launch(unsigned long long* written, uint64_t bytes, hipStream_t s)
+{
+    if (!written)
+        return hipSuccess;
+    if ((uintptr_t)written & 7u)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(file_written_init_kernel, dim3(1), dim3(64), 0, s, written, bytes);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t ppfs_file_write_merge_launch(const uint8_t* path, const uint8_t* wst, uint64_t n, uint8_t* status_out,
+    uint64_t i0, uint64_t off0, uint64_t bytes, uint64_t ds, unsigned long long* written, unsigned long long* counts, hipStream_t s)
+{
+    if (n == 0 || (!status_out && !written && !counts))
+        return hipSuccess;
+    if (!path || (((uintptr_t)written | (uintptr_t)counts) & 7u) || ds == 0 || off0 >= ds)
+        return hipErrorInvalidValue;
+    const uint64_t want = (n + 255u) / 256u;
+    const uint32_t grid = (uint32_t)(want < 2048u ? want : 2048u);
+    hipLaunchKernelGGL(file_write_merge_kernel, dim3(grid), dim3(256), 0, s, path, wst, n, status_out, i0, off0, bytes, ds, written,
+        counts);
     return hipGetLastError();
 }
 

@@ -10,6 +10,9 @@
 //           merge (statuses, counts, file flags, the caller's level-major arrays)
 //   blocks  per piece of fileplan::PIECE_BLOCKS merged file blocks, cut regardless of file boundaries:
 //           expand; for a read also extents, ppfs_ecc_read_extents_* into the batch's out, merge
+//   write   ppfs_ecc_write_files_*: the same plan under the stricter range rule (a write stays inside the file),
+//           per piece expand, extents, ppfs_ecc_write_extents_* out of the batch's in, the write merge; the
+//           device form first refuses two ranges of one inode record that share a file block
 // The device forms queue all of it on the caller's stream and read nothing back.  The host forms run the
 // same merged plan on the CPU around the *_host list and extent calls.
 #include <hip/hip_runtime.h>
@@ -81,6 +84,46 @@ int read_args(const ppfs_ecc_ctx* c, const void* image, const Plan& plan, const 
         return r;
     if (plan.total.blocks && (!out || out_bytes < plan.total.bytes))
         return fail(PPFS_ECC_EINVAL, (std::string(who) + ": the out buffer is null or shorter than the bytes to deliver").c_str());
+    return 0;
+}
+
+// The checks of a batch WRITE that need no GPU, and its plan: ppfs_ecc_files_plan's slots under the stricter range
+// rule (filesplan::build_write); distinct: also refuse two ranges of one inode record that share a file block
+int write_args(const ppfs_ecc_ctx* c, const void* image, const ppfs_ecc_file* files, const ppfs_ecc_file_range* ranges, size_t nfiles,
+    const void* in, uint64_t in_bytes, const void* flags, const void* written, const void* counts, bool distinct, const char* who,
+    Plan& plan)
+{
+    if (!c)
+        return fail(PPFS_ECC_EINVAL, (std::string(who) + ": null context").c_str());
+    if (nfiles && !files)
+        return fail(PPFS_ECC_EINVAL, (std::string(who) + ": null file records").c_str());
+    if (nfiles >= 0xFFFFFFFFull)
+        return fail(PPFS_ECC_EINVAL, (std::string(who) + ": a batch holds fewer than 2^32 - 1 files").c_str());
+    uint64_t bad = 0;
+    const int b = filesplan::build_write((const uint32_t*)files, (const uint64_t*)ranges, nfiles, c->data, plan, &bad);
+    if (b != filesplan::RANGE_OK)
+        return fail(PPFS_ECC_EINVAL,
+            (std::string(who) + ": file " + std::to_string(bad)
+                + (b == filesplan::BAD_CAPACITY ? ": the range's blocks pass the tree's capacity"
+                                                : ": the range runs past the file's end (a write does not grow the file)"))
+                .c_str());
+    if ((uintptr_t)written & 7u)
+        return fail(PPFS_ECC_EINVAL, (std::string(who) + ": the written array is 8-byte aligned").c_str());
+    if (c->data > 0xFFFFu)
+        return fail(PPFS_ECC_EINVAL, (std::string(who) + ": payloads past 65,535 bytes do not fit an extent").c_str());
+    const int r = walk_args(c, image, plan, nullptr, nullptr, flags, counts, who);
+    if (r)
+        return r;
+    if (plan.total.blocks && (!in || in_bytes < plan.total.bytes))
+        return fail(PPFS_ECC_EINVAL, (std::string(who) + ": the in buffer is null or shorter than the bytes to write").c_str());
+    if (distinct) {
+        const uint64_t f = filesplan::first_repeat(plan);
+        if (f < nfiles)
+            return fail(PPFS_ECC_EINVAL,
+                (std::string(who) + ": file " + std::to_string(f)
+                    + ": its range shares a file block with an earlier range of the same inode (device writes need distinct blocks)")
+                    .c_str());
+    }
     return 0;
 }
 
@@ -335,6 +378,48 @@ extern "C" int ppfs_ecc_read_files_device(ppfs_ecc_ctx* c, uint8_t* d_image, siz
     return call_queued(c, r, nblocks, stream, "read files (async)");
 }
 
+// FileIO::writeFile over an existing range (file_io.cpp:46-104) for every file of a batch: the read's walk and
+// extents with pos pointing into `in`, ppfs_ecc_write_extents_device per piece, then the write merge
+extern "C" int ppfs_ecc_write_files_device(ppfs_ecc_ctx* c, const uint8_t* d_in, size_t in_bytes, uint8_t* d_image,
+    size_t image_blocks, const ppfs_ecc_file* files, const ppfs_ecc_file_range* ranges, size_t nfiles, uint8_t* d_status,
+    uint32_t* d_file_flags, uint64_t* d_written, ppfs_ecc_file_counts* d_counts, int write_back, void* stream)
+{
+    Plan plan;
+    int r = write_args(c, d_image, files, ranges, nfiles, d_in, in_bytes, d_file_flags, d_written, d_counts, true, "write files", plan);
+    if (r)
+        return r;
+    hipStream_t s = (hipStream_t)stream;
+    if ((r = device_begin(s, nfiles, d_file_flags, d_counts)))
+        return r;
+    const uint64_t nblocks = plan.total.blocks;
+    unsigned long long *counts = (unsigned long long*)d_counts, *written = (unsigned long long*)d_written;
+    if (nblocks == 0) { // every range is empty: nothing is written, of nothing
+        if (written && nfiles)
+            HIP_TRY(hipMemsetAsync(written, 0, nfiles * sizeof(uint64_t), s), "files written clear");
+        return 0;
+    }
+    DeviceBatch w { c, d_image, blocks_seen(image_blocks), plan, c->data, write_back ? 1 : 0, stream };
+    const size_t piece = std::min<uint64_t>(nblocks, PIECE_BLOCKS);
+    if ((r = w.setup(piece, true)))
+        return r;
+    (void)((r = check_hip(ppfs_files_written_init_launch(w.x.tables + w.tl.recs, w.nfiles(), written, s), "files written init"))
+        || (r = w.levels(nullptr, nullptr, d_file_flags, counts)));
+    for (uint64_t off = 0; off < nblocks && !r; off += piece) {
+        const uint64_t nb = std::min<uint64_t>(piece, nblocks - off);
+        (void)((r = w.expand(LEVEL_DATA, off, nb, w.x.idx, w.x.path))
+            || (r = check_hip(ppfs_files_extents_launch(w.x.tables + w.tl.recs, w.nfiles(), w.rows(LEVEL_DATA), w.nrows(LEVEL_DATA),
+                                  w.x.idx, w.x.path, off, nb, w.ds, w.x.ext, s),
+                    "files extents"))
+            || (r = ppfs_ecc_write_extents_device(c, d_in, plan.total.bytes, d_image, image_blocks, w.x.ext, nb, w.x.rst, stream))
+            || (r = check_hip(ppfs_files_write_merge_launch(w.x.tables + w.tl.recs, w.nfiles(), w.rows(LEVEL_DATA),
+                                  w.nrows(LEVEL_DATA), w.x.path, w.x.rst, off, nb, d_status ? d_status + off : nullptr, w.ds,
+                                  d_file_flags, written, counts, s),
+                    "files write merge")));
+    }
+    scrub_scratch_used(c, s);
+    return call_queued(c, r, nblocks, stream, "write files (async)");
+}
+
 // ------------------------------------------------------------------------------------------------------
 // Host side: the same merged plan on the CPU
 // ------------------------------------------------------------------------------------------------------
@@ -480,6 +565,49 @@ extern "C" int ppfs_ecc_read_files_host(ppfs_ecc_ctx* c, uint8_t* image, size_t 
             status[e] = st;
         if (path[e] == STATUS_FAILED)
             std::memset(out + ext[e].pos, 0, ext[e].length);
+        w.note(f, st, false);
+    });
+    return 0;
+}
+
+// Repeats are not refused here: ppfs_ecc_write_extents_host cuts its list where a block repeats, so the ranges apply
+// in batch order
+extern "C" int ppfs_ecc_write_files_host(ppfs_ecc_ctx* c, const uint8_t* in, size_t in_bytes, uint8_t* image, size_t image_blocks,
+    const ppfs_ecc_file* files, const ppfs_ecc_file_range* ranges, size_t nfiles, uint8_t* status, uint32_t* file_flags,
+    uint64_t* written, ppfs_ecc_file_counts* counts, int write_back)
+{
+    Plan plan;
+    int r = write_args(c, image, files, ranges, nfiles, in, in_bytes, file_flags, written, counts, false, "write files (host)", plan);
+    if (r)
+        return r;
+    host_begin(nfiles, file_flags, counts);
+    if (written)
+        for (size_t f = 0; f < nfiles; ++f)
+            written[f] = plan.recs[f].bytes;
+    const uint64_t nblocks = plan.total.blocks;
+    if (nblocks == 0)
+        return 0;
+    HostBatch w { c, image, blocks_seen(image_blocks), plan, c->data, write_back ? 1 : 0, file_flags, counts, {}, {}, {}, {} };
+    if ((r = w.levels(nullptr, nullptr)))
+        return r;
+    const HostMem m = w.mem();
+    std::vector<ppfs_ecc_extent> ext(nblocks);
+    std::vector<uint8_t> path(nblocks), wst(nblocks);
+    w.each(LEVEL_DATA, [&](uint32_t f, uint64_t k, uint64_t e) {
+        const FileRec& rec = plan.recs[f];
+        const Expanded x = filesplan::expand_entry(rec, LEVEL_DATA, k, w.ds, m);
+        const Extent at = extent_of(k, rec.off0, rec.bytes, w.ds);
+        path[e] = x.inherited;
+        ext[e] = ppfs_ecc_extent { rec.out_pos + at.pos, x.inherited ? NO_BLOCK : x.pointer, (uint16_t)at.offset, (uint16_t)at.length };
+    });
+    if ((r = ppfs_ecc_write_extents_host(c, in, plan.total.bytes, image, image_blocks, ext.data(), nblocks, wst.data())))
+        return r;
+    w.each(LEVEL_DATA, [&](uint32_t f, uint64_t, uint64_t e) {
+        const uint8_t st = path[e] ? path[e] : wst[e];
+        if (status)
+            status[e] = st;
+        if (written && (st == STATUS_FAILED || st == STATUS_OUT))
+            written[f] = std::min<uint64_t>(written[f], ext[e].pos - plan.recs[f].out_pos);
         w.note(f, st, false);
     });
     return 0;

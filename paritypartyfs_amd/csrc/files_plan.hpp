@@ -27,6 +27,9 @@
 
 #include "file_plan.hpp"
 
+#include <algorithm>
+#include <cstring>
+#include <map>
 #include <vector>
 
 namespace ppfs {
@@ -165,9 +168,21 @@ struct Plan {
     Levels levels {};
     uint64_t count(int level) const { return level < 3 ? total.tree[level] : total.blocks; }
 };
+// The range rule of a WRITE (ppfs_ecc_write_file_*, ppfs_ecc_write_files_*): it stays inside the file as the inode
+// describes it, offset + nbytes <= file_size, and nothing is clamped (FileIO::writeFile would grow the file,
+// file_io.cpp:46-104; growing is the caller's job).  nbytes == 0 is an empty, valid range whatever the offset.
+constexpr int BAD_PAST_END = 3;
+PPFS_HD inline bool write_range_ok(uint64_t file_size, uint64_t offset, uint64_t nbytes)
+{
+    return nbytes == 0 || (offset + nbytes >= offset && offset + nbytes <= file_size);
+}
+
 // files: nfiles records of sixteen dwords (the last one file_size); ranges: nfiles (offset, nbytes) pairs or
-// null for every file whole.  Returns RANGE_OK, or what is wrong with file *bad.
-inline int build(const uint32_t* files, const uint64_t* ranges, uint64_t nfiles, uint64_t ds, Plan& p, uint64_t* bad)
+// null for every file whole.  Returns RANGE_OK, or what is wrong with file *bad, the first file that is refused.
+// write: the batch is a write, whose ranges must also pass write_range_ok (BAD_PAST_END); one that passes is never
+// clamped, so the slots, records and rows are the read's.
+inline int build(const uint32_t* files, const uint64_t* ranges, uint64_t nfiles, uint64_t ds, Plan& p, uint64_t* bad,
+    bool write = false)
 {
     p = Plan {};
     p.slots.resize(nfiles);
@@ -175,7 +190,8 @@ inline int build(const uint32_t* files, const uint64_t* ranges, uint64_t nfiles,
     for (uint64_t f = 0; f < nfiles; ++f) {
         const uint32_t* rec = files + 16u * f;
         const uint64_t offset = ranges ? ranges[2u * f] : 0u, nbytes = ranges ? ranges[2u * f + 1u] : rec[15];
-        const int r = next_slot(rec[15], ds, offset, nbytes, p.total, p.slots[f]);
+        const int r = write && !write_range_ok(rec[15], offset, nbytes) ? BAD_PAST_END
+                                                                        : next_slot(rec[15], ds, offset, nbytes, p.total, p.slots[f]);
         if (r != RANGE_OK) {
             if (bad)
                 *bad = f;
@@ -205,6 +221,70 @@ inline int build(const uint32_t* files, const uint64_t* ranges, uint64_t nfiles,
         level_major(s, p.total);
     }
     return RANGE_OK;
+}
+
+// ---- the write side, host only: the plan of a batch write, and the repeat rule of its device form ----
+inline int build_write(const uint32_t* files, const uint64_t* ranges, uint64_t nfiles, uint64_t ds, Plan& p, uint64_t* bad)
+{
+    return build(files, ranges, nfiles, ds, p, bad, true);
+}
+
+// Two ranges of the SAME inode record (64 identical bytes) whose file-block spans [first, first + blocks)
+// intersect would write one block twice in one device call, where one of the writes is silently lost.  Returns
+// the smallest f for which an earlier g < f has the same record and an intersecting span, or nfiles when
+// there is none.  Spans that merely touch do not intersect; empty ranges take no part.  O(n log n): the
+// files sorted by record (batch order within equal records), then per record the spans go into an ordered map
+// in batch order -- while the spans so far are disjoint, a new one intersects some span exactly when it
+// intersects its neighbour on either side.
+inline uint64_t first_repeat(const Plan& p)
+{
+    const uint64_t n = p.recs.size();
+    std::vector<uint32_t> order;
+    order.reserve(n);
+    for (uint64_t f = 0; f < n; ++f)
+        if (p.recs[f].blocks)
+            order.push_back((uint32_t)f);
+    // a 64-bit hash leads the sort key, so that almost every comparison is one of two integers; equal hashes
+    // fall back on the 64 bytes themselves
+    std::vector<uint64_t> hash(n, 0);
+    for (uint32_t f : order) {
+        uint64_t h = 0xcbf29ce484222325ull;
+        for (int d = 0; d < 16; ++d)
+            h = (h ^ p.recs[f].inode[d]) * 0x100000001b3ull;
+        hash[f] = h;
+    }
+    const auto record_cmp = [&](uint32_t a, uint32_t b) {
+        return hash[a] != hash[b] ? (hash[a] < hash[b] ? -1 : 1) : std::memcmp(p.recs[a].inode, p.recs[b].inode, 64);
+    };
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        const int c = record_cmp(a, b);
+        return c ? c < 0 : a < b;
+    });
+    uint64_t found = n;
+    std::map<uint64_t, uint64_t> spans; // first -> end, disjoint
+    for (size_t i = 0; i < order.size(); ++i) {
+        const bool fresh = i == 0 || record_cmp(order[i - 1], order[i]) != 0;
+        if (fresh)
+            spans.clear();
+        if (fresh && (i + 1 == order.size() || record_cmp(order[i], order[i + 1]) != 0))
+            continue; // the only range of its record
+        const uint32_t f = order[i];
+        if (f >= found)
+            continue; // cannot lower the answer; later files of this record are later still
+        const uint64_t lo = p.recs[f].first, hi = lo + p.recs[f].blocks;
+        const auto next = spans.lower_bound(lo); // the first span starting at or after lo
+        bool hit = next != spans.end() && next->first < hi;
+        if (!hit && next != spans.begin()) {
+            auto before = next;
+            --before;
+            hit = before->second > lo;
+        }
+        if (hit)
+            found = f;
+        else
+            spans.emplace(lo, hi);
+    }
+    return found;
 }
 
 } // namespace filesplan

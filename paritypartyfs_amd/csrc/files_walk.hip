@@ -9,6 +9,10 @@
 //   files_merge_kernel    path status over read status, zero fill under a failed index block within the
 //                         file's own range, the counts, the file flags; for a level of the tree also its
 //                         pointers and statuses into the caller's level-major arrays
+// and of the batch write (ppfs_ecc_write_files_*), which reuses the expansion and the extents:
+//   files_written_init_kernel   written[f] = file f's bytes, one lane per file
+//   files_write_merge_kernel    path status over write status, the counts, the file flags, written[file]
+//                               lowered to the first failing block's position; no payload byte is touched
 // One lane per merged entry, 256 lanes a workgroup; consecutive lanes store consecutive elements.
 //
 // The row lookup: every lane binary-searches the level's table in global memory (owner_of).  The other form
@@ -196,6 +200,84 @@ __global__ __launch_bounds__(256) void files_merge_kernel(FilesTables tb, const 
     }
 }
 
+// written[f] = file f's bytes, one lane per file: what a batch write reports for a file none of whose blocks
+// fails (the write merge lowers it)
+__global__ __launch_bounds__(256) void files_written_init_kernel(const FileRec* __restrict__ recs, uint64_t nfiles,
+    unsigned long long* __restrict__ written)
+{
+    const uint64_t f = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (f < nfiles && PPFS_DBG_OK(recs + f, 128, recs, nfiles * 128) && PPFS_DBG_OK(written + f, 8, written, nfiles * 8))
+        written[f] = recs[f].bytes;
+}
+
+// The merge of a batch WRITE over the merged file blocks e0 + i, i < n: the final status is path[i] where that
+// is non-zero, else wst[i], the write's.  It reads and writes no payload byte.
+//   status_out (may be null)   the final statuses
+//   flags (may be null)        as files_merge_kernel's, the data bits
+//   written (may be null)      written[file] lowered to the block's position within its file's bytes for a final
+//                              status 5 or 9: a 64-bit atomicMin from the first lane of every run of such lanes of
+//                              one file within a wave (positions grow along a file's entries)
+//   counts (may be null)       the tally into the file half
+__global__ __launch_bounds__(256) void files_write_merge_kernel(FilesTables tb, const uint8_t* __restrict__ path,
+    const uint8_t* __restrict__ wst, uint64_t e0, uint64_t n, uint8_t* __restrict__ status_out, uint64_t ds,
+    uint32_t* __restrict__ flags, unsigned long long* __restrict__ written, unsigned long long* __restrict__ counts)
+{
+    __shared__ uint32_t part[4][4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t c[4] = { 0, 0, 0, 0 };
+    for (uint64_t w0 = (uint64_t)blockIdx.x * 256u; w0 < n; w0 += (uint64_t)gridDim.x * 256u) {
+        const uint64_t i = w0 + threadIdx.x;
+        const bool live = i < n && PPFS_DBG_OK(path + i, 1, path, n);
+        uint32_t s = 0;
+        int slot = -1;
+        if (live) {
+            const uint32_t p = path[i];
+            s = p ? p : (wst && PPFS_DBG_OK(wst + i, 1, wst, n) ? wst[i] : 0u);
+            slot = fileplan::count_slot(s);
+            if (status_out && PPFS_DBG_OK(status_out + i, 1, status_out, n))
+                status_out[i] = (uint8_t)s;
+        }
+        const bool bad = slot == 2 || slot == 3, want = live && ((flags && s) || (written && bad));
+        Owner o;
+        o.file = 0xFFFFFFFFu;
+        o.k = 0;
+        o.ok = false;
+        if (kOwnerAllLanes || want)
+            o = owner_of(tb, e0 + w0, n - w0 < 256u ? n - w0 : 256u, e0 + i, want);
+        const bool stop = o.ok && written && bad;
+        const unsigned long long stopped = __builtin_amdgcn_ballot_w64(stop);
+        const uint32_t file_before = (uint32_t)__shfl_up((int)o.file, 1);
+        const bool continues = lane > 0u && ((stopped >> (lane - 1u)) & 1ull) && file_before == o.file;
+        if (o.ok) {
+            const uint32_t bit = filesplan::flag_of(s);
+            if (flags && bit && PPFS_DBG_OK(flags + o.file, 4, flags, tb.nfiles * 4))
+                atomicOr(flags + o.file, bit);
+            if (stop && !continues && PPFS_DBG_OK(written + o.file, 8, written, tb.nfiles * 8)) {
+                const FileRec& rec = tb.recs[o.file];
+                const uint64_t pos = fileplan::extent_of(o.k, rec.off0, rec.bytes, ds).pos;
+                atomicMin(written + o.file, (unsigned long long)(pos < rec.bytes ? pos : rec.bytes));
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            c[q] += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(slot == q));
+    }
+    if (!counts)
+        return;
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            part[wave][q] = c[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < 4u) {
+        const uint32_t q = threadIdx.x;
+        const unsigned long long sum = (unsigned long long)part[0][q] + part[1][q] + part[2][q] + part[3][q];
+        if (sum && PPFS_DBG_OK(counts + fileplan::SLOT_FILE + q, 8, counts, 64))
+            atomicAdd(counts + fileplan::SLOT_FILE + q, sum);
+    }
+}
+
 static bool grid_of(uint64_t n, uint32_t& grid)
 {
     const uint64_t g = (n + 255u) / 256u;
@@ -259,6 +341,34 @@ extern "C" hipError_t ppfs_files_merge_launch(const void* recs, uint64_t nfiles,
     const FilesTables tb { (const FileRec*)recs, nfiles, (const Row*)rows, nrows };
     hipLaunchKernelGGL(files_merge_kernel, dim3(grid), dim3(256), 0, s, tb, path, read, e0, n, status_out,
             pointer_out ? pointer_in : nullptr, pointer_out, out, out_bytes, ds, flags, flag_shift, counts, slot0);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t ppfs_files_written_init_launch(const void* recs, uint64_t nfiles, unsigned long long* written, hipStream_t s)
+{
+    uint32_t grid;
+    if (!written || nfiles == 0)
+        return hipSuccess;
+    if (!recs || nfiles >= 0xFFFFFFFFull || (((uintptr_t)recs | (uintptr_t)written) & 7u) || !grid_of(nfiles, grid))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(files_written_init_kernel, dim3(grid), dim3(256), 0, s, (const FileRec*)recs, nfiles, written);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t ppfs_files_write_merge_launch(const void* recs, uint64_t nfiles, const void* rows, uint64_t nrows,
+    const uint8_t* path, const uint8_t* wst, uint64_t e0, uint64_t n, uint8_t* status_out, uint64_t ds, uint32_t* flags,
+    unsigned long long* written, unsigned long long* counts, hipStream_t s)
+{
+    if (n == 0 || (!status_out && !flags && !written && !counts))
+        return hipSuccess;
+    if (!tables_ok(recs, nfiles, rows, nrows) || !path || ((uintptr_t)flags & 3u) || (((uintptr_t)written | (uintptr_t)counts) & 7u)
+        || ds == 0)
+        return hipErrorInvalidValue;
+    const uint64_t want = (n + 255u) / 256u;
+    const uint32_t grid = (uint32_t)(want < 2048u ? want : 2048u);
+    const FilesTables tb { (const FileRec*)recs, nfiles, (const Row*)rows, nrows };
+    hipLaunchKernelGGL(files_write_merge_kernel, dim3(grid), dim3(256), 0, s, tb, path, wst, e0, n, status_out, ds, flags, written,
+        counts);
     return hipGetLastError();
 }
 

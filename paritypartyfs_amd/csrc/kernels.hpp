@@ -122,4 +122,17 @@ hipError_t ppfs_files_merge_launch(const void* recs, uint64_t nfiles, const void
     const uint8_t* read, uint64_t e0, uint64_t n, uint8_t* status_out, const uint32_t* pointer_in, uint32_t* pointer_out,
     uint8_t* out, uint64_t out_bytes, uint64_t ds, uint32_t* flags, uint32_t flag_shift, unsigned long long* counts, int slot0,
     hipStream_t s);
+// the file writes (file_path.cpp, files_path.cpp ppfs_ecc_write_file_* / ppfs_ecc_write_files_*): the walk's expand and
+// extents launchers above, then
+// written_init: *written = bytes / written[f] = recs[f].bytes (8-byte aligned; null: nothing).
+// write_merge: status_out[i] = path[i] ? path[i] : wst[i]; counts' file half; flags[file] (batch); written (the file's
+// entry in the batch) lowered by a 64-bit atomicMin to the position, within the range's bytes, of a block whose final
+// status is 5 or 9.  No payload byte is read or written.
+hipError_t ppfs_file_written_init_launch(unsigned long long* written, uint64_t bytes, hipStream_t s);
+hipError_t ppfs_file_write_merge_launch(const uint8_t* path, const uint8_t* wst, uint64_t n, uint8_t* status_out, uint64_t i0,
+    uint64_t off0, uint64_t bytes, uint64_t ds, unsigned long long* written, unsigned long long* counts, hipStream_t s);
+hipError_t ppfs_files_written_init_launch(const void* recs, uint64_t nfiles, unsigned long long* written, hipStream_t s);
+hipError_t ppfs_files_write_merge_launch(const void* recs, uint64_t nfiles, const void* rows, uint64_t nrows, const uint8_t* path,
+    const uint8_t* wst, uint64_t e0, uint64_t n, uint8_t* status_out, uint64_t ds, uint32_t* flags, unsigned long long* written,
+    unsigned long long* counts, hipStream_t s);
 }

@@ -603,6 +603,99 @@ class EccEngine:
             self._u32_ptr(file_flags), byref(rec), int(bool(write_back))))
         return FileCounts(*[int(getattr(rec, k)) for k in FILE_COUNT_FIELDS])
 
+    # ---------------- write a file range from its inode (ppfs_ecc_write_file_*, ppfs_ecc_write_files_*) ----------------
+    # FileIO::writeFile over an EXISTING range: offset + nbytes <= file_size, nothing grows and no inode is updated.
+    # `data` holds the range's bytes (a batch: file f's at [slot.out_pos, + slot.bytes) of files_plan).  `written`: the
+    # bytes that precede the first block with final status 5 or 9 (the range's bytes when none fails), one per file.
+    # The device forms return (counts, written) as CUDA int64 tensors or None, the host forms (FileCounts, written).
+    @staticmethod
+    def _device_written(written, n: int):
+        if written is None or written is False:
+            return None
+        import torch
+
+        if written is True:
+            return torch.zeros(max(n, 1), dtype=torch.int64, device="cuda")
+        if not getattr(written, "is_cuda", False) or written.dtype != torch.int64 or not written.is_contiguous() \
+                or written.dim() != 1 or written.numel() < n:
+            raise ValueError(f"written: None, True or a contiguous 1-D CUDA int64 tensor of >= {n} elements")
+        return written
+
+    def _write_file_check(self, kind, data, image, file, offset, nbytes, status):
+        f = self._file(file)
+        if image is None:
+            raise ValueError("image: required")
+        if offset < 0 or nbytes < 0:
+            raise ValueError("offset and nbytes must be >= 0")
+        if nbytes and offset + nbytes > int(f["file_size"][0]):
+            raise ValueError("the range runs past the file's end: a write does not grow the file")
+        _, nblocks, _ = self.file_span(f, offset, nbytes)
+        if nbytes and data is None:
+            raise ValueError("data: required")
+        _need("image", image, 0, kind)
+        _need("data", data, nbytes, kind)
+        _need("status", status, nblocks, kind)
+        _ptr(image), _ptr(data), _ptr(status)  # contiguous uint8
+        return f, _size(image) // self.raw_block_size, 0 if data is None else _size(data)
+
+    def write_file(self, data, image, file, offset: int, nbytes: int, status=None, written=None, counts=None,
+                   write_back: bool = True, stream=None):
+        """Device file write (ppfs_ecc_write_file_device): data[0, nbytes) replaces the file range; status: one byte per
+        file block touched; write_back applies to the index blocks.  Never synchronises."""
+        f, blocks, in_bytes = self._write_file_check("device", data, image, file, offset, nbytes, status)
+        d_counts, d_written = self._device_counts(counts), self._device_written(written, 1)
+        check(lib().ppfs_ecc_write_file_device(
+            self._h, _ptr(data), in_bytes, _ptr(image), blocks, f.ctypes.data, int(offset), int(nbytes), _ptr(status),
+            None if d_written is None else d_written.data_ptr(), None if d_counts is None else d_counts.data_ptr(),
+            int(bool(write_back)), _stream_handle(stream)))
+        return d_counts, d_written
+
+    def write_file_host(self, data: Optional[np.ndarray], image: np.ndarray, file, offset: int, nbytes: int,
+                        status: Optional[np.ndarray] = None, write_back: bool = True):
+        f, blocks, in_bytes = self._write_file_check("host", data, image, file, offset, nbytes, status)
+        rec, written = _native.FileCounts(), ctypes.c_uint64(0)
+        check(lib().ppfs_ecc_write_file_host(self._h, _ptr(data), in_bytes, _ptr(image), blocks, f.ctypes.data, int(offset),
+                                             int(nbytes), _ptr(status), byref(written), byref(rec), int(bool(write_back))))
+        return FileCounts(*[int(getattr(rec, n)) for n in FILE_COUNT_FIELDS]), int(written.value)
+
+    def _write_files_check(self, kind, data, image, files, ranges, status, file_flags):
+        f, r = self._files(files, ranges)
+        sizes = f["file_size"].astype(np.uint64)
+        if r is not None and f.size:
+            over = np.flatnonzero((r[:, 1] > 0) & ((r[:, 0] + r[:, 1] < r[:, 0]) | (r[:, 0] + r[:, 1] > sizes)))
+            if over.size:
+                raise ValueError(f"file {int(over[0])}: the range runs past the file's end: a write does not grow the file")
+        args = self._files_check(kind, image, f, r, file_flags=file_flags, status=status)
+        total = int(sizes.sum() if r is None else r[:, 1].sum())  # a write is never clamped
+        if total and data is None:
+            raise ValueError("data: required")
+        _need("data", data, total, kind)
+        _ptr(data)  # contiguous uint8
+        return args
+
+    def write_files(self, data, image, files, ranges=None, status=None, file_flags=None, written=None, counts=None,
+                    write_back: bool = True, stream=None):
+        """Device write of a batch (ppfs_ecc_write_files_device): data[slot.out_pos, + slot.bytes) replaces file f's
+        range.  Two ranges of one inode record that share a file block are refused.  Never synchronises."""
+        fp, rp, n, f, r, blocks = self._write_files_check("device", data, image, files, ranges, status, file_flags)
+        d_counts, d_written = self._device_counts(counts), self._device_written(written, n)
+        check(lib().ppfs_ecc_write_files_device(
+            self._h, _ptr(data), 0 if data is None else _size(data), _ptr(image), blocks, fp, rp, n, _ptr(status),
+            self._u32_ptr(file_flags), None if d_written is None else d_written.data_ptr(),
+            None if d_counts is None else d_counts.data_ptr(), int(bool(write_back)), _stream_handle(stream)))
+        return d_counts, d_written
+
+    def write_files_host(self, data: Optional[np.ndarray], image: np.ndarray, files, ranges=None,
+                         status: Optional[np.ndarray] = None, file_flags: Optional[np.ndarray] = None,
+                         write_back: bool = True):
+        """Host write of a batch; repeats are not refused: ranges apply in batch order."""
+        fp, rp, n, f, r, blocks = self._write_files_check("host", data, image, files, ranges, status, file_flags)
+        rec, written = _native.FileCounts(), np.zeros(max(n, 1), np.uint64)
+        check(lib().ppfs_ecc_write_files_host(
+            self._h, _ptr(data), 0 if data is None else _size(data), _ptr(image), blocks, fp, rp, n, _ptr(status),
+            self._u32_ptr(file_flags), written.ctypes.data, byref(rec), int(bool(write_back))))
+        return FileCounts(*[int(getattr(rec, k)) for k in FILE_COUNT_FIELDS]), written[:n]
+
 
 # ppfs_ecc_scrub_counts: the host forms return it as this tuple, the device forms as a CUDA int64 tensor
 # in the same field order (ScrubCounts(*tensor.tolist()) after synchronising)
