@@ -29,6 +29,7 @@
 #include "host_tables.hpp"
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "resident_plan.hpp"
 
 using namespace ppfs;
 
@@ -370,6 +371,9 @@ extern "C" int ppfs_ecc_create(const ppfs_ecc_params* params, int device, ppfs_e
             // PPFS_ECC_LIST_DIRECT=0: list calls of this context take the staged path (A/B runs)
             const char* ld = std::getenv("PPFS_ECC_LIST_DIRECT");
             c->list_direct = rs_wb_direct(c) && !(ld && ld[0] == '0' && !ld[1]);
+            // PPFS_ECC_RESIDENT_MIB: the cache-resident codeword prefix of this context's 2t <= 8 ticket
+            // encodes (resident_plan.hpp), 0 = off
+            c->resident_bytes = plan::resident_env(std::getenv("PPFS_ECC_RESIDENT_MIB"));
         } else {
             tables.assign(1024 + 256, 0);
             build_gf_block(tables.data());
@@ -632,7 +636,8 @@ static int ppfs_ecc_encode_device_impl(ppfs_ecc_ctx* c, const uint8_t* d_data, u
         if (c->rs_fast && aligned16(d_data) && aligned16(d_raw)) {
             const TkSets t = ctr_for(c, s, 0);
             return check_hip(
-                tk_commit(c, t, ppfs_rs_fast_encode(c->rs_t2, d_data, d_raw, nblocks, c->d_tables, s, t.mine, t.clear)),
+                tk_commit(c, t, ppfs_rs_fast_encode(c->rs_t2, d_data, d_raw, nblocks, c->d_tables, s, t.mine, t.clear,
+                                plan::resident_tiles(nblocks, c->resident_bytes))),
                 "rs encode");
         }
         if (c->rs_fast) {

@@ -144,6 +144,10 @@ struct ppfs_ecc_ctx {
     // list decodes, encodes and writes go through the one-kernel direct paths (rs_wg_list.hpp): RS(255, 255-2t), 2t <= 8,
     // unless PPFS_ECC_LIST_DIRECT=0 was set when the context was created (list_path.cpp)
     bool list_direct = false;
+    // the cache-resident codeword prefix of the 2t <= 8 ticket encode, bytes (resident_plan.hpp): the
+    // default, or PPFS_ECC_RESIDENT_MIB as set when the context was created; each encode launch takes
+    // plan::resident_tiles(its blocks, this)
+    uint64_t resident_bytes = 0;
     // byte-extent calls (extent_path.cpp): the decoded payloads of one piece and the staged index of
     // its entries, made at the first extent call; ordered by list_ev like the rows they go with
     uint8_t* d_ext = nullptr;

@@ -15,8 +15,9 @@
 
 extern "C" {
 int ppfs_rs_fast_supported(int n, int t2);
+// res_tiles: the batch's resident prefix in tiles (resident_plan.hpp; the 2t <= 8 ticket encode)
 hipError_t ppfs_rs_fast_encode(int t2, const uint8_t* d, uint8_t* r, uint64_t nb, const uint8_t* tab, hipStream_t s,
-    uint32_t* ctr, uint32_t* ctr_clear);
+    uint32_t* ctr, uint32_t* ctr_clear, uint64_t res_tiles);
 const char* ppfs_rs_fast_path(int t2);
 hipError_t ppfs_flag_launch(uint32_t* flag, uint32_t v, hipStream_t s);
 hipError_t ppfs_rs_generic_server_launch(int n, int t2, ppfs::SrvBox* box, uint8_t* zc, uint64_t zc_bytes,

@@ -52,11 +52,16 @@ static uint32_t rs_tile_grid(uint64_t nb, int wpc, int tb = 64)
 
 #if PPFS_T2 <= 8
 // 2t <= 8 (rs_wg.hpp).  Encode: a ring of 3 LDS tile buffers, 2 workgroups per CU;
-// decode: double-buffered, 3 per CU.  Non-temporal output stores in both.
+// decode: double-buffered, 3 per CU.  Non-temporal output stores in both, except the ticket encode's
+// codeword stores inside the resident prefix (res_tiles, rs_wg_tk.hpp).
 // The static-walk encode fits as many workgroups as its LDS allows (at most 4); the ticket encode
 // runs 2 per CU (its LDS carries the ticket slots).
 constexpr int fit_wpc(int bytes, int most) { return 163840 / bytes < most ? 163840 / bytes : most; }
-constexpr int TK_NTST = 1; // ticket kernels' output stores non-temporal (plain stores: slower)
+// The ticket kernels' streaming stores -- the decode's payloads and the encode's codewords past the
+// resident prefix -- are non-temporal (every output plain: slower).  The encode's
+// codeword stores inside the prefix are plain whatever this says, and its payload loads are
+// non-temporal (rs_wg_tk.hpp; DESIGN.md A, resident prefix).
+constexpr int TK_NTST = 1;
 constexpr int ENC_NBUF = 3, ENC_WPC = 2, DEC_NBUF = 2, DEC_WPC = 3;
 constexpr int ENC_WPC_STATIC = fit_wpc(wg::lds_bytes<PPFS_T2, false, ENC_NBUF>(), 4);
 #elif PPFS_T2 == 32
@@ -81,14 +86,17 @@ static uint32_t rs_grid(uint64_t nb)
 #endif
 
 // ctr / ctr_clear: the stream's ticket-counter set for this launch and the one to zero (the previous
-// launch's; api.cpp ctr_for alternates them), or null: the static walk
+// launch's; api.cpp ctr_for alternates them), or null: the static walk.  res_tiles: the leading tiles
+// whose codewords the 2t <= 8 ticket encode leaves cache-resident (resident_plan.hpp); every other
+// kernel ignores it
 extern "C" hipError_t PPFS_CAT(ppfs_rs_fast_encode_t, PPFS_T2)(const uint8_t* d, uint8_t* r, uint64_t nb,
-    const uint8_t* tab, hipStream_t s, [[maybe_unused]] uint32_t* ctr, [[maybe_unused]] uint32_t* ctr_clear)
+    const uint8_t* tab, hipStream_t s, [[maybe_unused]] uint32_t* ctr, [[maybe_unused]] uint32_t* ctr_clear,
+    [[maybe_unused]] uint64_t res_tiles)
 {
 #if PPFS_T2 <= 8
     if (ctr && ctr_clear)
         PPFS_LAUNCH((wg::rs_wg_encode_tk_kernel<PPFS_T2, ENC_WPC, TK_NTST>), dim3(rs_tile_grid(nb, ENC_WPC)), dim3(256), 0, s,
-            d, r, nb, tab, ctr, ctr_clear);
+            d, r, nb, tab, ctr, ctr_clear, res_tiles);
     else
         PPFS_LAUNCH((wg::rs_wg_encode_kernel<PPFS_T2, ENC_NBUF, ENC_WPC_STATIC, 3, 1, false>), dim3(rs_tile_grid(nb, ENC_WPC_STATIC)),
             dim3(256), 0, s, d, r, nb, tab);

@@ -241,7 +241,7 @@ using namespace ppfs;
 
 #define X(T)                                                                                                           \
     extern "C" hipError_t ppfs_rs_fast_encode_t##T(const uint8_t*, uint8_t*, uint64_t, const uint8_t*, hipStream_t,   \
-        uint32_t*, uint32_t*);                                                                                         \
+        uint32_t*, uint32_t*, uint64_t);                                                                               \
     extern "C" hipError_t ppfs_rs_fast_decode_t##T(uint8_t*, uint8_t*, uint8_t*, uint64_t, const uint8_t*, int,       \
         hipStream_t, uint32_t*, uint32_t*, uint8_t*);
 PPFS_RS_CASES(X)
@@ -271,12 +271,12 @@ extern "C" int ppfs_rs_fast_tables_bytes(int t2)
 }
 
 extern "C" hipError_t ppfs_rs_fast_encode(int t2, const uint8_t* d, uint8_t* r, uint64_t nb, const uint8_t* tab,
-    hipStream_t s, uint32_t* ctr, uint32_t* ctr_clear)
+    hipStream_t s, uint32_t* ctr, uint32_t* ctr_clear, uint64_t res_tiles)
 {
     switch (t2) {
 #define X(T)                                                                                                           \
     case T:                                                                                                            \
-        return ppfs_rs_fast_encode_t##T(d, r, nb, tab, s, ctr, ctr_clear);
+        return ppfs_rs_fast_encode_t##T(d, r, nb, tab, s, ctr, ctr_clear, res_tiles);
         PPFS_RS_CASES(X)
 #undef X
     default:

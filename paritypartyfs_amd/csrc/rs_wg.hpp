@@ -56,13 +56,20 @@ __device__ __forceinline__ void barrier_lds()
 // Issued from inline asm on purpose: hipcc tracks a builtin LDS-DMA and then waits vmcnt(0) before
 // every later LDS read, which would drain the next tile's prefetch.  The waits for these loads are
 // the explicit counted vmcnt in the kernels.  (M0 write -> LDS-DMA needs one wait state.)
+// NT = 1: the non-temporal flavour (the ticket kernels' streams that nobody reads again, rs_wg_tk.hpp):
+// one vector-memory instruction as well, so every vmcnt count holds for either flavour.
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm" // m0 is reserved; nothing else in these kernels uses it
-__device__ __forceinline__ void dma16(const uint8_t* g, uint32_t lds_base)
+template <int NT = 0> __device__ __forceinline__ void dma16(const uint8_t* g, uint32_t lds_base)
 {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g),
-                 "s"(lds_base)
-                 : "memory", "m0");
+    if constexpr (NT)
+        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off nt" ::"v"(g),
+                     "s"(lds_base)
+                     : "memory", "m0");
+    else
+        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g),
+                     "s"(lds_base)
+                     : "memory", "m0");
 }
 #pragma clang diagnostic pop
 

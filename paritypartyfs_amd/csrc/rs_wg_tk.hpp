@@ -17,6 +17,16 @@
 // meanwhile and takes the first dynamic ticket.  Tickets continue after the static tiles of the XCD.
 // A workgroup's tiles increase, so it stops at its first tile past the batch without skipping one.
 //
+// Resident prefix (the encode's res_tiles, resident_plan.hpp): tiles with index < res_tiles are the
+// part of the codeword image meant to stay in the 256 MiB Infinity Cache from the encode to whoever
+// touches the codewords next.  The encode stores a prefix tile's codewords plainly and every other tile
+// non-temporally, and loads its payloads non-temporally throughout, so that the codewords are the only
+// stream of the kernel that allocates.  The choice is wave-uniform and swaps one vector-memory
+// instruction for another, so the counted vmcnt waits are the same.  res_tiles = 0: every tile streams.
+// The partial last tile is staged by plain loads and stored by plain stores whatever its index (at most
+// 16 KiB).  The decode is as it was: default-policy codeword loads for every tile (non-temporal loads of
+// the tiles past the prefix cost the step 4-18 %), non-temporal payload stores.
+//
 // This file holds the ticket walk, its loader (dma_tile192, dma_tables_w0) and the encode's scheduled
 // emission; the partial tile and the decode's emission are rs_wg.hpp's tile phases.
 #include "rs_wg.hpp"
@@ -31,7 +41,8 @@ template <int NPIECE> constexpr uint32_t dma_count(uint32_t wave)
     return (uint32_t)(NPIECE / 192) + ((NPIECE % 192) > (int)(64u * (wave - 1u)) ? 1u : 0u);
 }
 
-template <int NPIECE>
+// NT = 1: non-temporal LDS-DMA (rs_wg.hpp dma16), the same instruction count
+template <int NPIECE, int NT = 0>
 __device__ __forceinline__ void dma_tile192(uint8_t* dst, const uint8_t* __restrict__ src, uint32_t tid,
     [[maybe_unused]] const uint8_t* gbase, [[maybe_unused]] uint64_t extent)
 {
@@ -46,10 +57,10 @@ __device__ __forceinline__ void dma_tile192(uint8_t* dst, const uint8_t* __restr
         const uint32_t p = w + 192u * (uint32_t)k;
         if ((k + 1) * 192 <= NPIECE) {
             if (PPFS_DBG_OK(src + (size_t)p * 16, 16, gbase, extent))
-                dma16(src + (size_t)p * 16, __builtin_amdgcn_readfirstlane(lbase + 3072u * (uint32_t)k));
+                dma16<NT>(src + (size_t)p * 16, __builtin_amdgcn_readfirstlane(lbase + 3072u * (uint32_t)k));
         } else if (last_round) {
             if (p < (uint32_t)NPIECE && PPFS_DBG_OK(src + (size_t)p * 16, 16, gbase, extent))
-                dma16(src + (size_t)p * 16, __builtin_amdgcn_readfirstlane(lbase + 3072u * (uint32_t)k));
+                dma16<NT>(src + (size_t)p * 16, __builtin_amdgcn_readfirstlane(lbase + 3072u * (uint32_t)k));
         }
     }
 }
@@ -94,6 +105,12 @@ __device__ __forceinline__ void dma_tables_w0(uint8_t* dst, const uint8_t* __res
         if ((k + 1) * 64 <= NP || p < (uint32_t)NP)
             dma16(tables + 16u * p, lbase + 1024u * (uint32_t)k);
     }
+}
+
+// tile q lies in the resident prefix: the same for every lane, and said so to the compiler (a scalar branch)
+__device__ __forceinline__ bool tk_resident(uint64_t q, uint64_t res_tiles)
+{
+    return __builtin_amdgcn_readfirstlane((uint32_t)(q < res_tiles)) != 0u;
 }
 
 // XCD-local tile numbering: workgroup b sits on counter xc = b % nx with rank b / nx among the gx
@@ -198,7 +215,7 @@ template <int T2> __device__ __forceinline__ uint32_t sched_enc_src(uint32_t p)
 template <int T2, int WPC = 2, int NTST = 1>
 __global__ __launch_bounds__(256, WPC) void rs_wg_encode_tk_kernel(const uint8_t* __restrict__ data,
     uint8_t* __restrict__ raw, uint64_t nblocks, const uint8_t* __restrict__ tables, uint32_t* __restrict__ ctr,
-    uint32_t* __restrict__ ctr_clear)
+    uint32_t* __restrict__ ctr_clear, uint64_t res_tiles)
 {
     constexpr int NBUF = 3;
     using L = RsWgLayout<T2>;
@@ -237,10 +254,10 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_encode_tk_kernel(const uint8_t
     uint32_t hist = 0;
     if (dmaw) {
         if (q0 < nfull)
-            dma_tile192<IN_PIECES>(lds + D::OFF_BUF + PAD, data + q0 * (TB * K), tid, data, nblocks * K);
+            dma_tile192<IN_PIECES, 1>(lds + D::OFF_BUF + PAD, data + q0 * (TB * K), tid, data, nblocks * K);
         const bool go = q1 < nfull;
         if (go)
-            dma_tile192<IN_PIECES>(lds + D::OFF_BUF + BUF + PAD, data + q1 * (TB * K), tid, data, nblocks * K);
+            dma_tile192<IN_PIECES, 1>(lds + D::OFF_BUF + BUF + PAD, data + q1 * (TB * K), tid, data, nblocks * K);
         hist = go ? 1u : 0u;
     } else {
         dma_tables_w0<L::SL5_BYTES>(lds, tables + L::OFF_SL5, lane);
@@ -297,7 +314,7 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_encode_tk_kernel(const uint8_t
         const uint32_t buf = D::OFF_BUF + cur * BUF, par = D::OFF_PAR + pc * 512u;
         const bool go = ahead < nfull;
         if (dmaw && go)
-            dma_tile192<IN_PIECES>(lds + D::OFF_BUF + ring_add(cur, NBUF - 1, NBUF) * BUF + PAD, data + ahead * (TB * K),
+            dma_tile192<IN_PIECES, 1>(lds + D::OFF_BUF + ring_add(cur, NBUF - 1, NBUF) * BUF + PAD, data + ahead * (TB * K),
                 tid, data, nblocks * K);
         hist = (hist << 1) | (go ? 1u : 0u);
         PPFS_TK_MARK(1);
@@ -336,11 +353,22 @@ __global__ __launch_bounds__(256, WPC) void rs_wg_encode_tk_kernel(const uint8_t
         // stores in the natural order: a wave writes 1 KiB of consecutive output per instruction
         // (round 4: stored straight from the schedule's lanes, 128-byte runs from four blocks, the
         // t = 3 encode ran at half speed -- partial lines everywhere)
+        // a tile of the resident prefix (wave-uniform): plain stores, its lines stay in the cache
+        // for whoever reads the codewords next; the same 4 stores either way (the vmcnt counts below)
+        if (tk_resident(q0, res_tiles)) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t p = tid + 256u * k;
-            if ((k < 3 || p < (uint32_t)OUT_PIECES) && PPFS_DBG_OK(dst + 16u * p, 16, raw, nblocks * 255u))
-                st_nt<NTST>(dst + 16u * p, *(const uint4*)(lds + OFF_STG + 16u * p));
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t p = tid + 256u * k;
+                if ((k < 3 || p < (uint32_t)OUT_PIECES) && PPFS_DBG_OK(dst + 16u * p, 16, raw, nblocks * 255u))
+                    st_nt<0>(dst + 16u * p, *(const uint4*)(lds + OFF_STG + 16u * p));
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t p = tid + 256u * k;
+                if ((k < 3 || p < (uint32_t)OUT_PIECES) && PPFS_DBG_OK(dst + 16u * p, 16, raw, nblocks * 255u))
+                    st_nt<NTST>(dst + 16u * p, *(const uint4*)(lds + OFF_STG + 16u * p));
+            }
         }
         ++iter;
         PPFS_TK_MARK(4);
