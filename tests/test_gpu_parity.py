@@ -372,7 +372,9 @@ def test_hamming_matches_oracle(oracle, bs, nb):
     persistent wave walk several blocks (next-block prefetch) and end on a ragged last block.
     bs 1, 2, 4 (block_size_power 0-2, hamming_block_device.cpp:11-19) run the thread-per-block
     kernels: 0 / 8 / 24 payload bits, tail bits 13-15 / 30-31 kept from the old block, and at
-    power 0 used bits {1, 2, 4} only."""
+    power 0 used bits {1, 2, 4} only.  The flips here are uniform over the block; the cases aimed
+    at a position (bit 0, parity positions, the head, L, the tail, miscorrections) live in
+    tests/test_gpu_bit_branches.py."""
     eng = EccEngine(ECC_HAMMING, bs)
     ds = oracle.ham_data_size(bs)
     assert (eng.raw_block_size, eng.data_size) == (bs, ds)
