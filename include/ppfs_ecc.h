@@ -99,6 +99,28 @@ const char* ppfs_ecc_kernel_name(const ppfs_ecc_ctx* ctx);
 const char* ppfs_ecc_stream_kernel_name(ppfs_ecc_ctx* ctx, void* stream);
 
 /*
+ * Device pointers of the three contiguous calls below.  A call may name any sub-range of a larger
+ * buffer (blocks [first, first + n): d_raw + first * rawBlockSize(), d_data + first * dataSize(),
+ * d_status + first); it touches the rows of its nblocks blocks only.  Per codec:
+ *   RS, fast paths (rawBlockSize() == 255 and 2t one of 2, 4, 6, 8, 10, 16, 32; ppfs_ecc_kernel_name()
+ *       is not "rs-generic-lfsr"): d_raw, and the d_data and d_status the call passes, must be 16-byte
+ *       aligned, else PPFS_ECC_EINVAL with nothing queued or written.  The write call is its decode
+ *       (d_raw, a caller's d_status) and its encode (d_data, d_raw): a d_status inherits the decode's
+ *       rule, a NULL one is replaced by the context's own aligned array.
+ *   RS, generic path (shortened codes, every other 2t): any address, d_spill included.
+ *   Hamming: d_raw must be 16-byte aligned when rawBlockSize() >= 8, else PPFS_ECC_EINVAL with
+ *       nothing queued or written; d_data and d_status may have any address, and for blocks of 1, 2
+ *       and 4 bytes d_raw too.
+ *   CRC, parity: any address.
+ * 1, 2 and 4 KiB CRC (degree <= 32), Hamming and parity contexts run their streaming kernels when
+ * d_data and d_raw are 16-byte aligned (a NULL d_data counts as aligned) and the generic
+ * wave-per-block kernels otherwise -- same results, lower rate;
+ * ppfs_ecc_kernel_name() names the streaming path either way.  d_status may always have any address.
+ * hipMalloc and torch allocations are 256-byte aligned; a sub-range is aligned when its offsets are
+ * multiples of 16.
+ */
+
+/*
  * Encode nblocks full payloads.  raw is read-modify-write: bits the codec does not define
  * (CRC unused tail bits when degree % 8 != 0, Hamming bits after the last data bit) keep
  * raw's previous contents exactly as the reference's writeBlock keeps the old block's.

@@ -755,6 +755,8 @@ static int ppfs_ecc_write_device_impl(ppfs_ecc_ctx* c, const uint8_t* d_data, ui
     case PPFS_ECC_REED_SOLOMON:
         // old block decoded for its status (correction event) only; the new codeword does
         // not depend on it (rs_block_device.cpp:61-93)
+        if (c->rs_fast && !aligned16(d_data)) // the encode's rule, before the decode writes a status
+            return fail(PPFS_ECC_EINVAL, "rs write: device pointers must be 16-byte aligned");
         if ((r = ppfs_ecc_decode_device(c, d_raw, nullptr, st, nblocks, 0, nullptr, stream)))
             return r;
         return ppfs_ecc_encode_device(c, d_data, d_raw, nblocks, stream);

@@ -31,7 +31,8 @@ constexpr int BK_BUF = 4096 + 64; // per-wave LDS block buffer (with slack for f
 // ------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t lds_dw(const uint8_t* l, uint32_t off) { return *(const uint32_t*)(l + off); }
 
-// LDS [0,n) <- global src[0,n); src may have any alignment; never reads outside [src, src+n).
+// LDS [0,n) <- global src[0,n); src may have any alignment; reads [src, src+n) and, for a src that is
+// not 4-byte aligned, the rest of the aligned dword that holds src[0] (up to 3 bytes before it).
 __device__ __forceinline__ void wave_g2l(uint8_t* l, const uint8_t* __restrict__ src, uint32_t n, uint32_t lane)
 {
     const uint32_t a = (uint32_t)((uintptr_t)src & 3u);
@@ -854,6 +855,13 @@ extern "C" hipError_t ppfs_crc_fast_check(const uint8_t*, uint8_t*, uint8_t*, ui
 // the CRC fast path (n <= 32, 1-4 KiB blocks) reads its tables after the generic ones
 extern "C" int ppfs_crc_fast_supported(uint32_t bs, uint32_t n) { return ppfs_bitfast_supported(bs) && n <= 32; }
 
+// The streaming kernels address payload and raw rows as 16-byte pieces (and dwords) counted from the
+// buffer's base, so they take 16-byte aligned payload and raw pointers only (a null one counts as
+// aligned); any other sub-range of a buffer goes to the kernels above, which take any address (Hamming:
+// any payload address, api.cpp refuses a misaligned raw one).  status and skip are touched a byte at a
+// time by every kernel and may have any address.
+static bool bf_aligned(const void* data, const void* raw) { return (((uintptr_t)data | (uintptr_t)raw) & 15u) == 0; }
+
 static uint32_t bk_grid(uint64_t nb)
 {
     uint64_t g = (nb + BK_WAVES - 1) / BK_WAVES;
@@ -872,7 +880,7 @@ extern "C" int ppfs_crc_tables_bytes(void) { return CRC_TBL_BYTES; }
 extern "C" hipError_t ppfs_crc_encode(const uint8_t* d, uint8_t* r, const uint8_t* skip, uint64_t nb, uint32_t bs,
     uint32_t ds, uint32_t n, uint64_t mask, const uint8_t* tab, hipStream_t s)
 {
-    if (ppfs_crc_fast_supported(bs, n))
+    if (ppfs_crc_fast_supported(bs, n) && bf_aligned(d, r))
         return ppfs_crc_fast_encode(d, r, skip, nb, bs, ds, n, mask, tab + CRC_TBL_BYTES, s);
     CrcArgs a { bs, ds, n, (ds + 63) / 64, (n + 3) / 4, mask };
     hipLaunchKernelGGL(crc_encode_kernel, dim3(bk_grid(nb)), dim3(256), 0, s, d, r, skip, nb, a, tab);
@@ -882,7 +890,7 @@ extern "C" hipError_t ppfs_crc_encode(const uint8_t* d, uint8_t* r, const uint8_
 extern "C" hipError_t ppfs_crc_check(const uint8_t* r, uint8_t* d, uint8_t* st, uint64_t nb, uint32_t bs, uint32_t ds,
     uint32_t n, uint64_t mask, const uint8_t* tab, hipStream_t s)
 {
-    if (ppfs_crc_fast_supported(bs, n))
+    if (ppfs_crc_fast_supported(bs, n) && bf_aligned(d, r))
         return ppfs_crc_fast_check(r, d, st, nb, bs, ds, n, mask, tab + CRC_TBL_BYTES, s);
     CrcArgs a { bs, ds, n, (ds + 63) / 64, (n + 3) / 4, mask };
     hipLaunchKernelGGL(crc_check_kernel, dim3(bk_grid(nb)), dim3(256), 0, s, r, d, st, nb, a, tab);
@@ -892,7 +900,7 @@ extern "C" hipError_t ppfs_crc_check(const uint8_t* r, uint8_t* d, uint8_t* st, 
 extern "C" hipError_t ppfs_ham_encode(const uint8_t* d, uint8_t* r, const uint8_t* skip, uint64_t nb, uint32_t bs,
     uint32_t ds, uint32_t L, hipStream_t s)
 {
-    if (ppfs_bitfast_supported(bs))
+    if (ppfs_bitfast_supported(bs) && bf_aligned(d, r))
         return ppfs_ham_fast_encode(d, r, skip, nb, bs, ds, L, s);
     if (bs < 8) {
         hipLaunchKernelGGL(ham_tiny_encode_kernel, dim3(tiny_grid(nb)), dim3(256), 0, s, d, r, skip, nb, bs, ds);
@@ -906,7 +914,7 @@ extern "C" hipError_t ppfs_ham_encode(const uint8_t* d, uint8_t* r, const uint8_
 extern "C" hipError_t ppfs_ham_decode(uint8_t* r, uint8_t* d, uint8_t* st, uint64_t nb, int wb, uint32_t bs,
     uint32_t ds, uint32_t L, hipStream_t s)
 {
-    if (ppfs_bitfast_supported(bs))
+    if (ppfs_bitfast_supported(bs) && bf_aligned(d, r))
         return ppfs_ham_fast_decode(r, d, st, nb, wb, bs, ds, L, s);
     if (bs < 8) {
         hipLaunchKernelGGL(ham_tiny_decode_kernel, dim3(tiny_grid(nb)), dim3(256), 0, s, r, d, st, nb, wb, bs, ds);
@@ -920,7 +928,7 @@ extern "C" hipError_t ppfs_ham_decode(uint8_t* r, uint8_t* d, uint8_t* st, uint6
 extern "C" hipError_t ppfs_parity_encode(const uint8_t* d, uint8_t* r, const uint8_t* skip, uint64_t nb, uint32_t bs,
     hipStream_t s)
 {
-    if (ppfs_bitfast_supported(bs))
+    if (ppfs_bitfast_supported(bs) && bf_aligned(d, r))
         return ppfs_parity_fast_encode(d, r, skip, nb, bs, s);
     hipLaunchKernelGGL(parity_encode_kernel, dim3(bk_grid(nb)), dim3(256), 0, s, d, r, skip, nb, bs);
     return hipGetLastError();
@@ -929,7 +937,7 @@ extern "C" hipError_t ppfs_parity_encode(const uint8_t* d, uint8_t* r, const uin
 extern "C" hipError_t ppfs_parity_check(const uint8_t* r, uint8_t* d, uint8_t* st, uint64_t nb, uint32_t bs,
     hipStream_t s)
 {
-    if (ppfs_bitfast_supported(bs))
+    if (ppfs_bitfast_supported(bs) && bf_aligned(d, r))
         return ppfs_parity_fast_check(r, d, st, nb, bs, s);
     hipLaunchKernelGGL(parity_check_kernel, dim3(bk_grid(nb)), dim3(256), 0, s, r, d, st, nb, bs);
     return hipGetLastError();
