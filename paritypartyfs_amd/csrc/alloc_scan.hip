@@ -19,6 +19,7 @@
 
 #include "alloc_plan.hpp"
 #include "dbg.hpp"
+#include "status_tally.hpp"
 #include <stdint.h>
 
 namespace ppfs {
@@ -132,15 +133,11 @@ __global__ __launch_bounds__(256) void alloc_iota_kernel(uint32_t* __restrict__ 
 //   status_out (may be null; then index is not read): status_out[index[k] - first] = st[k] where that
 //   lies below out_n -- the per-bit array of the allocated scrub, any alignment;
 //   counts (may be null): counts[slot0 + alloc::count_slot(st[k])] grows by one for the slots below ncat.
-// Each category is counted by wave ballot and popcount over the workgroup's strided share of the
-// entries, the four waves combine through LDS, and one lane per category adds the workgroup's sum with
-// one 64-bit atomicAdd (none for a zero).  The record was zeroed on the stream before.
+// The tally is status_tally.hpp's, over the workgroup's strided share of the entries.
 __global__ __launch_bounds__(256) void scrub_tally_kernel(const uint8_t* __restrict__ st, const uint32_t* __restrict__ index,
     uint64_t n, uint32_t first, uint8_t* __restrict__ status_out, uint64_t out_n, unsigned long long* __restrict__ counts,
     int slot0, int ncat)
 {
-    __shared__ uint32_t part[4][4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint32_t c[4] = { 0, 0, 0, 0 };
     for (uint64_t k0 = (uint64_t)blockIdx.x * 256u; k0 < n; k0 += (uint64_t)gridDim.x * 256u) {
         const uint64_t k = k0 + threadIdx.x;
@@ -154,24 +151,9 @@ __global__ __launch_bounds__(256) void scrub_tally_kernel(const uint8_t* __restr
                     status_out[j] = (uint8_t)s;
             }
         }
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            c[q] += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(slot == q));
+        tally_add(c, slot);
     }
-    if (!counts)
-        return;
-    if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            part[wave][q] = c[q];
-    }
-    __syncthreads();
-    if (threadIdx.x < 4u && (int)threadIdx.x < ncat) {
-        const uint32_t q = threadIdx.x;
-        const unsigned long long sum = (unsigned long long)part[0][q] + part[1][q] + part[2][q] + part[3][q];
-        if (sum && PPFS_DBG_OK(counts + slot0 + q, 8, counts, 64))
-            atomicAdd(counts + slot0 + q, sum);
-    }
+    tally_flush(c, counts, slot0, ncat);
 }
 
 } // namespace ppfs

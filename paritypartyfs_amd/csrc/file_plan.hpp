@@ -1,5 +1,5 @@
 #pragma once
-// file_plan.hpp -- the arithmetic of the read-only file walk (file_path.cpp, file_walk.hip): how the 64
+// file_plan.hpp -- the arithmetic of the file walk (files_path.cpp, files_walk.hip): how the 64
 // bytes of an inode that describe its index-block tree (inode.hpp:18-41) and a range of file blocks
 // become the image blocks to read, as FileIO's BlockIndexIterator finds them (file_io.cpp:186-463,
 // should_resize == false).  Plain arithmetic for host and device alike, so the kernels, the host forms,

@@ -1,19 +1,26 @@
-// files_path.cpp -- the read-only walk over a batch of files of the ppfs_ecc C ABI (include/ppfs_ecc.h):
-// ppfs_ecc_files_plan, ppfs_ecc_files_blocks_* and ppfs_ecc_read_files_*.  They are file_path.cpp's calls
-// applied to many inodes at once: level A of all the files is one list, level B one list, level C one list
-// and the data blocks one extent stream (files_plan.hpp), so the number of launches is that of one file.
-//   plan    on the host: every file's span, its places in the batch's arrays, the merged levels, per level a
+// files_path.cpp -- the file walk of the ppfs_ecc C ABI (include/ppfs_ecc.h), and its batch entry points:
+// ppfs_ecc_files_plan, ppfs_ecc_files_blocks_*, ppfs_ecc_read_files_* and ppfs_ecc_write_files_*.  The single-file
+// entry points (file_path.cpp) run the same walk over a plan of one file (file_call.hpp).
+//
+// A file's index blocks are ordinary blocks of the image, the tree is at most three levels deep, and the number of
+// index blocks at each level follows from the range alone (file_plan.hpp).  Level A of all the files of a call is one
+// list, level B one list, level C one list and the data blocks one extent stream (files_plan.hpp), so the number of
+// launches is that of one file.
+//   plan    on the host: every file's span, its places in the call's arrays, the merged levels, per level a
 //           table of (first entry, file) rows and one 128-byte record per file
-//   upload  the tables go through a page-locked buffer into the call's share of the scrub scratch, on the
-//           caller's stream; the buffer returns to the cache once an event behind that copy has completed
-//   tree    per level A, B, C over the whole batch: expand (files_walk.hip), ONE ppfs_ecc_decode_list_*,
+//   upload  a batch only: the tables go through a page-locked buffer into the call's share of the scrub scratch, on
+//           the caller's stream; the buffer returns to the cache once an event behind that copy has completed.  The
+//           record of a single file travels in the kernel arguments instead
+//   tree    per level A, B, C over the whole call: expand (files_walk.hip), ONE ppfs_ecc_decode_list_*,
 //           merge (statuses, counts, file flags, the caller's level-major arrays)
 //   blocks  per piece of fileplan::PIECE_BLOCKS merged file blocks, cut regardless of file boundaries:
-//           expand; for a read also extents, ppfs_ecc_read_extents_* into the batch's out, merge
-//   write   ppfs_ecc_write_files_*: the same plan under the stricter range rule (a write stays inside the file),
-//           per piece expand, extents, ppfs_ecc_write_extents_* out of the batch's in, the write merge; the
-//           device form first refuses two ranges of one inode record that share a file block
-// The device forms queue all of it on the caller's stream and read nothing back.  The host forms run the
+//           expand; for a read also extents, ppfs_ecc_read_extents_* into the call's out, merge
+//   write   the same plan under the stricter range rule (a write stays inside the file), per piece expand,
+//           extents with pos pointing into the call's in, ppfs_ecc_write_extents_*, the write merge (`written`;
+//           no payload byte is filled in); the batch's device form first refuses two ranges of one inode record
+//           that share a file block
+// The device forms queue all of it on the caller's stream and read nothing back; their scratch is the context's
+// scrub scratch (scrub_path.cpp), so no call allocates or frees on the caller's stream.  The host forms run the
 // same merged plan on the CPU around the *_host list and extent calls.
 #include <hip/hip_runtime.h>
 
@@ -23,9 +30,7 @@
 #include <vector>
 
 #include "ctx.hpp"
-#pragma GCC visibility push(hidden) // the plan's out-of-line inlines are no part of the library's ABI
-#include "files_plan.hpp"
-#pragma GCC visibility pop
+#include "file_call.hpp"
 #include "kernels.hpp"
 #include "list_call.hpp"
 
@@ -33,6 +38,7 @@ using namespace ppfs;
 using namespace ppfs::fileplan;
 using filesplan::FileRec;
 using filesplan::Plan;
+using filesplan::PlanView;
 using filesplan::Row;
 
 static_assert(sizeof(ppfs_ecc_file_range) == 16, "a range is two 64-bit words");
@@ -128,14 +134,16 @@ int write_args(const ppfs_ecc_ctx* c, const void* image, const ppfs_ecc_file* fi
 }
 
 // where a level starts in the caller's level-major tree arrays
-uint64_t entry_base(const Plan& p, int level) { return level == LEVEL_A ? 0u : level == LEVEL_B ? p.total.tree[0] : p.total.tree[0] + p.total.tree[1]; }
+uint64_t entry_base(const PlanView& p, int level) { return level == LEVEL_A ? 0u : level == LEVEL_B ? p.total.tree[0] : p.total.tree[0] + p.total.tree[1]; }
 
 // ------------------------------------------------------------------------------------------------------
 // Device side
 // ------------------------------------------------------------------------------------------------------
-// A call's share of the context's scrub scratch: the tables (the records, then the four row tables), the
-// merged tree as in file_path.cpp (pointer, decode status, inherited status, payload per slot), a piece of
-// merged file blocks (pointer, path status, extent, read status).
+// A call's share of the context's scrub scratch: a batch's tables (the records, then the four row tables; a
+// single file has none), the merged tree (a pointer, a decode status, an inherited status and a payload per
+// slot; each level starts on a 16-entry boundary, so every level's payload and status pointers are 16-byte
+// aligned and a context that decodes lists directly keeps doing so), a piece of merged file blocks (pointer,
+// path status, extent, read or write status).
 struct Scratch {
     uint8_t* tables;
     uint32_t* tidx;
@@ -148,26 +156,27 @@ struct Scratch {
 struct TableLayout {
     size_t recs, rows[filesplan::LEVELS], bytes;
 };
-TableLayout table_layout(const Plan& p)
+TableLayout table_layout(const PlanView& p)
 {
     TableLayout t {};
     t.recs = 0;
-    size_t at = round_up(p.recs.size() * sizeof(FileRec), 256);
+    size_t at = round_up(p.nfiles * sizeof(FileRec), 256);
     for (int l = 0; l < filesplan::LEVELS; ++l) {
         t.rows[l] = at;
-        at = round_up(at + p.rows[l].size() * sizeof(Row), 256);
+        at = round_up(at + (p.nrows[l] + 1) * sizeof(Row), 256);
     }
     t.bytes = at;
     return t;
 }
-size_t scratch_layout(const Plan& p, size_t table_bytes, size_t ds, size_t piece, bool read, uint8_t* base, Scratch* s)
+// io: the call reads or writes, so a piece also has extents and statuses
+size_t scratch_layout(const PlanView& p, size_t table_bytes, size_t ds, size_t piece, bool io, uint8_t* base, Scratch* s)
 {
     const size_t slots = p.levels.slots;
     const size_t o_tidx = round_up(table_bytes, 256), o_tst = round_up(o_tidx + slots * 4, 256), o_tinh = round_up(o_tst + slots, 256),
                  o_tpay = round_up(o_tinh + slots, 256), o_idx = round_up(o_tpay + slots * ds + 16, 256),
                  o_path = round_up(o_idx + piece * 4, 256), o_ext = round_up(o_path + piece, 256),
-                 o_rst = round_up(o_ext + (read ? piece * 16 : 0), 256),
-                 bytes = round_up(o_rst + (read ? piece : 0), 256); // the codecs store statuses in whole 16-byte windows
+                 o_rst = round_up(o_ext + (io ? piece * 16 : 0), 256),
+                 bytes = round_up(o_rst + (io ? piece : 0), 256); // the codecs store statuses in whole 16-byte windows
     if (s)
         *s = Scratch { base, (uint32_t*)(base + o_tidx), base + o_tst, base + o_tinh, base + o_tpay, (uint32_t*)(base + o_idx),
             base + o_path, (ppfs_ecc_extent*)(base + o_ext), base + o_rst };
@@ -195,32 +204,52 @@ void reap_stages(ppfs_ecc_ctx* c)
     }
 }
 
-struct DeviceBatch {
-    ppfs_ecc_ctx* c;
-    uint8_t* image;
-    size_t blocks;
-    const Plan& plan;
-    size_t ds;
-    int wb;
+// what a failed launch is reported under: the texts of the single-file calls and of the batch calls
+struct Steps {
+    const char *expand, *extents, *tree_merge, *blocks_merge, *read_merge, *write_merge, *written_init;
+};
+constexpr Steps kOneSteps { "file expand", "file extents", "file tree merge", "file blocks tally", "file read merge", "file write merge",
+    "file written init" };
+constexpr Steps kBatchSteps { "files expand", "files extents", "files merge", "files merge", "files merge", "files write merge",
+    "files written init" };
+
+struct DeviceWalk {
+    const FileCall& a;
     void* stream;
+    const PlanView& plan = a.plan;
+    const size_t ds = a.c->data;
+    const bool one = plan.one != nullptr;
+    const Steps& step = one ? kOneSteps : kBatchSteps;
     Scratch x {};
     TableLayout tl {};
     hipStream_t s() const { return (hipStream_t)stream; }
-    uint64_t nfiles() const { return plan.recs.size(); }
-    const void* rows(int level) const { return x.tables + tl.rows[level]; }
-    uint64_t nrows(int level) const { return plan.rows[level].size() - 1; }
-
-    // the scratch (after a wait for its previous user), then the tables into it through a page-locked
-    // buffer that outlives the copy
-    int setup(size_t piece, bool read)
+    unsigned long long* counts() const { return (unsigned long long*)a.counts; }
+    // who owns the entries of a launch at a level: the single file, or the batch's tables in the scratch
+    ppfs_files_owner owner(int level) const
     {
-        reap_stages(c);
-        tl = table_layout(plan);
+        if (one)
+            return ppfs_files_owner { nullptr, 0, nullptr, 0, plan.one };
+        return ppfs_files_owner { x.tables + tl.recs, plan.nfiles, x.tables + tl.rows[level], plan.nrows[level], nullptr };
+    }
+
+    // the scratch (after a wait for its previous user); for a batch then the tables into it through a page-locked
+    // buffer that outlives the copy
+    int setup(size_t piece, bool io)
+    {
+        if (!one) {
+            reap_stages(a.c);
+            tl = table_layout(plan);
+        }
         uint8_t* scratch = nullptr;
-        int r = scrub_scratch(c, scratch_layout(plan, tl.bytes, ds, piece, read, nullptr, nullptr), s(), &scratch);
+        int r = scrub_scratch(a.c, scratch_layout(plan, tl.bytes, ds, piece, io, nullptr, nullptr), s(), &scratch);
         if (r)
             return r;
-        scratch_layout(plan, tl.bytes, ds, piece, read, scratch, &x);
+        scratch_layout(plan, tl.bytes, ds, piece, io, scratch, &x);
+        return one ? 0 : upload();
+    }
+    int upload()
+    {
+        ppfs_ecc_ctx* c = a.c;
         size_t cap = 4096; // few distinct sizes, so that the cache of page-locked buffers hits
         while (cap < tl.bytes)
             cap *= 2;
@@ -229,9 +258,9 @@ struct DeviceBatch {
             (void)hipGetLastError();
             return fail(PPFS_ECC_ENOMEM, "files: page-locked staging of the tables");
         }
-        std::memcpy(pin + tl.recs, plan.recs.data(), plan.recs.size() * sizeof(FileRec));
+        std::memcpy(pin + tl.recs, plan.recs, plan.nfiles * sizeof(FileRec));
         for (int l = 0; l < filesplan::LEVELS; ++l)
-            std::memcpy(pin + tl.rows[l], plan.rows[l].data(), plan.rows[l].size() * sizeof(Row));
+            std::memcpy(pin + tl.rows[l], plan.rows[l], (plan.nrows[l] + 1) * sizeof(Row));
         hipError_t e = dma_async(x.tables, pin, tl.bytes, hipMemcpyHostToDevice, s());
         hipEvent_t done = nullptr;
         if (e == hipSuccess && (e = hipEventCreateWithFlags(&done, hipEventDisableTiming)) == hipSuccess
@@ -249,21 +278,20 @@ struct DeviceBatch {
     }
     int expand(int level, uint64_t e0, uint64_t n, uint32_t* pointer, uint8_t* inherited) const
     {
-        return check_hip(ppfs_files_expand_launch(x.tables + tl.recs, nfiles(), rows(level), nrows(level), level, e0, n, ds, x.tpay,
-                             x.tst, x.tinh, plan.levels.slots, pointer, inherited, s()),
-            "files expand");
+        const ppfs_files_owner who = owner(level);
+        return check_hip(ppfs_files_expand_launch(&who, level, e0, n, ds, x.tpay, x.tst, x.tinh, plan.levels.slots, pointer, inherited, s()),
+            step.expand);
     }
     int merge(int level, const uint8_t* path, const uint8_t* read, uint64_t e0, uint64_t n, uint8_t* status_out,
-        const uint32_t* pointer_in, uint32_t* pointer_out, uint8_t* out, uint32_t* flags, unsigned long long* counts) const
+        const uint32_t* pointer_in, uint32_t* pointer_out, uint8_t* out, const char* what) const
     {
-        const bool tree = level != LEVEL_DATA;
-        return check_hip(ppfs_files_merge_launch(x.tables + tl.recs, nfiles(), rows(level), nrows(level), path, read, e0, n, status_out,
-                             pointer_in, pointer_out, out, plan.total.bytes, ds, flags, tree ? filesplan::FLAG_TREE_SHIFT : 0u, counts,
-                             tree ? SLOT_INDEX : SLOT_FILE, s()),
-            "files merge");
+        const ppfs_files_owner who = owner(level);
+        return check_hip(ppfs_files_merge_launch(&who, level, path, read, e0, n, status_out, pointer_in, pointer_out, out,
+                             plan.total.bytes, ds, a.flags, counts(), s()),
+            what);
     }
-    // levels A, B, C of the whole batch: each one list decode; the caller's arrays level-major (either may be null)
-    int levels(uint32_t* tree_index, uint8_t* tree_status, uint32_t* flags, unsigned long long* counts) const
+    // levels A, B, C of the whole call: each one list decode; the caller's arrays level-major (either may be null)
+    int levels() const
     {
         int r = 0;
         for (int level = LEVEL_A; level <= LEVEL_C && !r; ++level) {
@@ -271,15 +299,44 @@ struct DeviceBatch {
             if (n == 0)
                 continue;
             (void)((r = expand(level, 0, n, x.tidx + at, x.tinh + at))
-                || (r = ppfs_ecc_decode_list_device(c, image, blocks, x.tidx + at, n, x.tpay + at * ds, x.tst + at, wb, nullptr, stream))
-                || (r = merge(level, x.tinh + at, x.tst + at, 0, n, tree_status ? tree_status + to : nullptr, x.tidx + at,
-                        tree_index ? tree_index + to : nullptr, nullptr, flags, counts)));
+                || (r = ppfs_ecc_decode_list_device(a.c, a.image, blocks_seen(a.image_blocks), x.tidx + at, n, x.tpay + at * ds, x.tst + at,
+                        a.wb, nullptr, stream))
+                || (r = merge(level, x.tinh + at, x.tst + at, 0, n, a.tree_status ? a.tree_status + to : nullptr, x.tidx + at,
+                        a.tree_index ? a.tree_index + to : nullptr, nullptr, step.tree_merge)));
         }
         return r;
     }
+    // the merged file blocks [off, off + nb): expand, for a read or a write the extents and the extent call, the mode's merge
+    int piece(uint64_t off, uint64_t nb) const
+    {
+        const bool io = a.mode != FileMode::blocks;
+        uint32_t* idx = io ? x.idx : a.index ? a.index + off : nullptr;
+        uint8_t* path = !io && a.path_status ? a.path_status + off : x.path;
+        uint8_t* status = a.status ? a.status + off : nullptr;
+        const ppfs_files_owner who = owner(LEVEL_DATA);
+        int r = expand(LEVEL_DATA, off, nb, idx, path);
+        if (!r && io)
+            r = check_hip(ppfs_files_extents_launch(&who, idx, path, off, nb, ds, x.ext, s()), step.extents);
+        if (r)
+            return r;
+        switch (a.mode) {
+        case FileMode::blocks:
+            return merge(LEVEL_DATA, path, nullptr, off, nb, nullptr, nullptr, nullptr, nullptr, step.blocks_merge);
+        case FileMode::read:
+            if ((r = ppfs_ecc_read_extents_device(a.c, a.image, a.image_blocks, x.ext, nb, a.out, plan.total.bytes, x.rst, a.wb, stream)))
+                return r;
+            return merge(LEVEL_DATA, path, x.rst, off, nb, status, nullptr, nullptr, a.out, step.read_merge);
+        default:
+            if ((r = ppfs_ecc_write_extents_device(a.c, a.in, plan.total.bytes, a.image, a.image_blocks, x.ext, nb, x.rst, stream)))
+                return r;
+            return check_hip(ppfs_files_write_merge_launch(&who, path, x.rst, off, nb, status, ds, a.flags,
+                                 (unsigned long long*)a.written, counts(), s()),
+                step.write_merge);
+        }
+    }
 };
 
-// what both device forms do before the walk: refuse a capture, clear the counts and the flags
+// what the batch's device forms do before the walk: refuse a capture, clear the counts and the flags
 int device_begin(hipStream_t s, size_t nfiles, uint32_t* d_flags, ppfs_ecc_file_counts* d_counts)
 {
     if (stream_capturing(s))
@@ -301,6 +358,28 @@ void slots_out(const Plan& plan, ppfs_ecc_files_slot* slots, ppfs_ecc_files_tota
 
 } // namespace
 
+int ppfs::file_call_device(const FileCall& a, void* stream, const char* queued)
+{
+    const uint64_t nblocks = a.plan.total.blocks;
+    const size_t piece = std::min<uint64_t>(nblocks, PIECE_BLOCKS);
+    const bool io = a.mode != FileMode::blocks;
+    DeviceWalk w { a, stream };
+    int r = w.setup(piece, io);
+    if (r)
+        return r;
+    if (a.mode == FileMode::write) {
+        const ppfs_files_owner who = w.owner(LEVEL_DATA);
+        r = check_hip(ppfs_files_written_init_launch(&who, (unsigned long long*)a.written, w.s()), w.step.written_init);
+    }
+    if (!r)
+        r = w.levels();
+    if (io || a.index || a.path_status || a.counts || a.flags)
+        for (uint64_t off = 0; off < nblocks && !r; off += piece)
+            r = w.piece(off, std::min<uint64_t>(piece, nblocks - off));
+    scrub_scratch_used(a.c, w.s());
+    return call_queued(a.c, r, nblocks, stream, queued);
+}
+
 extern "C" int ppfs_ecc_files_plan(const ppfs_ecc_ctx* c, const ppfs_ecc_file* files, const ppfs_ecc_file_range* ranges, size_t nfiles,
     ppfs_ecc_files_slot* slots, ppfs_ecc_files_totals* totals)
 {
@@ -320,28 +399,16 @@ extern "C" int ppfs_ecc_files_blocks_device(ppfs_ecc_ctx* c, uint8_t* d_image, s
     int r = batch_args(c, files, ranges, nfiles, "files blocks", plan);
     if (r || (r = walk_args(c, d_image, plan, d_index, d_tree_index, d_file_flags, d_counts, "files blocks")))
         return r;
-    hipStream_t s = (hipStream_t)stream;
-    if ((r = device_begin(s, nfiles, d_file_flags, d_counts)))
+    if ((r = device_begin((hipStream_t)stream, nfiles, d_file_flags, d_counts)) || plan.total.blocks == 0)
         return r;
-    const uint64_t nblocks = plan.total.blocks;
-    if (nblocks == 0)
-        return 0;
-    unsigned long long* counts = (unsigned long long*)d_counts;
-    DeviceBatch w { c, d_image, blocks_seen(image_blocks), plan, c->data, write_back ? 1 : 0, stream };
-    const size_t piece = std::min<uint64_t>(nblocks, PIECE_BLOCKS);
-    if ((r = w.setup(piece, false)))
-        return r;
-    r = w.levels(d_tree_index, d_tree_status, d_file_flags, counts);
-    if (d_index || d_path_status || counts || d_file_flags) {
-        for (uint64_t off = 0; off < nblocks && !r; off += piece) {
-            const uint64_t nb = std::min<uint64_t>(piece, nblocks - off);
-            uint8_t* path = d_path_status ? d_path_status + off : w.x.path;
-            (void)((r = w.expand(LEVEL_DATA, off, nb, d_index ? d_index + off : nullptr, path))
-                || (r = w.merge(LEVEL_DATA, path, nullptr, off, nb, nullptr, nullptr, nullptr, nullptr, d_file_flags, counts)));
-        }
-    }
-    scrub_scratch_used(c, s);
-    return call_queued(c, r, nblocks, stream, "files blocks (async)");
+    FileCall a { c, d_image, image_blocks, plan.view(), FileMode::blocks, write_back ? 1 : 0 };
+    a.index = d_index;
+    a.path_status = d_path_status;
+    a.tree_index = d_tree_index;
+    a.tree_status = d_tree_status;
+    a.flags = d_file_flags;
+    a.counts = d_counts;
+    return file_call_device(a, stream, "files blocks (async)");
 }
 
 extern "C" int ppfs_ecc_read_files_device(ppfs_ecc_ctx* c, uint8_t* d_image, size_t image_blocks, const ppfs_ecc_file* files,
@@ -352,34 +419,17 @@ extern "C" int ppfs_ecc_read_files_device(ppfs_ecc_ctx* c, uint8_t* d_image, siz
     int r = batch_args(c, files, ranges, nfiles, "read files", plan);
     if (r || (r = read_args(c, d_image, plan, d_out, out_bytes, d_file_flags, d_counts, "read files")))
         return r;
-    hipStream_t s = (hipStream_t)stream;
-    if ((r = device_begin(s, nfiles, d_file_flags, d_counts)))
+    if ((r = device_begin((hipStream_t)stream, nfiles, d_file_flags, d_counts)) || plan.total.blocks == 0)
         return r;
-    const uint64_t nblocks = plan.total.blocks;
-    if (nblocks == 0)
-        return 0;
-    unsigned long long* counts = (unsigned long long*)d_counts;
-    DeviceBatch w { c, d_image, blocks_seen(image_blocks), plan, c->data, write_back ? 1 : 0, stream };
-    const size_t piece = std::min<uint64_t>(nblocks, PIECE_BLOCKS);
-    if ((r = w.setup(piece, true)))
-        return r;
-    r = w.levels(nullptr, nullptr, d_file_flags, counts);
-    for (uint64_t off = 0; off < nblocks && !r; off += piece) {
-        const uint64_t nb = std::min<uint64_t>(piece, nblocks - off);
-        (void)((r = w.expand(LEVEL_DATA, off, nb, w.x.idx, w.x.path))
-            || (r = check_hip(ppfs_files_extents_launch(w.x.tables + w.tl.recs, w.nfiles(), w.rows(LEVEL_DATA), w.nrows(LEVEL_DATA),
-                                  w.x.idx, w.x.path, off, nb, w.ds, w.x.ext, s),
-                    "files extents"))
-            || (r = ppfs_ecc_read_extents_device(c, d_image, image_blocks, w.x.ext, nb, d_out, plan.total.bytes, w.x.rst, w.wb, stream))
-            || (r = w.merge(LEVEL_DATA, w.x.path, w.x.rst, off, nb, d_status ? d_status + off : nullptr, nullptr, nullptr, d_out,
-                    d_file_flags, counts)));
-    }
-    scrub_scratch_used(c, s);
-    return call_queued(c, r, nblocks, stream, "read files (async)");
+    FileCall a { c, d_image, image_blocks, plan.view(), FileMode::read, write_back ? 1 : 0 };
+    a.out = d_out;
+    a.status = d_status;
+    a.flags = d_file_flags;
+    a.counts = d_counts;
+    return file_call_device(a, stream, "read files (async)");
 }
 
-// FileIO::writeFile over an existing range (file_io.cpp:46-104) for every file of a batch: the read's walk and
-// extents with pos pointing into `in`, ppfs_ecc_write_extents_device per piece, then the write merge
+// FileIO::writeFile over an existing range (file_io.cpp:46-104) for every file of a batch
 extern "C" int ppfs_ecc_write_files_device(ppfs_ecc_ctx* c, const uint8_t* d_in, size_t in_bytes, uint8_t* d_image,
     size_t image_blocks, const ppfs_ecc_file* files, const ppfs_ecc_file_range* ranges, size_t nfiles, uint8_t* d_status,
     uint32_t* d_file_flags, uint64_t* d_written, ppfs_ecc_file_counts* d_counts, int write_back, void* stream)
@@ -391,33 +441,18 @@ extern "C" int ppfs_ecc_write_files_device(ppfs_ecc_ctx* c, const uint8_t* d_in,
     hipStream_t s = (hipStream_t)stream;
     if ((r = device_begin(s, nfiles, d_file_flags, d_counts)))
         return r;
-    const uint64_t nblocks = plan.total.blocks;
-    unsigned long long *counts = (unsigned long long*)d_counts, *written = (unsigned long long*)d_written;
-    if (nblocks == 0) { // every range is empty: nothing is written, of nothing
-        if (written && nfiles)
-            HIP_TRY(hipMemsetAsync(written, 0, nfiles * sizeof(uint64_t), s), "files written clear");
+    if (plan.total.blocks == 0) { // every range is empty: nothing is written, of nothing
+        if (d_written && nfiles)
+            HIP_TRY(hipMemsetAsync(d_written, 0, nfiles * sizeof(uint64_t), s), "files written clear");
         return 0;
     }
-    DeviceBatch w { c, d_image, blocks_seen(image_blocks), plan, c->data, write_back ? 1 : 0, stream };
-    const size_t piece = std::min<uint64_t>(nblocks, PIECE_BLOCKS);
-    if ((r = w.setup(piece, true)))
-        return r;
-    (void)((r = check_hip(ppfs_files_written_init_launch(w.x.tables + w.tl.recs, w.nfiles(), written, s), "files written init"))
-        || (r = w.levels(nullptr, nullptr, d_file_flags, counts)));
-    for (uint64_t off = 0; off < nblocks && !r; off += piece) {
-        const uint64_t nb = std::min<uint64_t>(piece, nblocks - off);
-        (void)((r = w.expand(LEVEL_DATA, off, nb, w.x.idx, w.x.path))
-            || (r = check_hip(ppfs_files_extents_launch(w.x.tables + w.tl.recs, w.nfiles(), w.rows(LEVEL_DATA), w.nrows(LEVEL_DATA),
-                                  w.x.idx, w.x.path, off, nb, w.ds, w.x.ext, s),
-                    "files extents"))
-            || (r = ppfs_ecc_write_extents_device(c, d_in, plan.total.bytes, d_image, image_blocks, w.x.ext, nb, w.x.rst, stream))
-            || (r = check_hip(ppfs_files_write_merge_launch(w.x.tables + w.tl.recs, w.nfiles(), w.rows(LEVEL_DATA),
-                                  w.nrows(LEVEL_DATA), w.x.path, w.x.rst, off, nb, d_status ? d_status + off : nullptr, w.ds,
-                                  d_file_flags, written, counts, s),
-                    "files write merge")));
-    }
-    scrub_scratch_used(c, s);
-    return call_queued(c, r, nblocks, stream, "write files (async)");
+    FileCall a { c, d_image, image_blocks, plan.view(), FileMode::write, write_back ? 1 : 0 };
+    a.in = d_in;
+    a.status = d_status;
+    a.flags = d_file_flags;
+    a.written = d_written;
+    a.counts = d_counts;
+    return file_call_device(a, stream, "write files (async)");
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -433,36 +468,31 @@ struct HostMem {
 };
 
 struct HostBatch {
-    ppfs_ecc_ctx* c;
-    uint8_t* image;
-    size_t blocks;
-    const Plan& plan;
-    size_t ds;
-    int wb;
-    uint32_t* flags;
-    ppfs_ecc_file_counts* counts;
-    std::vector<uint32_t> tidx;
-    std::vector<uint8_t> tst, tinh, tpay;
+    const FileCall& a;
+    const PlanView& plan = a.plan;
+    const size_t ds = a.c->data;
+    std::vector<uint32_t> tidx {};
+    std::vector<uint8_t> tst {}, tinh {}, tpay {};
 
     HostMem mem() const { return HostMem { tpay.data(), tst.data(), tinh.data() }; }
-    void note(uint32_t file, uint32_t st, bool tree)
+    void note(uint32_t file, uint32_t st, bool tree) const
     {
         const int slot = count_slot(st);
-        if (counts && slot >= 0)
-            ++(&counts->ok)[(tree ? SLOT_INDEX : SLOT_FILE) + slot];
-        if (flags)
-            flags[file] |= filesplan::flag_of(st) << (tree ? filesplan::FLAG_TREE_SHIFT : 0u);
+        if (a.counts && slot >= 0)
+            ++(&a.counts->ok)[(tree ? SLOT_INDEX : SLOT_FILE) + slot];
+        if (a.flags)
+            a.flags[file] |= filesplan::flag_of(st) << (tree ? filesplan::FLAG_TREE_SHIFT : 0u);
     }
     // fn(file, k, merged entry) for every entry of a level, in merged order
     template <class Fn>
     void each(int level, Fn fn) const
     {
-        const std::vector<Row>& rows = plan.rows[level];
-        for (size_t r = 0; r + 1 < rows.size(); ++r)
+        const Row* rows = plan.rows[level];
+        for (size_t r = 0; r < plan.nrows[level]; ++r)
             for (uint64_t e = rows[r].first; e < rows[r + 1].first; ++e)
                 fn(rows[r].file, e - rows[r].first, e);
     }
-    int levels(uint32_t* tree_index, uint8_t* tree_status)
+    int levels()
     {
         const size_t slots = plan.levels.slots;
         tidx.assign(slots, NO_BLOCK);
@@ -479,16 +509,16 @@ struct HostBatch {
                 tidx[at + e] = x.pointer;
                 tinh[at + e] = x.inherited;
             });
-            const int r = ppfs_ecc_decode_list_host(c, image, blocks, tidx.data() + at, n, tpay.data() + at * ds, tst.data() + at, wb,
-                nullptr);
+            const int r = ppfs_ecc_decode_list_host(a.c, a.image, blocks_seen(a.image_blocks), tidx.data() + at, n, tpay.data() + at * ds,
+                tst.data() + at, a.wb, nullptr);
             if (r)
                 return r;
             each(level, [&](uint32_t f, uint64_t, uint64_t e) {
                 const uint8_t st = tinh[at + e] ? tinh[at + e] : tst[at + e];
-                if (tree_index)
-                    tree_index[to + e] = tidx[at + e];
-                if (tree_status)
-                    tree_status[to + e] = st;
+                if (a.tree_index)
+                    a.tree_index[to + e] = tidx[at + e];
+                if (a.tree_status)
+                    a.tree_status[to + e] = st;
                 note(f, st, true);
             });
         }
@@ -506,6 +536,53 @@ void host_begin(size_t nfiles, uint32_t* flags, ppfs_ecc_file_counts* counts)
 
 } // namespace
 
+int ppfs::file_call_host(const FileCall& a)
+{
+    const PlanView& plan = a.plan;
+    const uint64_t nblocks = plan.total.blocks;
+    HostBatch w { a };
+    int r = w.levels();
+    if (r)
+        return r;
+    const HostMem m = w.mem();
+    if (a.mode == FileMode::blocks) {
+        w.each(LEVEL_DATA, [&](uint32_t f, uint64_t k, uint64_t e) {
+            const Expanded x = filesplan::expand_entry(plan.recs[f], LEVEL_DATA, k, w.ds, m);
+            if (a.index)
+                a.index[e] = x.pointer;
+            if (a.path_status)
+                a.path_status[e] = x.inherited;
+            w.note(f, x.inherited, false);
+        });
+        return 0;
+    }
+    // a read or a write: the extents, the extent call, then path status over its status
+    std::vector<ppfs_ecc_extent> ext(nblocks);
+    std::vector<uint8_t> path(nblocks), st(nblocks);
+    w.each(LEVEL_DATA, [&](uint32_t f, uint64_t k, uint64_t e) {
+        const FileRec& rec = plan.recs[f];
+        const Expanded x = filesplan::expand_entry(rec, LEVEL_DATA, k, w.ds, m);
+        const Extent at = extent_of(k, rec.off0, rec.bytes, w.ds);
+        path[e] = x.inherited;
+        ext[e] = ppfs_ecc_extent { rec.out_pos + at.pos, x.inherited ? NO_BLOCK : x.pointer, (uint16_t)at.offset, (uint16_t)at.length };
+    });
+    const bool read = a.mode == FileMode::read;
+    if ((r = read ? ppfs_ecc_read_extents_host(a.c, a.image, a.image_blocks, ext.data(), nblocks, a.out, plan.total.bytes, st.data(), a.wb)
+                  : ppfs_ecc_write_extents_host(a.c, a.in, plan.total.bytes, a.image, a.image_blocks, ext.data(), nblocks, st.data())))
+        return r;
+    w.each(LEVEL_DATA, [&](uint32_t f, uint64_t, uint64_t e) {
+        const uint8_t fin = path[e] ? path[e] : st[e];
+        if (a.status)
+            a.status[e] = fin;
+        if (read && path[e] == STATUS_FAILED) // the zero fill under a failed index block
+            std::memset(a.out + ext[e].pos, 0, ext[e].length);
+        if (!read && a.written && (fin == STATUS_FAILED || fin == STATUS_OUT)) // lowered to the first failing block's position
+            a.written[f] = std::min<uint64_t>(a.written[f], ext[e].pos - plan.recs[f].out_pos);
+        w.note(f, fin, false);
+    });
+    return 0;
+}
+
 extern "C" int ppfs_ecc_files_blocks_host(ppfs_ecc_ctx* c, uint8_t* image, size_t image_blocks, const ppfs_ecc_file* files,
     const ppfs_ecc_file_range* ranges, size_t nfiles, uint32_t* index, uint8_t* path_status, uint32_t* tree_index,
     uint8_t* tree_status, uint32_t* file_flags, ppfs_ecc_file_counts* counts, int write_back)
@@ -517,19 +594,14 @@ extern "C" int ppfs_ecc_files_blocks_host(ppfs_ecc_ctx* c, uint8_t* image, size_
     host_begin(nfiles, file_flags, counts);
     if (plan.total.blocks == 0)
         return 0;
-    HostBatch w { c, image, blocks_seen(image_blocks), plan, c->data, write_back ? 1 : 0, file_flags, counts, {}, {}, {}, {} };
-    if ((r = w.levels(tree_index, tree_status)))
-        return r;
-    const HostMem m = w.mem();
-    w.each(LEVEL_DATA, [&](uint32_t f, uint64_t k, uint64_t e) {
-        const Expanded x = filesplan::expand_entry(plan.recs[f], LEVEL_DATA, k, w.ds, m);
-        if (index)
-            index[e] = x.pointer;
-        if (path_status)
-            path_status[e] = x.inherited;
-        w.note(f, x.inherited, false);
-    });
-    return 0;
+    FileCall a { c, image, image_blocks, plan.view(), FileMode::blocks, write_back ? 1 : 0 };
+    a.index = index;
+    a.path_status = path_status;
+    a.tree_index = tree_index;
+    a.tree_status = tree_status;
+    a.flags = file_flags;
+    a.counts = counts;
+    return file_call_host(a);
 }
 
 extern "C" int ppfs_ecc_read_files_host(ppfs_ecc_ctx* c, uint8_t* image, size_t image_blocks, const ppfs_ecc_file* files,
@@ -541,33 +613,14 @@ extern "C" int ppfs_ecc_read_files_host(ppfs_ecc_ctx* c, uint8_t* image, size_t 
     if (r || (r = read_args(c, image, plan, out, out_bytes, file_flags, counts, "read files (host)")))
         return r;
     host_begin(nfiles, file_flags, counts);
-    const uint64_t nblocks = plan.total.blocks;
-    if (nblocks == 0)
+    if (plan.total.blocks == 0)
         return 0;
-    HostBatch w { c, image, blocks_seen(image_blocks), plan, c->data, write_back ? 1 : 0, file_flags, counts, {}, {}, {}, {} };
-    if ((r = w.levels(nullptr, nullptr)))
-        return r;
-    const HostMem m = w.mem();
-    std::vector<ppfs_ecc_extent> ext(nblocks);
-    std::vector<uint8_t> path(nblocks), rst(nblocks);
-    w.each(LEVEL_DATA, [&](uint32_t f, uint64_t k, uint64_t e) {
-        const FileRec& rec = plan.recs[f];
-        const Expanded x = filesplan::expand_entry(rec, LEVEL_DATA, k, w.ds, m);
-        const Extent at = extent_of(k, rec.off0, rec.bytes, w.ds);
-        path[e] = x.inherited;
-        ext[e] = ppfs_ecc_extent { rec.out_pos + at.pos, x.inherited ? NO_BLOCK : x.pointer, (uint16_t)at.offset, (uint16_t)at.length };
-    });
-    if ((r = ppfs_ecc_read_extents_host(c, image, image_blocks, ext.data(), nblocks, out, plan.total.bytes, rst.data(), w.wb)))
-        return r;
-    w.each(LEVEL_DATA, [&](uint32_t f, uint64_t, uint64_t e) {
-        const uint8_t st = path[e] ? path[e] : rst[e];
-        if (status)
-            status[e] = st;
-        if (path[e] == STATUS_FAILED)
-            std::memset(out + ext[e].pos, 0, ext[e].length);
-        w.note(f, st, false);
-    });
-    return 0;
+    FileCall a { c, image, image_blocks, plan.view(), FileMode::read, write_back ? 1 : 0 };
+    a.out = out;
+    a.status = status;
+    a.flags = file_flags;
+    a.counts = counts;
+    return file_call_host(a);
 }
 
 // Repeats are not refused here: ppfs_ecc_write_extents_host cuts its list where a block repeats, so the ranges apply
@@ -584,31 +637,13 @@ extern "C" int ppfs_ecc_write_files_host(ppfs_ecc_ctx* c, const uint8_t* in, siz
     if (written)
         for (size_t f = 0; f < nfiles; ++f)
             written[f] = plan.recs[f].bytes;
-    const uint64_t nblocks = plan.total.blocks;
-    if (nblocks == 0)
+    if (plan.total.blocks == 0)
         return 0;
-    HostBatch w { c, image, blocks_seen(image_blocks), plan, c->data, write_back ? 1 : 0, file_flags, counts, {}, {}, {}, {} };
-    if ((r = w.levels(nullptr, nullptr)))
-        return r;
-    const HostMem m = w.mem();
-    std::vector<ppfs_ecc_extent> ext(nblocks);
-    std::vector<uint8_t> path(nblocks), wst(nblocks);
-    w.each(LEVEL_DATA, [&](uint32_t f, uint64_t k, uint64_t e) {
-        const FileRec& rec = plan.recs[f];
-        const Expanded x = filesplan::expand_entry(rec, LEVEL_DATA, k, w.ds, m);
-        const Extent at = extent_of(k, rec.off0, rec.bytes, w.ds);
-        path[e] = x.inherited;
-        ext[e] = ppfs_ecc_extent { rec.out_pos + at.pos, x.inherited ? NO_BLOCK : x.pointer, (uint16_t)at.offset, (uint16_t)at.length };
-    });
-    if ((r = ppfs_ecc_write_extents_host(c, in, plan.total.bytes, image, image_blocks, ext.data(), nblocks, wst.data())))
-        return r;
-    w.each(LEVEL_DATA, [&](uint32_t f, uint64_t, uint64_t e) {
-        const uint8_t st = path[e] ? path[e] : wst[e];
-        if (status)
-            status[e] = st;
-        if (written && (st == STATUS_FAILED || st == STATUS_OUT))
-            written[f] = std::min<uint64_t>(written[f], ext[e].pos - plan.recs[f].out_pos);
-        w.note(f, st, false);
-    });
-    return 0;
+    FileCall a { c, image, image_blocks, plan.view(), FileMode::write, write_back ? 1 : 0 };
+    a.in = in;
+    a.status = status;
+    a.flags = file_flags;
+    a.written = written;
+    a.counts = counts;
+    return file_call_host(a);
 }

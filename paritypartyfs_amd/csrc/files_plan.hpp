@@ -1,7 +1,7 @@
 #pragma once
-// files_plan.hpp -- the arithmetic of a walk over a BATCH of files (files_path.cpp, files_walk.hip): the
-// single-file plan of file_plan.hpp applied to file after file, with every level of all the files merged
-// into one list, so that a batch costs the launches of one file.  Plain arithmetic for host and device
+// files_plan.hpp -- the arithmetic of a walk over a BATCH of files, a batch of one included (files_path.cpp,
+// files_walk.hip): the single-file plan of file_plan.hpp applied to file after file, with every level of
+// all the files merged into one list, so that a batch costs the launches of one file.  Plain arithmetic for host and device
 // alike; tests/cpp/test_files_plan.cpp (a plain g++ program under the address sanitizer) checks it against
 // a per-file loop of file_plan.hpp.
 //
@@ -148,14 +148,20 @@ struct RecSrc {
 };
 // entry k of a level of the file of `rec`: fileplan's expansion against the merged scratch.  A k past the
 // level (a table that does not go with the records) names no block.
+// t: the Tree of the record's range, for a caller that has it already
 template <class Mem>
-PPFS_HD inline fileplan::Expanded expand_entry(const FileRec& rec, int level, uint64_t k, uint64_t ds, const Mem& mem)
+PPFS_HD inline fileplan::Expanded expand_entry(const FileRec& rec, const fileplan::Tree& t, int level, uint64_t k, uint64_t ds,
+    const Mem& mem)
 {
-    const fileplan::Tree t = fileplan::tree_of(rec.first, rec.blocks, fileplan::ipb_of(ds));
     if (k >= fileplan::level_count(t, level))
         return fileplan::Expanded { fileplan::NO_BLOCK, fileplan::STATUS_OUT };
     const RecSrc<Mem> src { &rec, &mem };
     return fileplan::expand_at(t, level, k, ds, src, rec.lvl[0], rec.lvl[1], rec.lvl[2]);
+}
+template <class Mem>
+PPFS_HD inline fileplan::Expanded expand_entry(const FileRec& rec, int level, uint64_t k, uint64_t ds, const Mem& mem)
+{
+    return expand_entry(rec, fileplan::tree_of(rec.first, rec.blocks, fileplan::ipb_of(ds)), level, k, ds, mem);
 }
 
 // The host-built plan of a batch.  rows[l] ends with the sentinel, so rows[l].size() - 1 files have entries
@@ -167,7 +173,45 @@ struct Plan {
     Totals total {};
     Levels levels {};
     uint64_t count(int level) const { return level < 3 ? total.tree[level] : total.blocks; }
+    struct PlanView view() const;
 };
+// What a walk reads of a plan, a batch's (Plan::view) or a single file's (OnePlan::view): pointers into the plan, which
+// outlives the view.  rows[l] holds nrows[l] rows and then the sentinel.  one: a single file's record with its Tree
+// (recs then points at its record); null for a batch.
+struct OneRec;
+struct PlanView {
+    const FileRec* recs;
+    uint64_t nfiles;
+    const Row* rows[LEVELS];
+    uint64_t nrows[LEVELS];
+    Totals total;
+    Levels levels;
+    const OneRec* one = nullptr;
+};
+inline PlanView Plan::view() const
+{
+    PlanView v { recs.data(), recs.size(), {}, {}, total, levels };
+    for (int l = 0; l < LEVELS; ++l) {
+        v.rows[l] = rows[l].data();
+        v.nrows[l] = rows[l].size() - 1;
+    }
+    return v;
+}
+// the record of a file out of its inode, its slot (tree_pos still counted within each level) and the merged levels
+inline FileRec rec_of(const uint32_t* inode, const Slot& s, uint64_t off0, const Levels& levels)
+{
+    FileRec q;
+    for (int d = 0; d < 16; ++d)
+        q.inode[d] = inode[d];
+    q.first = s.first;
+    q.blocks = s.blocks;
+    q.off0 = s.blocks ? off0 : 0u;
+    q.bytes = s.bytes;
+    q.out_pos = s.out_pos;
+    for (int l = 0; l < 3; ++l)
+        q.lvl[l] = levels.base[l] + s.tree_pos[l];
+    return q;
+}
 // The range rule of a WRITE (ppfs_ecc_write_file_*, ppfs_ecc_write_files_*): it stays inside the file as the inode
 // describes it, offset + nbytes <= file_size, and nothing is clamped (FileIO::writeFile would grow the file,
 // file_io.cpp:46-104; growing is the caller's job).  nbytes == 0 is an empty, valid range whatever the offset.
@@ -207,20 +251,50 @@ inline int build(const uint32_t* files, const uint64_t* ranges, uint64_t nfiles,
     for (int l = 0; l < LEVELS; ++l)
         p.rows[l].push_back(Row { p.count(l), (uint32_t)nfiles, 0 });
     for (uint64_t f = 0; f < nfiles; ++f) {
-        Slot& s = p.slots[f];
-        FileRec& q = p.recs[f];
-        for (int d = 0; d < 16; ++d)
-            q.inode[d] = files[16u * f + d];
-        q.first = s.first;
-        q.blocks = s.blocks;
-        q.off0 = ds && s.blocks ? (ranges ? ranges[2u * f] : 0u) % ds : 0u;
-        q.bytes = s.bytes;
-        q.out_pos = s.out_pos;
-        for (int l = 0; l < 3; ++l)
-            q.lvl[l] = p.levels.base[l] + s.tree_pos[l]; // still counted within the level here
-        level_major(s, p.total);
+        p.recs[f] = rec_of(files + 16u * f, p.slots[f], ds ? (ranges ? ranges[2u * f] : 0u) % ds : 0u, p.levels);
+        level_major(p.slots[f], p.total);
     }
     return RANGE_OK;
+}
+
+// The plan of ONE file whose range is already known as blocks -- its file blocks [first, first + count), of which
+// `bytes` bytes from payload byte off0 of the first are the call's (the single-file calls, which check their ranges
+// themselves): what build() yields for a batch of that one file and the equivalent byte range, in a fixed record
+// without a heap allocation, and the Tree of the range, which a batch's kernels rebuild per lane.
+struct OneRec {
+    FileRec rec;
+    fileplan::Tree tree;
+};
+struct OnePlan {
+    Slot slot;
+    OneRec one;
+    Row rows[LEVELS][2];
+    Totals total;
+    Levels levels;
+    PlanView view() const
+    {
+        PlanView v { &one.rec, 1, {}, {}, total, levels, &one };
+        for (int l = 0; l < LEVELS; ++l) {
+            v.rows[l] = rows[l];
+            v.nrows[l] = rows[l][0].file == 0 ? 1 : 0;
+        }
+        return v;
+    }
+};
+inline void build_one(const uint32_t* inode, uint64_t first, uint64_t count, uint64_t off0, uint64_t bytes, uint64_t ds, OnePlan& p)
+{
+    p = OnePlan {};
+    const fileplan::Tree t = fileplan::tree_of(first, count, fileplan::ipb_of(ds));
+    p.slot = Slot { first, count, bytes, 0, 0, { 0, 0, 0 }, { t.nA, t.nB, t.nC } };
+    add_slot(p.total, p.slot);
+    p.levels = levels_of(p.total);
+    p.one = OneRec { rec_of(inode, p.slot, off0, p.levels), t };
+    level_major(p.slot, p.total);
+    for (int l = 0; l < LEVELS; ++l) {
+        const uint64_t n = l < 3 ? p.total.tree[l] : p.total.blocks;
+        p.rows[l][0] = n ? Row { 0, 0, 0 } : Row { 0, 1, 0 }; // an empty level holds the sentinel alone
+        p.rows[l][1] = Row { n, 1, 0 };
+    }
 }
 
 // ---- the write side, host only: the plan of a batch write, and the repeat rule of its device form ----

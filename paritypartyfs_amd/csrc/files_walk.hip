@@ -1,24 +1,31 @@
-// files_walk.hip -- the kernels of the read-only walk over a batch of files (files_path.cpp; include/ppfs_ecc.h
-// ppfs_ecc_files_blocks_*, ppfs_ecc_read_files_*).  They are file_walk.hip's three kernels in batch form:
-// every level of all the files is one merged list (files_plan.hpp), and a lane first finds the file that
-// owns its merged entry.
-//   files_expand_kernel   one merged level (or a piece of the merged file blocks): the lane's row, its
-//                         file's record, its entry k of that file, then fileplan's expansion against the
-//                         merged scratch
+// files_walk.hip -- the kernels of the file walk (files_path.cpp; include/ppfs_ecc.h ppfs_ecc_file_blocks_*,
+// ppfs_ecc_read_file_*, ppfs_ecc_write_file_* and their ppfs_ecc_files_* batch forms).
+//
+// A file's index-block tree is at most three levels deep, and how many index blocks a walk over a range of its
+// file blocks visits at each level follows from the range alone (file_plan.hpp).  Every level of all the files of
+// a call is one merged list (files_plan.hpp), so the walk is one list decode per level with an expansion in
+// between, all queued, nothing read back:
+//   files_expand_kernel   one merged level (or a piece of the merged file blocks): the file that owns the
+//                         lane's entry, its record, the entry's number k within that file, then fileplan's
+//                         expansion against the merged scratch
 //   files_extents_kernel  a piece of merged file blocks: pos = the file's out_pos + its extent's pos
 //   files_merge_kernel    path status over read status, zero fill under a failed index block within the
 //                         file's own range, the counts, the file flags; for a level of the tree also its
 //                         pointers and statuses into the caller's level-major arrays
-// and of the batch write (ppfs_ecc_write_files_*), which reuses the expansion and the extents:
+// and of the writes, which reuse the expansion and the extents:
 //   files_written_init_kernel   written[f] = file f's bytes, one lane per file
 //   files_write_merge_kernel    path status over write status, the counts, the file flags, written[file]
 //                               lowered to the first failing block's position; no payload byte is touched
 // One lane per merged entry, 256 lanes a workgroup; consecutive lanes store consecutive elements.
 //
-// The row lookup: every lane binary-searches the level's table in global memory (owner_of).  The other form
-// that was built and measured -- the workgroup loads the at most 256 rows of its 256 entries into LDS and the
-// lanes search there -- was no faster on either workload of DESIGN.md section 4.11 and lives in
-// tools/ablations/files_lookup_lds.hpp (tools/build_alt.sh files_lds -DPPFS_FILES_LOOKUP_LDS=1).
+// Each kernel is a template on who owns an entry:
+//   OneFile  the call is about one file, whose record and Tree travel by value in the kernel arguments: entry e
+//            is entry k = e of file 0; no table, no search, no global read, no Tree rebuilt per lane
+//   Batch    the batch's records and the level's row table in device memory: every lane binary-searches the
+//            table (owner_of).  The other form that was built and measured -- the workgroup loads the at most
+//            256 rows of its 256 entries into LDS and the lanes search there -- was no faster on either
+//            workload of DESIGN.md section 4.11 and lives in tools/ablations/files_lookup_lds.hpp
+//            (tools/build_alt.sh files_lds -DPPFS_FILES_LOOKUP_LDS=1).
 // Nothing read from the tables is used unchecked: a file number is compared with nfiles, an entry number k
 // with the file's level count, and every scratch position and out position with its array's extent.
 #include <hip/hip_runtime.h>
@@ -26,11 +33,13 @@
 #include "dbg.hpp"
 #include "files_plan.hpp"
 #include "kernels.hpp"
+#include "status_tally.hpp"
 #include <stdint.h>
 
 namespace ppfs {
 
 using filesplan::FileRec;
+using filesplan::OneRec;
 using filesplan::Row;
 
 // the records of the batch and the row table of the level a launch works on (rows: without the sentinel)
@@ -41,7 +50,7 @@ struct FilesTables {
     uint64_t nrows;
 };
 
-// the merged tree scratch, as file_walk.hip's FileSrc reads a single file's
+// the merged tree scratch
 struct FilesMem {
     const uint8_t* payload; // slots * ds bytes
     uint64_t payload_bytes;
@@ -50,6 +59,8 @@ struct FilesMem {
     uint64_t slots;
     __device__ uint32_t status(uint64_t p) const { return PPFS_DBG_OK(st + p, 1, st, slots) && p < slots ? st[p] : 9u; }
     __device__ uint32_t inherited(uint64_t p) const { return PPFS_DBG_OK(inh + p, 1, inh, slots) && p < slots ? inh[p] : 9u; }
+    // a byte, never a dword: ds is rarely a multiple of 4 and the last entry of the last payload ends
+    // where the scratch's payload area does
     __device__ uint32_t payload_byte(uint64_t at) const
     {
         return PPFS_DBG_OK(payload + at, 1, payload, payload_bytes) && at < payload_bytes ? payload[at] : 0xFFu;
@@ -85,20 +96,64 @@ __device__ inline Owner owner_of(const FilesTables& tb, uint64_t w0, uint64_t wn
 }
 #endif
 
+// The two owners.  owner(w0, wn, e, want) as owner_of; rec(f): the record of a file that owner() or has() found;
+// expand(f, ...): filesplan::expand_entry of that file;
+// has(f): file f is one of the call's (written_init's lanes); continues(file, stopped, lane): see there; kAllLanes: owner_of's kOwnerAllLanes.
+struct OneFile {
+    OneRec one;     // the record and the Tree of its range, built once on the host
+    uint64_t count; // the entries of the level the launch works on
+    static constexpr bool kAllLanes = false;
+    static constexpr uint32_t kInitLanes = 64; // written_init's workgroup: one wave for the one word
+    __device__ uint64_t nfiles() const { return 1u; }
+    __device__ bool has(uint64_t f) const { return f == 0u; }
+    __device__ const FileRec& rec(uint32_t) const { return one.rec; }
+    template <class Mem>
+    __device__ fileplan::Expanded expand(uint32_t, int level, uint64_t k, uint64_t ds, const Mem& mem) const
+    {
+        return filesplan::expand_entry(one.rec, one.tree, level, k, ds, mem);
+    }
+    __device__ Owner owner(uint64_t, uint64_t, uint64_t e, bool want) const { return Owner { 0u, e, want && e < count }; }
+    // every lane of the wave: an earlier lane of `stopped` (the ballot of the lanes that lower written[file]) lowers it
+    // to a position no greater than this lane's.  One file: any earlier lane, so only the wave's first one is left
+    __device__ bool continues(uint32_t, unsigned long long stopped, uint32_t lane) const { return (stopped & ((1ull << lane) - 1ull)) != 0; }
+};
+struct Batch {
+    FilesTables tb;
+    static constexpr bool kAllLanes = kOwnerAllLanes;
+    static constexpr uint32_t kInitLanes = 256;
+    __device__ uint64_t nfiles() const { return tb.nfiles; }
+    __device__ bool has(uint64_t f) const { return f < tb.nfiles && PPFS_DBG_OK(tb.recs + f, 128, tb.recs, tb.nfiles * 128); }
+    __device__ const FileRec& rec(uint32_t f) const { return tb.recs[f]; }
+    template <class Mem>
+    __device__ fileplan::Expanded expand(uint32_t f, int level, uint64_t k, uint64_t ds, const Mem& mem) const
+    {
+        return filesplan::expand_entry(tb.recs[f], level, k, ds, mem); // the Tree rebuilt from the record
+    }
+    __device__ Owner owner(uint64_t w0, uint64_t wn, uint64_t e, bool want) const { return owner_of(tb, w0, wn, e, want); }
+    // a batch: the lane before this one, when it has the same file, so the first lane of every run of one file is left.
+    // The shuffle runs in every lane, before anything is decided by it
+    __device__ bool continues(uint32_t file, unsigned long long stopped, uint32_t lane) const
+    {
+        const uint32_t file_before = (uint32_t)__shfl_up((int)file, 1);
+        return lane > 0u && ((stopped >> (lane - 1u)) & 1ull) && file_before == file;
+    }
+};
+
 // merged entries [e0, e0 + n) of a level: pointer[i] and inherited[i] for entry e0 + i (either may be null)
-__global__ __launch_bounds__(256) void files_expand_kernel(FilesTables tb, FilesMem mem, int level, uint64_t e0, uint64_t n,
+template <class Who>
+__global__ __launch_bounds__(256) void files_expand_kernel(Who who, FilesMem mem, int level, uint64_t e0, uint64_t n,
     uint64_t ds, uint32_t* __restrict__ pointer, uint8_t* __restrict__ inherited)
 {
     const uint64_t w0 = (uint64_t)blockIdx.x * 256u, i = w0 + threadIdx.x;
     if (w0 >= n)
         return;
     const bool live = i < n;
-    const Owner o = owner_of(tb, e0 + w0, n - w0 < 256u ? n - w0 : 256u, e0 + i, live);
+    const Owner o = who.owner(e0 + w0, n - w0 < 256u ? n - w0 : 256u, e0 + i, live);
     if (!live)
         return;
     fileplan::Expanded x { fileplan::NO_BLOCK, fileplan::STATUS_OUT };
     if (o.ok)
-        x = filesplan::expand_entry(tb.recs[o.file], level, o.k, ds, mem);
+        x = who.expand(o.file, level, o.k, ds, mem);
     if (pointer && PPFS_DBG_OK(pointer + i, 4, pointer, n * 4))
         pointer[i] = x.pointer;
     if (inherited && PPFS_DBG_OK(inherited + i, 1, inherited, n))
@@ -107,14 +162,15 @@ __global__ __launch_bounds__(256) void files_expand_kernel(FilesTables tb, Files
 
 // ext[i] = the read of merged file block e0 + i: the resolved block, or NO_BLOCK where the path failed, at
 // its file's place in the batch's out
-__global__ __launch_bounds__(256) void files_extents_kernel(FilesTables tb, const uint32_t* __restrict__ pointer,
+template <class Who>
+__global__ __launch_bounds__(256) void files_extents_kernel(Who who, const uint32_t* __restrict__ pointer,
     const uint8_t* __restrict__ path, uint64_t e0, uint64_t n, uint64_t ds, ppfs_ecc_extent* __restrict__ ext)
 {
     const uint64_t w0 = (uint64_t)blockIdx.x * 256u, i = w0 + threadIdx.x;
     if (w0 >= n)
         return;
     const bool live = i < n && PPFS_DBG_OK(pointer + i, 4, pointer, n * 4) && PPFS_DBG_OK(path + i, 1, path, n);
-    const Owner o = owner_of(tb, e0 + w0, n - w0 < 256u ? n - w0 : 256u, e0 + i, live);
+    const Owner o = who.owner(e0 + w0, n - w0 < 256u ? n - w0 : 256u, e0 + i, live);
     if (!live)
         return;
     ppfs_ecc_extent e;
@@ -122,7 +178,7 @@ __global__ __launch_bounds__(256) void files_extents_kernel(FilesTables tb, cons
     e.block = fileplan::NO_BLOCK;
     e.offset = e.length = 0;
     if (o.ok) {
-        const FileRec& rec = tb.recs[o.file];
+        const FileRec& rec = who.rec(o.file);
         const fileplan::Extent x = fileplan::extent_of(o.k, rec.off0, rec.bytes, ds);
         e.pos = rec.out_pos + x.pos;
         e.block = path[i] ? fileplan::NO_BLOCK : pointer[i];
@@ -140,14 +196,13 @@ __global__ __launch_bounds__(256) void files_extents_kernel(FilesTables tb, cons
 //                                       path status 5 is zero-filled within its file's range
 //   flags (may be null)                 flags[file] |= filesplan::flag_of(final) << flag_shift, one atomicOr per
 //                                       lane whose status is non-zero; zeroed on the stream before
-//   counts (may be null)                as file_walk.hip's merge
-__global__ __launch_bounds__(256) void files_merge_kernel(FilesTables tb, const uint8_t* __restrict__ path,
+//   counts (may be null)                counts[slot0 + fileplan::count_slot(final)] grows by one (status_tally.hpp)
+template <class Who>
+__global__ __launch_bounds__(256) void files_merge_kernel(Who who, const uint8_t* __restrict__ path,
     const uint8_t* __restrict__ read, uint64_t e0, uint64_t n, uint8_t* __restrict__ status_out,
     const uint32_t* __restrict__ pointer_in, uint32_t* __restrict__ pointer_out, uint8_t* __restrict__ out, uint64_t out_bytes,
     uint64_t ds, uint32_t* __restrict__ flags, uint32_t flag_shift, unsigned long long* __restrict__ counts, int slot0)
 {
-    __shared__ uint32_t part[4][4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint32_t c[4] = { 0, 0, 0, 0 };
     for (uint64_t w0 = (uint64_t)blockIdx.x * 256u; w0 < n; w0 += (uint64_t)gridDim.x * 256u) {
         const uint64_t i = w0 + threadIdx.x;
@@ -164,14 +219,14 @@ __global__ __launch_bounds__(256) void files_merge_kernel(FilesTables tb, const 
                 pointer_out[i] = pointer_in[i];
         }
         const bool fill = out && p == fileplan::STATUS_FAILED, want = live && ((flags && s) || fill);
-        if (kOwnerAllLanes || want) {
-            const Owner o = owner_of(tb, e0 + w0, n - w0 < 256u ? n - w0 : 256u, e0 + i, want);
+        if (Who::kAllLanes || want) {
+            const Owner o = who.owner(e0 + w0, n - w0 < 256u ? n - w0 : 256u, e0 + i, want);
             if (o.ok) {
                 const uint32_t bit = filesplan::flag_of(s) << flag_shift;
-                if (flags && bit && PPFS_DBG_OK(flags + o.file, 4, flags, tb.nfiles * 4))
+                if (flags && bit && PPFS_DBG_OK(flags + o.file, 4, flags, who.nfiles() * 4))
                     atomicOr(flags + o.file, bit);
                 if (fill) {
-                    const FileRec& rec = tb.recs[o.file];
+                    const FileRec& rec = who.rec(o.file);
                     const fileplan::Extent x = fileplan::extent_of(o.k, rec.off0, rec.bytes, ds);
                     const uint64_t at = rec.out_pos + x.pos;
                     for (uint32_t b = 0; b < x.length; ++b)
@@ -180,37 +235,22 @@ __global__ __launch_bounds__(256) void files_merge_kernel(FilesTables tb, const 
                 }
             }
         }
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            c[q] += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(slot == q));
+        tally_add(c, slot);
     }
-    if (!counts)
-        return;
-    if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            part[wave][q] = c[q];
-    }
-    __syncthreads();
-    if (threadIdx.x < 4u) {
-        const uint32_t q = threadIdx.x;
-        const unsigned long long sum = (unsigned long long)part[0][q] + part[1][q] + part[2][q] + part[3][q];
-        if (sum && PPFS_DBG_OK(counts + slot0 + q, 8, counts, 64))
-            atomicAdd(counts + slot0 + q, sum);
-    }
+    tally_flush(c, counts, slot0, 4);
 }
 
-// written[f] = file f's bytes, one lane per file: what a batch write reports for a file none of whose blocks
-// fails (the write merge lowers it)
-__global__ __launch_bounds__(256) void files_written_init_kernel(const FileRec* __restrict__ recs, uint64_t nfiles,
-    unsigned long long* __restrict__ written)
+// written[f] = file f's bytes, one lane per file: what a write reports for a file none of whose blocks fails
+// (the write merge lowers it)
+template <class Who>
+__global__ __launch_bounds__(256) void files_written_init_kernel(Who who, unsigned long long* __restrict__ written)
 {
-    const uint64_t f = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (f < nfiles && PPFS_DBG_OK(recs + f, 128, recs, nfiles * 128) && PPFS_DBG_OK(written + f, 8, written, nfiles * 8))
-        written[f] = recs[f].bytes;
+    const uint64_t f = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (who.has(f) && PPFS_DBG_OK(written + f, 8, written, who.nfiles() * 8))
+        written[f] = who.rec((uint32_t)f).bytes;
 }
 
-// The merge of a batch WRITE over the merged file blocks e0 + i, i < n: the final status is path[i] where that
+// The merge of a WRITE over the merged file blocks e0 + i, i < n: the final status is path[i] where that
 // is non-zero, else wst[i], the write's.  It reads and writes no payload byte.
 //   status_out (may be null)   the final statuses
 //   flags (may be null)        as files_merge_kernel's, the data bits
@@ -218,12 +258,12 @@ __global__ __launch_bounds__(256) void files_written_init_kernel(const FileRec* 
 //                              status 5 or 9: a 64-bit atomicMin from the first lane of every run of such lanes of
 //                              one file within a wave (positions grow along a file's entries)
 //   counts (may be null)       the tally into the file half
-__global__ __launch_bounds__(256) void files_write_merge_kernel(FilesTables tb, const uint8_t* __restrict__ path,
+template <class Who>
+__global__ __launch_bounds__(256) void files_write_merge_kernel(Who who, const uint8_t* __restrict__ path,
     const uint8_t* __restrict__ wst, uint64_t e0, uint64_t n, uint8_t* __restrict__ status_out, uint64_t ds,
     uint32_t* __restrict__ flags, unsigned long long* __restrict__ written, unsigned long long* __restrict__ counts)
 {
-    __shared__ uint32_t part[4][4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t lane = threadIdx.x & 63u;
     uint32_t c[4] = { 0, 0, 0, 0 };
     for (uint64_t w0 = (uint64_t)blockIdx.x * 256u; w0 < n; w0 += (uint64_t)gridDim.x * 256u) {
         const uint64_t i = w0 + threadIdx.x;
@@ -242,40 +282,24 @@ __global__ __launch_bounds__(256) void files_write_merge_kernel(FilesTables tb, 
         o.file = 0xFFFFFFFFu;
         o.k = 0;
         o.ok = false;
-        if (kOwnerAllLanes || want)
-            o = owner_of(tb, e0 + w0, n - w0 < 256u ? n - w0 : 256u, e0 + i, want);
+        if (Who::kAllLanes || want)
+            o = who.owner(e0 + w0, n - w0 < 256u ? n - w0 : 256u, e0 + i, want);
         const bool stop = o.ok && written && bad;
         const unsigned long long stopped = __builtin_amdgcn_ballot_w64(stop);
-        const uint32_t file_before = (uint32_t)__shfl_up((int)o.file, 1);
-        const bool continues = lane > 0u && ((stopped >> (lane - 1u)) & 1ull) && file_before == o.file;
+        const bool continues = who.continues(o.file, stopped, lane);
         if (o.ok) {
             const uint32_t bit = filesplan::flag_of(s);
-            if (flags && bit && PPFS_DBG_OK(flags + o.file, 4, flags, tb.nfiles * 4))
+            if (flags && bit && PPFS_DBG_OK(flags + o.file, 4, flags, who.nfiles() * 4))
                 atomicOr(flags + o.file, bit);
-            if (stop && !continues && PPFS_DBG_OK(written + o.file, 8, written, tb.nfiles * 8)) {
-                const FileRec& rec = tb.recs[o.file];
+            if (stop && !continues && PPFS_DBG_OK(written + o.file, 8, written, who.nfiles() * 8)) {
+                const FileRec& rec = who.rec(o.file);
                 const uint64_t pos = fileplan::extent_of(o.k, rec.off0, rec.bytes, ds).pos;
                 atomicMin(written + o.file, (unsigned long long)(pos < rec.bytes ? pos : rec.bytes));
             }
         }
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            c[q] += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(slot == q));
+        tally_add(c, slot);
     }
-    if (!counts)
-        return;
-    if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            part[wave][q] = c[q];
-    }
-    __syncthreads();
-    if (threadIdx.x < 4u) {
-        const uint32_t q = threadIdx.x;
-        const unsigned long long sum = (unsigned long long)part[0][q] + part[1][q] + part[2][q] + part[3][q];
-        if (sum && PPFS_DBG_OK(counts + fileplan::SLOT_FILE + q, 8, counts, 64))
-            atomicAdd(counts + fileplan::SLOT_FILE + q, sum);
-    }
+    tally_flush(c, counts, fileplan::SLOT_FILE, 4);
 }
 
 static bool grid_of(uint64_t n, uint32_t& grid)
@@ -284,92 +308,109 @@ static bool grid_of(uint64_t n, uint32_t& grid)
     grid = (uint32_t)g;
     return g <= 0x7FFFFFFFull;
 }
-static bool tables_ok(const void* recs, uint64_t nfiles, const void* rows, uint64_t nrows)
+// The launch's owner out of the ABI's ppfs_files_owner, handed to fn: the tables checked, or the one file's record
+// copied with its entries at `level`
+template <class Fn>
+static hipError_t with_owner(const ppfs_files_owner* w, int level, Fn fn)
 {
-    return recs && rows && nfiles >= 1 && nfiles < 0xFFFFFFFFull && nrows >= 1 && nrows <= nfiles
-        && !(((uintptr_t)recs | (uintptr_t)rows) & 7u);
+    if (!w || level < fileplan::LEVEL_A || level > fileplan::LEVEL_DATA)
+        return hipErrorInvalidValue;
+    if (w->one) {
+        const OneRec& one = *(const OneRec*)w->one;
+        return fn(OneFile { one, fileplan::level_count(one.tree, level) });
+    }
+    if (!w->recs || !w->rows || (((uintptr_t)w->recs | (uintptr_t)w->rows) & 7u) || w->nfiles < 1 || w->nfiles >= 0xFFFFFFFFull
+        || w->nrows < 1 || w->nrows > w->nfiles)
+        return hipErrorInvalidValue;
+    return fn(Batch { FilesTables { (const FileRec*)w->recs, w->nfiles, (const Row*)w->rows, w->nrows } });
+}
+// the merges: grid-stride, at most 2,048 workgroups
+static uint32_t merge_grid(uint64_t n)
+{
+    const uint64_t want = (n + 255u) / 256u;
+    return (uint32_t)(want < 2048u ? want : 2048u);
 }
 
 } // namespace ppfs
 
 using namespace ppfs;
 
-extern "C" hipError_t ppfs_files_expand_launch(const void* recs, uint64_t nfiles, const void* rows, uint64_t nrows, int level,
-    uint64_t e0, uint64_t n, uint64_t ds, const uint8_t* payload, const uint8_t* st, const uint8_t* inh, uint64_t slots,
-    uint32_t* pointer, uint8_t* inherited, hipStream_t s)
-{
-    uint32_t grid;
-    if (n == 0)
-        return hipSuccess;
-    if (!tables_ok(recs, nfiles, rows, nrows) || level < fileplan::LEVEL_A || level > fileplan::LEVEL_DATA
-        || ((uintptr_t)pointer & 3u) || !grid_of(n, grid))
-        return hipErrorInvalidValue;
-    const FilesTables tb { (const FileRec*)recs, nfiles, (const Row*)rows, nrows };
-    const FilesMem mem { payload, slots * ds, st, inh, slots };
-    hipLaunchKernelGGL(files_expand_kernel, dim3(grid), dim3(256), 0, s, tb, mem, level, e0, n, ds, pointer, inherited);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t ppfs_files_extents_launch(const void* recs, uint64_t nfiles, const void* rows, uint64_t nrows,
-    const uint32_t* pointer, const uint8_t* path, uint64_t e0, uint64_t n, uint64_t ds, ppfs_ecc_extent* ext,
+extern "C" hipError_t ppfs_files_expand_launch(const ppfs_files_owner* owner, int level, uint64_t e0, uint64_t n, uint64_t ds,
+    const uint8_t* payload, const uint8_t* st, const uint8_t* inh, uint64_t slots, uint32_t* pointer, uint8_t* inherited,
     hipStream_t s)
 {
     uint32_t grid;
     if (n == 0)
         return hipSuccess;
-    if (!tables_ok(recs, nfiles, rows, nrows) || !pointer || !path || !ext || ds == 0 || ds > 0xFFFFu || ((uintptr_t)pointer & 3u)
-        || ((uintptr_t)ext & 7u) || !grid_of(n, grid))
+    if (((uintptr_t)pointer & 3u) || !grid_of(n, grid))
         return hipErrorInvalidValue;
-    const FilesTables tb { (const FileRec*)recs, nfiles, (const Row*)rows, nrows };
-    hipLaunchKernelGGL(files_extents_kernel, dim3(grid), dim3(256), 0, s, tb, pointer, path, e0, n, ds, ext);
-    return hipGetLastError();
+    const FilesMem mem { payload, slots * ds, st, inh, slots };
+    return with_owner(owner, level, [&](auto who) {
+        hipLaunchKernelGGL(files_expand_kernel<decltype(who)>, dim3(grid), dim3(256), 0, s, who, mem, level, e0, n, ds, pointer,
+            inherited);
+        return hipGetLastError();
+    });
 }
 
-extern "C" hipError_t ppfs_files_merge_launch(const void* recs, uint64_t nfiles, const void* rows, uint64_t nrows,
-    const uint8_t* path, const uint8_t* read, uint64_t e0, uint64_t n, uint8_t* status_out, const uint32_t* pointer_in,
-    uint32_t* pointer_out, uint8_t* out, uint64_t out_bytes, uint64_t ds, uint32_t* flags, uint32_t flag_shift,
-    unsigned long long* counts, int slot0, hipStream_t s)
+extern "C" hipError_t ppfs_files_extents_launch(const ppfs_files_owner* owner, const uint32_t* pointer, const uint8_t* path,
+    uint64_t e0, uint64_t n, uint64_t ds, ppfs_ecc_extent* ext, hipStream_t s)
+{
+    uint32_t grid;
+    if (n == 0)
+        return hipSuccess;
+    if (!pointer || !path || !ext || ds == 0 || ds > 0xFFFFu || ((uintptr_t)pointer & 3u) || ((uintptr_t)ext & 7u) || !grid_of(n, grid))
+        return hipErrorInvalidValue;
+    return with_owner(owner, fileplan::LEVEL_DATA, [&](auto who) {
+        hipLaunchKernelGGL(files_extents_kernel<decltype(who)>, dim3(grid), dim3(256), 0, s, who, pointer, path, e0, n, ds, ext);
+        return hipGetLastError();
+    });
+}
+
+extern "C" hipError_t ppfs_files_merge_launch(const ppfs_files_owner* owner, int level, const uint8_t* path, const uint8_t* read,
+    uint64_t e0, uint64_t n, uint8_t* status_out, const uint32_t* pointer_in, uint32_t* pointer_out, uint8_t* out,
+    uint64_t out_bytes, uint64_t ds, uint32_t* flags, unsigned long long* counts, hipStream_t s)
 {
     if (n == 0 || (!status_out && !pointer_out && !out && !counts && !flags))
         return hipSuccess;
-    if (!tables_ok(recs, nfiles, rows, nrows) || !path || (pointer_out && !pointer_in)
-        || (((uintptr_t)pointer_in | (uintptr_t)pointer_out | (uintptr_t)flags) & 3u) || ((uintptr_t)counts & 7u)
-        || (slot0 != fileplan::SLOT_FILE && slot0 != fileplan::SLOT_INDEX) || flag_shift > 8u || (out && ds == 0))
+    if (!path || (pointer_out && !pointer_in) || (((uintptr_t)pointer_in | (uintptr_t)pointer_out | (uintptr_t)flags) & 3u)
+        || ((uintptr_t)counts & 7u) || (out && ds == 0))
         return hipErrorInvalidValue;
-    const uint64_t want = (n + 255u) / 256u;
-    const uint32_t grid = (uint32_t)(want < 2048u ? want : 2048u);
-    const FilesTables tb { (const FileRec*)recs, nfiles, (const Row*)rows, nrows };
-    hipLaunchKernelGGL(files_merge_kernel, dim3(grid), dim3(256), 0, s, tb, path, read, e0, n, status_out,
-            pointer_out ? pointer_in : nullptr, pointer_out, out, out_bytes, ds, flags, flag_shift, counts, slot0);
-    return hipGetLastError();
+    const bool tree = level != fileplan::LEVEL_DATA;
+    return with_owner(owner, level, [&](auto who) {
+        hipLaunchKernelGGL(files_merge_kernel<decltype(who)>, dim3(merge_grid(n)), dim3(256), 0, s, who, path, read, e0, n, status_out,
+            pointer_out ? pointer_in : nullptr, pointer_out, out, out_bytes, ds, flags, tree ? filesplan::FLAG_TREE_SHIFT : 0u, counts,
+            tree ? fileplan::SLOT_INDEX : fileplan::SLOT_FILE);
+        return hipGetLastError();
+    });
 }
 
-extern "C" hipError_t ppfs_files_written_init_launch(const void* recs, uint64_t nfiles, unsigned long long* written, hipStream_t s)
+extern "C" hipError_t ppfs_files_written_init_launch(const ppfs_files_owner* owner, unsigned long long* written, hipStream_t s)
 {
     uint32_t grid;
+    const uint64_t nfiles = owner ? (owner->one ? 1u : owner->nfiles) : 0u;
     if (!written || nfiles == 0)
         return hipSuccess;
-    if (!recs || nfiles >= 0xFFFFFFFFull || (((uintptr_t)recs | (uintptr_t)written) & 7u) || !grid_of(nfiles, grid))
+    if (((uintptr_t)written & 7u) || !grid_of(nfiles, grid))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(files_written_init_kernel, dim3(grid), dim3(256), 0, s, (const FileRec*)recs, nfiles, written);
-    return hipGetLastError();
+    return with_owner(owner, fileplan::LEVEL_DATA, [&](auto who) {
+        hipLaunchKernelGGL(files_written_init_kernel<decltype(who)>, dim3(grid), dim3(decltype(who)::kInitLanes), 0, s, who, written);
+        return hipGetLastError();
+    });
 }
 
-extern "C" hipError_t ppfs_files_write_merge_launch(const void* recs, uint64_t nfiles, const void* rows, uint64_t nrows,
-    const uint8_t* path, const uint8_t* wst, uint64_t e0, uint64_t n, uint8_t* status_out, uint64_t ds, uint32_t* flags,
-    unsigned long long* written, unsigned long long* counts, hipStream_t s)
+extern "C" hipError_t ppfs_files_write_merge_launch(const ppfs_files_owner* owner, const uint8_t* path, const uint8_t* wst, uint64_t e0,
+    uint64_t n, uint8_t* status_out, uint64_t ds, uint32_t* flags, unsigned long long* written, unsigned long long* counts,
+    hipStream_t s)
 {
     if (n == 0 || (!status_out && !flags && !written && !counts))
         return hipSuccess;
-    if (!tables_ok(recs, nfiles, rows, nrows) || !path || ((uintptr_t)flags & 3u) || (((uintptr_t)written | (uintptr_t)counts) & 7u)
-        || ds == 0)
+    if (!path || ((uintptr_t)flags & 3u) || (((uintptr_t)written | (uintptr_t)counts) & 7u) || ds == 0)
         return hipErrorInvalidValue;
-    const uint64_t want = (n + 255u) / 256u;
-    const uint32_t grid = (uint32_t)(want < 2048u ? want : 2048u);
-    const FilesTables tb { (const FileRec*)recs, nfiles, (const Row*)rows, nrows };
-    hipLaunchKernelGGL(files_write_merge_kernel, dim3(grid), dim3(256), 0, s, tb, path, wst, e0, n, status_out, ds, flags, written,
-        counts);
-    return hipGetLastError();
+    return with_owner(owner, fileplan::LEVEL_DATA, [&](auto who) {
+        hipLaunchKernelGGL(files_write_merge_kernel<decltype(who)>, dim3(merge_grid(n)), dim3(256), 0, s, who, path, wst, e0, n,
+            status_out, ds, flags, written, counts);
+        return hipGetLastError();
+    });
 }
 
 // this unit's PPFS_ECC_DEBUG counter, summed into ppfs_ecc_debug_faults (api.cpp)

@@ -1,8 +1,7 @@
 // kernels.hpp -- the host-callable launchers of the kernel translation units, declared once:
 // rs_kernels.hip (Reed-Solomon and its servers), bit_kernels.hip (CRC, Hamming, parity and the bit
 // server) vote.hip (vote, copy, gather, patch list, inject, flag, block lists), alloc_scan.hip (bitmap
-// expansion, scrub tally), file_walk.hip (the file walk's expansion, extents and merge) and files_walk.hip
-// (the same for a batch of files).  The
+// expansion, scrub tally) and files_walk.hip (the file walk's expansion, extents and merges).  The
 // three table-sizing functions are in host_tables.hpp, beside the builders that use them.
 #pragma once
 
@@ -10,8 +9,19 @@
 #include <stdint.h>
 
 #include "../../include/ppfs_ecc.h" // ppfs_ecc_extent, ppfs_ecc_file
-#include "file_plan.hpp"
 #include "server_box.hpp"
+
+// Who owns the entries of a launch of the file walk.  A batch: recs, its nfiles filesplan::FileRec, and rows, the nrows
+// filesplan::Row of the level the launch works on (sentinel not counted), both in device memory, 8-byte aligned; one
+// null.  ONE file: one, a HOST pointer to its filesplan::OneRec (the record and the Tree of its range), which travels
+// to the kernel by value; the other fields are not read.
+struct ppfs_files_owner {
+    const void* recs;
+    uint64_t nfiles;
+    const void* rows;
+    uint64_t nrows;
+    const void* one;
+};
 
 extern "C" {
 int ppfs_rs_fast_supported(int n, int t2);
@@ -92,48 +102,29 @@ hipError_t ppfs_alloc_expand_launch(const uint8_t* stream, const uint8_t* bstatu
 hipError_t ppfs_alloc_iota_launch(uint32_t* index, uint32_t first, uint64_t n, hipStream_t s);
 hipError_t ppfs_scrub_tally_launch(const uint8_t* st, const uint32_t* index, uint64_t n, uint32_t first, uint8_t* status_out,
     uint64_t out_n, unsigned long long* counts, int slot0, int ncat, hipStream_t s);
-// the read-only file walk (file_path.cpp; file_walk.hip, arithmetic in file_plan.hpp).  file and tree are
-// host pointers, passed to the kernels by value; payload / st / inh: the tree's scratch, fileplan::tree_slots
-// entries (ds bytes, 1 and 1 byte each).
-// expand: entries [k0, k0 + n) of a level -> pointer[i] (4-byte aligned) and inherited[i], either may be null.
-// extents: the ppfs_ecc_extent entries (8-byte aligned) of blocks [i0, i0 + n) of a read of `bytes` bytes that
-// starts at payload byte off0 of its first block; NO_BLOCK where path[i] != 0.
-// merge: status_out[i] = path[i] ? path[i] : read[i] (read null: 0); pointer_out[i] = pointer_in[i]; out's range of
-// a block with path status 5 zero-filled; counts[slot0 + slot] (slot0: fileplan::SLOT_FILE / SLOT_INDEX).
-hipError_t ppfs_file_expand_launch(const ppfs_ecc_file* file, const ppfs::fileplan::Tree* tree, int level, uint64_t k0, uint64_t n,
-    uint64_t ds, const uint8_t* payload, const uint8_t* st, const uint8_t* inh, uint32_t* pointer, uint8_t* inherited,
+// the file walk (files_path.cpp; files_walk.hip, arithmetic in file_plan.hpp and files_plan.hpp).  owner: who owns the
+// launch's entries (ppfs_files_owner above); e0: the merged entry of element 0 of the launch's arrays; payload / st /
+// inh: the merged tree scratch of `slots` entries (ds bytes, 1 and 1 byte each).
+// expand: merged entries [e0, e0 + n) of a level -> pointer[i] (4-byte aligned) and inherited[i], either may be null.
+// extents: the ppfs_ecc_extent entries (8-byte aligned) of the merged file blocks [e0, e0 + n), each at its file's place
+// in the call's buffer; NO_BLOCK where path[i] != 0.
+// merge: status_out[i] = path[i] ? path[i] : read[i] (read null: 0); pointer_out[i] = pointer_in[i]; out's (out_bytes
+// bytes) range of a block with path status 5 zero-filled; flags[file] |= filesplan::flag_of(final status), and the
+// counts, in the tree half for a level of the tree and in the data half for LEVEL_DATA.
+// written_init: written[f] = file f's bytes (8-byte aligned; null: nothing).
+// write_merge: status_out[i] = path[i] ? path[i] : wst[i]; counts' file half; flags[file]; written[file] lowered by a
+// 64-bit atomicMin to the position, within the file's bytes, of a block whose final status is 5 or 9.  No payload byte
+// is read or written.
+hipError_t ppfs_files_expand_launch(const ppfs_files_owner* owner, int level, uint64_t e0, uint64_t n, uint64_t ds,
+    const uint8_t* payload, const uint8_t* st, const uint8_t* inh, uint64_t slots, uint32_t* pointer, uint8_t* inherited,
     hipStream_t s);
-hipError_t ppfs_file_extents_launch(const uint32_t* pointer, const uint8_t* path, uint64_t i0, uint64_t n, uint64_t off0,
-    uint64_t bytes, uint64_t ds, ppfs_ecc_extent* ext, hipStream_t s);
-hipError_t ppfs_file_merge_launch(const uint8_t* path, const uint8_t* read, uint64_t n, uint8_t* status_out,
-    const uint32_t* pointer_in, uint32_t* pointer_out, uint8_t* out, uint64_t i0, uint64_t off0, uint64_t bytes, uint64_t ds,
-    unsigned long long* counts, int slot0, hipStream_t s);
-// the walk over a batch of files (files_path.cpp; files_walk.hip, arithmetic in files_plan.hpp).  recs: the
-// batch's nfiles filesplan::FileRec; rows: the nrows filesplan::Row of the level the launch works on (sentinel
-// not counted); both in device memory, 8-byte aligned.  e0: the merged entry of element 0 of the launch's
-// arrays.  Otherwise as the three launchers above, with
-// payload / st / inh the merged scratch of `slots` entries, out the batch's buffer of out_bytes bytes and
-// flags[file] |= filesplan::flag_of(final status) << flag_shift.
-hipError_t ppfs_files_expand_launch(const void* recs, uint64_t nfiles, const void* rows, uint64_t nrows, int level, uint64_t e0,
-    uint64_t n, uint64_t ds, const uint8_t* payload, const uint8_t* st, const uint8_t* inh, uint64_t slots, uint32_t* pointer,
-    uint8_t* inherited, hipStream_t s);
-hipError_t ppfs_files_extents_launch(const void* recs, uint64_t nfiles, const void* rows, uint64_t nrows, const uint32_t* pointer,
-    const uint8_t* path, uint64_t e0, uint64_t n, uint64_t ds, ppfs_ecc_extent* ext, hipStream_t s);
-hipError_t ppfs_files_merge_launch(const void* recs, uint64_t nfiles, const void* rows, uint64_t nrows, const uint8_t* path,
-    const uint8_t* read, uint64_t e0, uint64_t n, uint8_t* status_out, const uint32_t* pointer_in, uint32_t* pointer_out,
-    uint8_t* out, uint64_t out_bytes, uint64_t ds, uint32_t* flags, uint32_t flag_shift, unsigned long long* counts, int slot0,
+hipError_t ppfs_files_extents_launch(const ppfs_files_owner* owner, const uint32_t* pointer, const uint8_t* path, uint64_t e0,
+    uint64_t n, uint64_t ds, ppfs_ecc_extent* ext, hipStream_t s);
+hipError_t ppfs_files_merge_launch(const ppfs_files_owner* owner, int level, const uint8_t* path, const uint8_t* read, uint64_t e0,
+    uint64_t n, uint8_t* status_out, const uint32_t* pointer_in, uint32_t* pointer_out, uint8_t* out, uint64_t out_bytes,
+    uint64_t ds, uint32_t* flags, unsigned long long* counts, hipStream_t s);
+hipError_t ppfs_files_written_init_launch(const ppfs_files_owner* owner, unsigned long long* written, hipStream_t s);
+hipError_t ppfs_files_write_merge_launch(const ppfs_files_owner* owner, const uint8_t* path, const uint8_t* wst, uint64_t e0,
+    uint64_t n, uint8_t* status_out, uint64_t ds, uint32_t* flags, unsigned long long* written, unsigned long long* counts,
     hipStream_t s);
-// the file writes (file_path.cpp, files_path.cpp ppfs_ecc_write_file_* / ppfs_ecc_write_files_*): the walk's expand and
-// extents launchers above, then
-// written_init: *written = bytes / written[f] = recs[f].bytes (8-byte aligned; null: nothing).
-// write_merge: status_out[i] = path[i] ? path[i] : wst[i]; counts' file half; flags[file] (batch); written (the file's
-// entry in the batch) lowered by a 64-bit atomicMin to the position, within the range's bytes, of a block whose final
-// status is 5 or 9.  No payload byte is read or written.
-hipError_t ppfs_file_written_init_launch(unsigned long long* written, uint64_t bytes, hipStream_t s);
-hipError_t ppfs_file_write_merge_launch(const uint8_t* path, const uint8_t* wst, uint64_t n, uint8_t* status_out, uint64_t i0,
-    uint64_t off0, uint64_t bytes, uint64_t ds, unsigned long long* written, unsigned long long* counts, hipStream_t s);
-hipError_t ppfs_files_written_init_launch(const void* recs, uint64_t nfiles, unsigned long long* written, hipStream_t s);
-hipError_t ppfs_files_write_merge_launch(const void* recs, uint64_t nfiles, const void* rows, uint64_t nrows, const uint8_t* path,
-    const uint8_t* wst, uint64_t e0, uint64_t n, uint8_t* status_out, uint64_t ds, uint32_t* flags, unsigned long long* written,
-    unsigned long long* counts, hipStream_t s);
 }

@@ -65,7 +65,7 @@ private:
 };
 
 // The context's scrub scratch (scrub_path.cpp), which the scrubs of named blocks and the file walk
-// (file_path.cpp) use: at least `bytes` of it for work queued on s, after a wait for its previous user;
+// (files_path.cpp) use: at least `bytes` of it for work queued on s, after a wait for its previous user;
 // scrub_scratch_used after the call's last use of it was queued on s (also after a failure).
 int scrub_scratch(ppfs_ecc_ctx* c, size_t bytes, hipStream_t s, uint8_t** out);
 void scrub_scratch_used(ppfs_ecc_ctx* c, hipStream_t s);

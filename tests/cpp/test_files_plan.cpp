@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <utility>
 #include <vector>
 
@@ -206,28 +207,89 @@ static void check_batch(uint64_t ds, const std::vector<File>& files, bool whole)
         }
 }
 
+// every (first, count) shape of the small trees; the large trees' edges, and 40 drawn
+static std::vector<std::pair<uint64_t, uint64_t>> shapes_of(uint64_t ds)
+{
+    const uint64_t I = ipb_of(ds), cap = capacity_ipb(I);
+    std::vector<std::pair<uint64_t, uint64_t>> shapes;
+    if (I <= 3) {
+        for (uint64_t first = 0; first < cap; ++first)
+            for (uint64_t count = 0; first + count <= cap; ++count)
+                shapes.push_back({ first, count });
+        return shapes;
+    }
+    const uint64_t edges[] = { 0, 1, 11, 12, 13, 12 + I - 1, 12 + I, 12 + I + 1, 12 + I + I * I - 1, 12 + I + I * I, 12 + I + I * I + I,
+        cap - 1 };
+    for (uint64_t a : edges)
+        for (uint64_t b : edges)
+            if (a <= b)
+                shapes.push_back({ a, b - a + (b < cap ? 1 : 0) });
+    for (int q = 0; q < 40; ++q) {
+        const uint64_t first = rnd_below(cap);
+        shapes.push_back({ first, rnd_below(cap - first + 1) });
+    }
+    return shapes;
+}
+
+// build_one, the plan of the single-file calls (which know their range as blocks), against build() of a batch of
+// that one file and the equivalent byte range: the same slot, record, rows, totals and levels; and the scratch
+// layout is the single-file one of file_plan.hpp
+static void test_one_file()
+{
+    for (uint64_t ds : { (uint64_t)2, (uint64_t)3, (uint64_t)5, (uint64_t)9, (uint64_t)12, (uint64_t)16, (uint64_t)58, (uint64_t)508 })
+        for (const std::pair<uint64_t, uint64_t>& sh : shapes_of(ds)) {
+            const File f = make_file(ds, sh.first, sh.second);
+            const uint64_t range[2] = { f.offset, f.nbytes };
+            fp::Plan batch;
+            fp::OnePlan one;
+            uint64_t bad = 99;
+            const int r = fp::build(f.rec, range, 1, ds, batch, &bad);
+            CHECK(r == fp::RANGE_OK, "ds %llu: a valid file is refused (%d)", (unsigned long long)ds, r);
+            if (r != fp::RANGE_OK)
+                continue;
+            const Span sp = span(f.rec[15], ds, f.offset, f.nbytes);
+            CHECK(sp.ok && sp.first == f.first && sp.count == f.count && sp.bytes == f.bytes, "the test's own range");
+            fp::build_one(f.rec, sp.first, sp.count, f.offset % ds, sp.bytes, ds, one);
+            const unsigned long long a = sp.first, b = sp.count;
+            CHECK(!std::memcmp(&one.slot, &batch.slots[0], sizeof(fp::Slot)), "ds %llu [%llu, +%llu): slot", (unsigned long long)ds, a, b);
+            CHECK(!std::memcmp(&one.one.rec, &batch.recs[0], sizeof(fp::FileRec)), "ds %llu [%llu, +%llu): record", (unsigned long long)ds, a, b);
+            CHECK(!std::memcmp(&one.total, &batch.total, sizeof(fp::Totals)), "ds %llu [%llu, +%llu): totals", (unsigned long long)ds, a, b);
+            CHECK(!std::memcmp(&one.levels, &batch.levels, sizeof(fp::Levels)), "ds %llu [%llu, +%llu): levels", (unsigned long long)ds, a, b);
+            // the two views: what the walk reads
+            const fp::PlanView v1 = one.view(), vb = batch.view();
+            CHECK(v1.nfiles == 1 && vb.nfiles == 1 && v1.recs == &one.one.rec && !std::memcmp(&v1.total, &vb.total, sizeof(fp::Totals))
+                    && !std::memcmp(&v1.levels, &vb.levels, sizeof(fp::Levels)),
+                "ds %llu [%llu, +%llu): views", (unsigned long long)ds, a, b);
+            for (int l = 0; l < fp::LEVELS; ++l) {
+                CHECK(v1.nrows[l] == vb.nrows[l] && vb.nrows[l] + 1 == batch.rows[l].size(), "ds %llu [%llu, +%llu): level %d rows",
+                    (unsigned long long)ds, a, b, l);
+                for (size_t q = 0; q <= v1.nrows[l] && q <= vb.nrows[l]; ++q) // the sentinel too
+                    CHECK(v1.rows[l][q].first == vb.rows[l][q].first && v1.rows[l][q].file == vb.rows[l][q].file
+                            && v1.rows[l][q].pad == vb.rows[l][q].pad,
+                        "ds %llu [%llu, +%llu): level %d row %llu", (unsigned long long)ds, a, b, l, (unsigned long long)q);
+            }
+            const Tree t = tree_of(sp.first, sp.count, ipb_of(ds));
+            const Tree& u = one.one.tree;
+            CHECK(u.j0 == t.j0 && u.j1 == t.j1 && u.I == t.I && u.S1 == t.S1 && u.S2 == t.S2 && u.a_ind == t.a_ind && u.a_dbl == t.a_dbl
+                    && u.a_trb == t.a_trb && u.d0 == t.d0 && u.d1 == t.d1 && u.t0 == t.t0 && u.t1 == t.t1 && u.nA == t.nA && u.nBd == t.nBd
+                    && u.nBt == t.nBt && u.nB == t.nB && u.nC == t.nC,
+                "ds %llu [%llu, +%llu): the range's tree", (unsigned long long)ds, a, b);
+            if (tree_blocks(t)) {
+                for (int l = 0; l < 3; ++l)
+                    CHECK(one.one.rec.lvl[l] == slot_base(t, l), "ds %llu [%llu, +%llu): level %d starts at the single-file slot",
+                        (unsigned long long)ds, a, b, l);
+                CHECK(one.levels.slots == tree_slots(t), "ds %llu [%llu, +%llu): the single-file scratch slots", (unsigned long long)ds, a, b);
+            } else {
+                CHECK(one.levels.slots == 0, "ds %llu [%llu, +%llu): no tree, no slots", (unsigned long long)ds, a, b);
+            }
+        }
+}
+
 static void test_batches()
 {
     for (uint64_t ds : { (uint64_t)3, (uint64_t)5, (uint64_t)9, (uint64_t)12, (uint64_t)58 }) {
         const uint64_t I = ipb_of(ds), cap = capacity_ipb(I);
-        // every (first, count) shape of the small trees leads one batch; the large tree's are drawn
-        std::vector<std::pair<uint64_t, uint64_t>> shapes;
-        if (I <= 3) {
-            for (uint64_t first = 0; first < cap; ++first)
-                for (uint64_t count = 0; first + count <= cap; ++count)
-                    shapes.push_back({ first, count });
-        } else {
-            const uint64_t edges[] = { 0, 1, 11, 12, 13, 12 + I - 1, 12 + I, 12 + I + 1, 12 + I + I * I - 1, 12 + I + I * I,
-                12 + I + I * I + I, cap - 1 };
-            for (uint64_t a : edges)
-                for (uint64_t b : edges)
-                    if (a <= b)
-                        shapes.push_back({ a, b - a + (b < cap ? 1 : 0) });
-            for (int q = 0; q < 40; ++q) {
-                const uint64_t first = rnd_below(cap);
-                shapes.push_back({ first, rnd_below(cap - first + 1) });
-            }
-        }
+        const std::vector<std::pair<uint64_t, uint64_t>> shapes = shapes_of(ds);
         for (size_t s = 0; s < shapes.size(); ++s) {
             const uint64_t nfiles = 1 + s % 6;
             std::vector<File> files;
@@ -301,6 +363,7 @@ static void test_refusals()
 int main()
 {
     test_batches();
+    test_one_file();
     test_refusals();
     if (g_fail) {
         std::printf("%d checks failed\n", g_fail);

@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "paritypartyfs_amd", "_lib", "libppfs_ecc.so")
 NAMES = ("ppfs_ecc_file_span", "ppfs_ecc_file_tree_blocks", "ppfs_ecc_file_blocks_device", "ppfs_ecc_file_blocks_host",
          "ppfs_ecc_read_file_device", "ppfs_ecc_read_file_host")
-KERNELS = ("file_expand_kernel", "file_extents_kernel", "file_merge_kernel")
+KERNELS = ("files_expand_kernelINS_7OneFileE", "files_extents_kernelINS_7OneFileE", "files_merge_kernelINS_7OneFileE")
 
 
 @pytest.fixture(scope="module")

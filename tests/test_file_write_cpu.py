@@ -15,7 +15,8 @@ from tests.test_kernel_resources import kernel_descriptors
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "paritypartyfs_amd", "_lib", "libppfs_ecc.so")
 NAMES = ("ppfs_ecc_write_file_device", "ppfs_ecc_write_file_host", "ppfs_ecc_write_files_device", "ppfs_ecc_write_files_host")
-KERNELS = ("file_written_init_kernel", "file_write_merge_kernel", "files_written_init_kernel", "files_write_merge_kernel")
+KERNELS = ("files_written_init_kernelINS_7OneFileE", "files_write_merge_kernelINS_7OneFileE", "files_written_init_kernelINS_5BatchE",
+           "files_write_merge_kernelINS_5BatchE")
 
 
 @pytest.fixture(scope="module")

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "paritypartyfs_amd", "_lib", "libppfs_ecc.so")
 NAMES = ("ppfs_ecc_files_plan", "ppfs_ecc_files_blocks_device", "ppfs_ecc_files_blocks_host", "ppfs_ecc_read_files_device",
          "ppfs_ecc_read_files_host")
-KERNELS = ("files_expand_kernel", "files_extents_kernel", "files_merge_kernel")
+KERNELS = ("files_expand_kernelINS_5BatchE", "files_extents_kernelINS_5BatchE", "files_merge_kernelINS_5BatchE")
 
 
 @pytest.fixture(scope="module")

@@ -594,6 +594,71 @@ def test_two_reads_of_one_context_on_two_streams(oracle):
         assert np.array_equal(img, e_img)
 
 
+def test_single_file_calls_between_two_batches_on_one_stream(oracle):
+    """read_files, read_file, write_file and read_files again on one stream with nothing in between.  The single-file
+    calls run the batch's walk in the same scratch, their record in the kernel arguments where a batch has tables: they
+    must neither disturb a batch's tables nor depend on them.  rs64_t3 (ds 58, ipb 14), one file of 12 + 14 + 3 blocks
+    (levels A and B), one flipped byte in the doubly root, which the first call corrects and writes back.  Every
+    result against the oracle's walk (the reads) and the per-block loop over its device model (the write)."""
+    from tests.test_gpu_file_write import Img
+    from tests.test_gpu_files import bits
+
+    fi = FileImage(oracle, "rs64_t3", n=12 + 14 + 3, damage_data=False)
+    ds, size, f = fi.ds, int(fi.file["file_size"][0]), fi.file
+    assert (ds, fi.I) == (58, 14) and [len(lv) for lv in tree_ids(0, fi.n, fi.I)] == [2, 1, 0]
+    start = fi.clean.copy()
+    start.reshape(fi.blocks, fi.raw)[fi.node_blk[(2,)], 9] ^= 0x5A
+    batch = [(0, size), (0, 5 * ds)]  # the file, and its first 5 blocks: no tree
+    files, ranges = np.concatenate([f, f]), np.array(batch, np.uint64)
+    one = (13 * ds + 5, 12 * ds)  # through both roots and the leaf
+    w_off, w_bytes = 20 * ds + 7, 6 * ds + 11  # from the singly into the doubly tree, mid-block at both ends
+    data = rng_for("between").integers(0, 256, w_bytes, dtype=np.uint8)
+
+    def expect_batch(image):
+        """out, status, flags, counts, the image afterwards of the batch on `image`"""
+        fi.image = image
+        per = [fi.read(o, nb) for o, nb in batch]
+        assert np.array_equal(per[1][5], image)  # five clean direct blocks: nothing to write back
+        counts = FileCounts(*np.sum([list(p[3]) for p in per], axis=0).tolist())
+        flags = np.array([bits(p[2]) | bits(p[4]) << 8 for p in per], np.uint32)
+        return np.concatenate([p[1] for p in per]), np.concatenate([p[2] for p in per]), flags, counts, per[0][5]
+
+    e1 = expect_batch(start)
+    assert e1[3].index_corrected == 1 and e1[2].tolist() == [1 << 8, 0] and np.array_equal(e1[4], fi.clean)
+    fi.image = e1[4]
+    (_, one_cnt, one_bytes), e2_out, e2_st, e2_counts, _, e2_img = fi.read(*one)
+    assert np.array_equal(e2_img, e1[4])
+    e3 = Img(fi).loop([0], [(w_off, w_bytes)], data)
+    assert int(e3["written"][0]) == w_bytes and not np.array_equal(e3["image"], e2_img)
+    e4 = expect_batch(e3["image"])
+    assert e4[3].index_corrected == 0 and not np.array_equal(e4[0], e1[0])
+
+    g = Guarded(start)
+    nb, nbytes = fi.n + 5, size + 5 * ds
+    outs = [torch.full((nbytes,), 0x5A, dtype=torch.uint8, device="cuda") for _ in range(2)]
+    sts = [torch.full((nb,), 77, dtype=torch.uint8, device="cuda") for _ in range(2)]
+    fls = [d_index(np.full(2, 0x77777777)) for _ in range(2)]
+    out2 = torch.full((one_bytes,), 0x5A, dtype=torch.uint8, device="cuda")
+    st2 = torch.full((one_cnt,), 77, dtype=torch.uint8, device="cuda")
+    src = torch.from_numpy(data).cuda()
+    st3 = torch.full((e3["st"].size,), 77, dtype=torch.uint8, device="cuda")
+    wr = torch.full((1,), -1, dtype=torch.int64, device="cuda")
+    cn = [torch.full((8,), -1, dtype=torch.int64, device="cuda") for _ in range(4)]
+    s = torch.cuda.Stream()
+    torch.cuda.synchronize()  # the buffers were filled on the default stream
+    fi.eng.read_files(g.image, files, ranges, outs[0], sts[0], fls[0], counts=cn[0], stream=s)
+    fi.eng.read_file(g.image, f, *one, out2, st2, counts=cn[1], stream=s)
+    fi.eng.write_file(src, g.image, f, w_off, w_bytes, st3, written=wr, counts=cn[2], stream=s)
+    fi.eng.read_files(g.image, files, ranges, outs[1], sts[1], fls[1], counts=cn[3], stream=s)
+    torch.cuda.synchronize()
+    for k, e in ((0, e1), (1, e4)):
+        assert np.array_equal(host(outs[k]), e[0]) and np.array_equal(host(sts[k]), e[1]), k
+        assert np.array_equal(host(fls[k]).view(np.uint32), e[2]) and FileCounts(*cn[3 * k].tolist()) == e[3], k
+    assert np.array_equal(host(out2), e2_out) and np.array_equal(host(st2), e2_st) and FileCounts(*cn[1].tolist()) == e2_counts
+    assert np.array_equal(host(st3), e3["st"]) and int(wr[0]) == w_bytes and FileCounts(*cn[2].tolist()) == e3["counts"]
+    assert np.array_equal(g.result(), e4[4]) and np.array_equal(e4[4], e3["image"])
+
+
 def test_batch_built_image_equals_per_block_writes(oracle):
     """The images above come from the oracle's batch encode; the reference writes an index block's entries at
     {block, 0} of a zeroed block and a data block whole.  Both give the same bytes."""
