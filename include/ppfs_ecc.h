@@ -645,6 +645,81 @@ int ppfs_ecc_write_files_host(ppfs_ecc_ctx* ctx, const uint8_t* in, size_t in_by
     uint64_t* written, ppfs_ecc_file_counts* counts, int write_back);
 
 /*
+ * Read inodes from the inode table: a batch of inode numbers per call.  Every file
+ * call above starts from a ppfs_ecc_file record; InodeManager::get (lib/inode_manager/src/inode_manager.cpp:
+ * 127-138) fetches it with one Bitmap::getBit -- a one-byte readBlock of the inode bitmap (bitmap.cpp:8-25,
+ * 87-101) -- and _readInode (:56-89), one or more readBlocks of the inode table.  ppfs_ecc_read_inodes_* is that
+ * for n inode numbers of one inode table: records, metadata and statuses.  Engine extension; read-only.
+ *
+ * On disk.  The packed Inode (inode.hpp:18-41) is 81 bytes: time_creation [0, 8), time_modified [8, 16),
+ * direct[12] [16, 64), indirect 64, doubly_indirect 68, trebly_indirect 72, file_size 76, type 80 (0 file,
+ * 1 directory); ppfs_ecc_file is bytes [16, 80) of it.  Inode i lies at table byte 81 i (_getInodeLocation,
+ * :11-18): block table_block + 81 i / ds at offset 81 i % ds, in 64-bit arithmetic, and is read as a plain cut
+ * at block boundaries (readBlock clamps to ds - offset, rs_block_device.cpp:28-48): pieces(i) = (81 i % ds + 80)
+ * / ds + 1 pieces, at most K(ds) = 2 + 79 / ds (2 for ds >= 80, 4 at ds = 31, 81 at ds = 1).  Bit i of the inode
+ * bitmap is byte i / 8 of the bitmap's payload stream under mask 0x80 >> (i % 8): block bitmap_block + (i / 8) /
+ * ds, offset (i / 8) % ds.  In this bitmap 1 means FREE (InodeManager::create / remove / format): get returns
+ * InodeManager_NotFound for a set bit, and getBit returns Bitmap_IndexOutOfRange for i >= total_inodes.
+ *
+ * ppfs_ecc_inode_span: block, offset and piece count of inode `ino`; -EINVAL for a null ctx or table, for
+ * ino >= total_inodes and for a first block at or past 2^32 - 1.  Outputs may be NULL.  No GPU.
+ *
+ * Inode numbers.  Number j is the little-endian uint32 at byte j * ino_stride of `ino`, at any alignment;
+ * ino_stride >= 4 (-EINVAL below): 4 for a packed array, 128 for DirectoryEntry records (directory.hpp:8-12) as a
+ * ppfs_ecc_read_file(s)_* call left them in its out buffer.
+ * Outputs, each may be NULL.  files (4-byte aligned): n ppfs_ecc_file records, which ppfs_ecc_read_files_* takes
+ * as its `files` argument once they are in host memory; meta (8-byte aligned): n ppfs_ecc_inode_meta; status: n
+ * bytes; piece_status: n * (1 + K(ds)) bytes, per inode slot 0 the bitmap byte's read status and slots 1 ..
+ * pieces(i) the table pieces' read statuses, 255 in every slot that is unused or was never read; counts (8-byte
+ * aligned): the n statuses tallied.  The status arrays may have any alignment.
+ * Status of inode j, in the loop's order of evaluation:
+ *   1. ino >= total_inodes: 9, whether or not check_bitmap is set;
+ *   2. with check_bitmap: a bitmap read status of 5 or 9 as it stands; a set bit: PPFS_ECC_NOT_ALLOCATED (255);
+ *   3. the first piece in order whose status is 5 or 9: that status (a table block at or past image_blocks is 9);
+ *   4. otherwise 1 if the bitmap byte or any piece reported 1, else 0.
+ * For a status other than 0 or 1 the files and meta records are zero-filled.
+ * Blocks touched: exactly those the per-inode loop would touch.  A bitmap block only if an in-range number of the
+ * batch has its bit there; a table block only if an inode that passed steps 1-2 has bytes there (all pieces of
+ * such an inode are read, also after a failing one); the pieces of every other inode are invalid extents (block
+ * 0xFFFFFFFF) and touch nothing.  write_back applies to both regions, as in ppfs_ecc_read_extents_*.
+ * Repeats are the norm: three inodes share a table block at ds = 249, eight or more a bitmap byte, and a number
+ * may appear twice.  The repeated-index rules of ppfs_ecc_decode_list_* hold: every copy gets the same bytes.  On
+ * the device with write_back, the inodes that share a corrected block each report 1 or 0, at least one reports 1,
+ * and the image ends corrected; without write_back every sharer reports 1.  (A sharer whose status another rule
+ * decides -- a free inode that shares the bitmap block -- reports that status; piece_status shows what its read saw.)  The host form equals the loop: the
+ * first toucher reports 1, later ones read the written-back block.
+ * Errors: -EINVAL, before anything touches the GPU, for a null ctx, table, image or ino (n > 0), a misaligned
+ * files, meta or counts, a stride below 4, a payload of 0 or above 65,535 bytes.  n == 0 returns 0 with zeroed
+ * counts.  A capturing stream gets PPFS_ECC_ENOTSUP.  Shortened RS is decoded as by a list decode with no spill.
+ * Device form: never synchronises `stream`, reads nothing back, allocates and frees nothing on the caller's
+ * stream; its scratch is the context's scrub scratch.  In pieces of PPFS_ECC_INODE_PIECE inodes (2 / K(ds) of
+ * that where K > 2): bitmap extents kernel, ppfs_ecc_read_extents_device, table extents kernel,
+ * ppfs_ecc_read_extents_device, merge kernel.  `table` is a HOST pointer in both forms.
+ * Host form: the same plan on the CPU around two ppfs_ecc_read_extents_host calls and a CPU tally.
+ */
+#define PPFS_ECC_INODE_PIECE 16384
+
+typedef struct ppfs_ecc_inode_table { /* 16 bytes: the SuperBlock fields InodeManager reads */
+    uint32_t table_block, bitmap_block, total_inodes, check_bitmap;
+} ppfs_ecc_inode_table;
+typedef struct ppfs_ecc_inode_meta { /* 24 bytes */
+    uint64_t time_creation, time_modified;
+    uint8_t type, pad[7];
+} ppfs_ecc_inode_meta;
+typedef struct ppfs_ecc_inode_counts { /* 64 bytes, overwritten by each call */
+    uint64_t ok, corrected, failed, out_of_range, not_allocated, reserved[3];
+} ppfs_ecc_inode_counts;
+
+int ppfs_ecc_inode_span(const ppfs_ecc_ctx* ctx, const ppfs_ecc_inode_table* table, uint32_t ino, uint32_t* block,
+    uint32_t* offset, uint32_t* pieces);
+int ppfs_ecc_read_inodes_device(ppfs_ecc_ctx* ctx, uint8_t* d_image, size_t image_blocks, const ppfs_ecc_inode_table* table,
+    const void* d_ino, size_t ino_stride, size_t n, ppfs_ecc_file* d_files, ppfs_ecc_inode_meta* d_meta, uint8_t* d_status,
+    uint8_t* d_piece_status, ppfs_ecc_inode_counts* d_counts, int write_back, void* stream);
+int ppfs_ecc_read_inodes_host(ppfs_ecc_ctx* ctx, uint8_t* image, size_t image_blocks, const ppfs_ecc_inode_table* table,
+    const void* ino, size_t ino_stride, size_t n, ppfs_ecc_file* files, ppfs_ecc_inode_meta* meta, uint8_t* status,
+    uint8_t* piece_status, ppfs_ecc_inode_counts* counts, int write_back);
+
+/*
  * 2-of-3 bitwise majority of nrec replicated records of rec_bytes each, replacing
  * SuperBlockManager::_performBitVoting (lib/super_block_manager/src/super_block_manager.cpp:133-165):
  *   out[i] = majority(a[i], b[i], c[i]) bit by bit;

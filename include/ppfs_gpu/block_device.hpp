@@ -856,6 +856,99 @@ public:
             read_one(reads[i], readFile(reads[i].file, reads[i].offset, reads[i].bytes_to_read, reads[i].out, &reads[i].delivered));
     }
 
+    // Inode extension (ppfs_ecc.h ppfs_ecc_read_inodes_*): n inode numbers of one inode table in one call -- the
+    // children of a directory.  By definition the per-inode loop, InodeManager::get (inode_manager.cpp:127-138):
+    // Bitmap::getBit (bitmap.cpp:8-25, 87-101), a one-byte readBlock of the inode bitmap, in which a SET bit means
+    // free (InodeManager_NotFound); then _readInode (:56-89), the 81 packed bytes cut at block boundaries by a
+    // clamping readBlock.  The first error ends that inode.  table.check_bitmap == 0 skips the bit's read, not the
+    // range check.  The codecs read the whole batch in one engine call.
+    using InodeTable = ppfs_ecc_inode_table;
+#pragma pack(push, 1)
+    struct PackedInode { // inode.hpp:18-41
+        uint64_t time_creation, time_modified;
+        ppfs_ecc_file file; // direct[12], indirect, doubly_indirect, trebly_indirect, file_size
+        uint8_t type;       // 0 file, 1 directory
+    };
+#pragma pack(pop)
+    static_assert(sizeof(PackedInode) == 81, "the packed Inode");
+    struct InodeRead {
+        bool ok;
+        FsError error;
+        PackedInode inode; // zero unless ok
+    };
+    expected<bool> inodeBit(const InodeTable& table, uint32_t bit_index)
+    {
+        if (bit_index >= table.total_inodes)
+            return unexpected(FsError::Bitmap_IndexOutOfRange);
+        const size_t ds = dataSize(), byte = bit_index / 8;
+        uint8_t b = 0;
+        static_vector<uint8_t> v(&b, 1, 0);
+        auto r = readBlock(DataLocation((int)(table.bitmap_block + byte / ds), byte % ds), 1, v);
+        if (!r)
+            return unexpected(r.error());
+        return ((b >> (7 - bit_index % 8)) & 1) > 0;
+    }
+    expected<void> readInode(const InodeTable& table, uint32_t index, PackedInode& inode)
+    {
+        const size_t ds = dataSize(), size = sizeof(PackedInode);
+        uint8_t* bytes = reinterpret_cast<uint8_t*>(&inode);
+        size_t bytes_read = 0;
+        DataLocation start((int)(table.table_block + (uint64_t)index * size / ds), (size_t)((uint64_t)index * size % ds));
+        if (ds - start.offset < size) { // does not fit in one block: the unaligned part first
+            static_vector<uint8_t> v(bytes, size, 0);
+            auto r = readBlock(start, size, v);
+            if (!r)
+                return unexpected(r.error());
+            start.offset = 0;
+            start.block_index++;
+            bytes_read += v.size();
+        }
+        while (bytes_read < size) {
+            const size_t bytes_left = size - bytes_read;
+            static_vector<uint8_t> v(bytes + bytes_read, bytes_left, 0);
+            auto r = readBlock(start, bytes_left, v);
+            if (!r)
+                return unexpected(r.error());
+            bytes_read += v.size();
+            start.block_index++;
+        }
+        return {};
+    }
+    virtual void readInodes(const InodeTable& table, const uint32_t* numbers, size_t n, InodeRead* out)
+    {
+        for (size_t j = 0; j < n; ++j) {
+            InodeRead& r = out[j];
+            r = InodeRead {};
+            auto fail = [&](FsError e) { r.error = e; };
+            if (dataSize() == 0) {
+                fail(FsError::Disk_InvalidRequest);
+                continue;
+            }
+            if (table.check_bitmap) {
+                auto is_free = inodeBit(table, numbers[j]);
+                if (!is_free) {
+                    fail(is_free.error());
+                    continue;
+                }
+                if (*is_free) {
+                    fail(FsError::InodeManager_NotFound);
+                    continue;
+                }
+            } else if (numbers[j] >= table.total_inodes) {
+                fail(FsError::Bitmap_IndexOutOfRange);
+                continue;
+            }
+            PackedInode inode {};
+            auto got = readInode(table, numbers[j], inode);
+            if (!got) {
+                fail(got.error());
+                continue;
+            }
+            r.ok = true;
+            r.inode = inode;
+        }
+    }
+
     // Write extension (ppfs_ecc.h ppfs_ecc_write_file_* / ppfs_ecc_write_files_*): the in-place case of
     // FileIO::writeFile (file_io.cpp:46-104).  The range must lie inside the file as the inode describes it --
     // offset + n <= file_size, else FileIO_OutOfBounds as readFile reports a range past the end; nothing is
@@ -1747,6 +1840,74 @@ public:
                 }
             }
             read_one(r, got);
+        }
+    }
+
+    // readInodes as ONE ppfs_ecc_read_inodes_host on a mapped disk image.  Records and errors equal the loop's, and
+    // so does the log, which piece_status makes possible: inodes in batch order, the bitmap block then the pieces up
+    // to the first failing one, each block that some read of the call corrected logged where the loop first touches
+    // it.  The pieces behind an inode's failing piece, which the loop does not read, have been read (and corrected)
+    // as well: the one deviation.  Elsewhere, and for a shortened RS code, the per-inode loop.
+    void readInodes(const InodeTable& table, const uint32_t* numbers, size_t n, InodeRead* out) override
+    {
+        uint8_t* img = _disk.mapped();
+        if (!img || has_spill() || !_raw || !_ds || _ds > 0xFFFFu || !n)
+            return IBlockDevice::readInodes(table, numbers, n, out);
+        const size_t K = 2 + 79 / _ds, W = 1 + K;
+        std::vector<ppfs_ecc_file> files(n);
+        std::vector<ppfs_ecc_inode_meta> meta(n);
+        std::vector<uint8_t> status(n), pieces(n * W);
+        const int wb = (_type == PPFS_ECC_REED_SOLOMON || _type == PPFS_ECC_HAMMING) ? 1 : 0;
+        if (!EccEngine::ok(ppfs_ecc_read_inodes_host(_eng.ctx(), img, _disk.size() / _raw, &table, numbers, 4, n, files.data(),
+                               meta.data(), status.data(), pieces.data(), nullptr, wb),
+                "read inodes")) {
+            for (size_t j = 0; j < n; ++j) {
+                out[j] = InodeRead {};
+                out[j].error = FsError::Disk_IOError;
+            }
+            return;
+        }
+        // the reads the loop makes for inode j, in its order: fn(block, status) until it returns false
+        auto reads_of = [&](size_t j, auto fn) {
+            const uint8_t* ps = pieces.data() + j * W;
+            const uint64_t i = numbers[j];
+            if (ps[0] != 255 && !fn((uint64_t)table.bitmap_block + (i / 8) / _ds, ps[0]))
+                return;
+            for (size_t k = 0; k < K && ps[1 + k] != 255; ++k)
+                if (!fn((uint64_t)table.table_block + 81 * i / _ds + k, ps[1 + k]))
+                    return;
+        };
+        std::unordered_set<uint64_t> corrected, logged;
+        for (size_t j = 0; j < n; ++j)
+            reads_of(j, [&](uint64_t b, uint8_t st) {
+                if (st == PPFS_ECC_CORRECTED)
+                    corrected.insert(b);
+                return true;
+            });
+        for (size_t j = 0; j < n; ++j) {
+            reads_of(j, [&](uint64_t b, uint8_t st) {
+                if (st == PPFS_ECC_CORRECTION_ERROR || st == PPFS_ECC_OUT_OF_BOUNDS)
+                    return false;
+                if (corrected.count(b) && logged.insert(b).second)
+                    log((block_index_t)b);
+                return true;
+            });
+            InodeRead& r = out[j];
+            r = InodeRead {};
+            const uint8_t st = status[j];
+            if (st == PPFS_ECC_OK || st == PPFS_ECC_CORRECTED) {
+                r.ok = true;
+                r.inode.time_creation = meta[j].time_creation;
+                r.inode.time_modified = meta[j].time_modified;
+                r.inode.file = files[j];
+                r.inode.type = meta[j].type;
+            } else if (numbers[j] >= table.total_inodes) {
+                r.error = FsError::Bitmap_IndexOutOfRange;
+            } else if (st == PPFS_ECC_NOT_ALLOCATED) {
+                r.error = FsError::InodeManager_NotFound;
+            } else {
+                r.error = (FsError)st; // 5 and 9 are BlockDevice_CorrectionError and Disk_OutOfBounds
+            }
         }
     }
 

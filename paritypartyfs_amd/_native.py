@@ -72,6 +72,9 @@ EXPORTED_SYMBOLS = (
     "ppfs_ecc_write_file_host",
     "ppfs_ecc_write_files_device",
     "ppfs_ecc_write_files_host",
+    "ppfs_ecc_inode_span",
+    "ppfs_ecc_read_inodes_device",
+    "ppfs_ecc_read_inodes_host",
     "ppfs_vote3_device",
     "ppfs_vote3_host",
     "ppfs_copy_device",
@@ -108,6 +111,12 @@ FILES_SLOT_DTYPE = np.dtype([("first_block", "<u8"), ("blocks", "<u8"), ("bytes"
                              ("out_pos", "<u8"), ("tree_pos", "<u8", (3,)), ("tree_n", "<u8", (3,))])
 FILES_TOTALS_DTYPE = np.dtype([("blocks", "<u8"), ("bytes", "<u8"), ("tree_level", "<u8", (3,)), ("tree_blocks", "<u8")])
 
+# ppfs_ecc_inode_table: the SuperBlock fields InodeManager reads (16 bytes), and ppfs_ecc_inode_meta: what an Inode
+# holds besides its ppfs_ecc_file record (24 bytes)
+INODE_TABLE_DTYPE = np.dtype([("table_block", "<u4"), ("bitmap_block", "<u4"), ("total_inodes", "<u4"), ("check_bitmap", "<u4")])
+INODE_META_DTYPE = np.dtype([("time_creation", "<u8"), ("time_modified", "<u8"), ("type", "u1"), ("pad", "u1", (7,))])
+INODE_PIECE = 16384  # PPFS_ECC_INODE_PIECE: inodes per piece of a device call
+
 
 class EccParams(ctypes.Structure):
     _fields_ = [
@@ -129,6 +138,12 @@ class FileCounts(ctypes.Structure):
     """ppfs_ecc_file_counts: what a file walk / file read found (64 bytes, overwritten by each call)."""
     _fields_ = [(n, c_uint64) for n in ("ok", "corrected", "failed", "out_of_range", "index_ok", "index_corrected",
                                         "index_failed", "index_out_of_range")]
+
+
+class InodeCounts(ctypes.Structure):
+    """ppfs_ecc_inode_counts: the statuses of a batch of inode reads (64 bytes, overwritten by each call)."""
+    _fields_ = [(n, c_uint64) for n in ("ok", "corrected", "failed", "out_of_range", "not_allocated", "reserved0",
+                                        "reserved1", "reserved2")]
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -300,6 +315,16 @@ def lib() -> ctypes.CDLL:
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]
     L.ppfs_ecc_write_files_host.restype = c_int
     L.ppfs_ecc_write_files_host.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_int]
+    # inode reads: span (ctx, table, ino, block, offset, pieces); read (ctx, image, image_blocks, table, ino, ino_stride,
+    # n, files, meta, status, piece_status, counts, write_back[, stream])
+    L.ppfs_ecc_inode_span.restype = c_int
+    L.ppfs_ecc_inode_span.argtypes = [c_void_p, c_void_p, c_uint32, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32)]
+    L.ppfs_ecc_read_inodes_device.restype = c_int
+    L.ppfs_ecc_read_inodes_device.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]
+    L.ppfs_ecc_read_inodes_host.restype = c_int
+    L.ppfs_ecc_read_inodes_host.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p,
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_int]
     L.ppfs_vote3_device.restype = c_int
     L.ppfs_vote3_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]

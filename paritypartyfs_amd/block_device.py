@@ -26,8 +26,8 @@ from typing import Generic, List, Optional, Tuple, TypeVar
 
 import numpy as np
 
-from ._native import (ECC_CRC, ECC_HAMMING, ECC_NONE, ECC_PARITY, ECC_REED_SOLOMON, EXTENT_DTYPE, FILE_DTYPE, STATUS_CORRECTED,
-                      STATUS_CORRECTION_ERROR, STATUS_NOT_ALLOCATED, STATUS_OUT_OF_BOUNDS)
+from ._native import (ECC_CRC, ECC_HAMMING, ECC_NONE, ECC_PARITY, ECC_REED_SOLOMON, EXTENT_DTYPE, FILE_DTYPE, INODE_META_DTYPE, INODE_TABLE_DTYPE, STATUS_CORRECTED,
+                      STATUS_CORRECTION_ERROR, STATUS_NOT_ALLOCATED, STATUS_OK, STATUS_OUT_OF_BOUNDS)
 from .ecc import EccEngine, ScrubCounts
 
 MAX_BLOCK_SIZE = 4096  # iblock_device.hpp:3
@@ -56,7 +56,13 @@ class FsError(enum.IntEnum):  # lib/common/include/ppfs/common/types.hpp:11-80 (
     Disk_InvalidRequest = 10
     Disk_IOError = 11
     FileIO_OutOfBounds = 12
+    InodeManager_NotFound = 26
 
+
+# the packed Inode (inode.hpp:18-41), 81 bytes: what IBlockDevice.read_inodes delivers per inode
+INODE_DTYPE = np.dtype([("time_creation", "<u8"), ("time_modified", "<u8"), ("direct", "<u4", (12,)), ("indirect", "<u4"),
+                        ("doubly_indirect", "<u4"), ("trebly_indirect", "<u4"), ("file_size", "<u4"), ("type", "u1")])
+assert INODE_DTYPE.itemsize == 81
 
 T = TypeVar("T")
 
@@ -440,6 +446,65 @@ class IBlockDevice:
         batch order."""
         files = np.asarray(files).reshape(-1)
         return [self.write_file(files[f:f + 1], int(off), bytes(datas[f])[:max(int(n), 0)]) for f, (off, n) in enumerate(ranges)]
+
+    # read inodes from the inode table (include/ppfs_ecc.h ppfs_ecc_read_inodes_*): `table` is one record of
+    # INODE_TABLE_DTYPE, `numbers` the inode numbers.  The per-inode loop is the definition -- InodeManager::get
+    # (inode_manager.cpp:127-138): Bitmap::getBit (bitmap.cpp:8-25, 87-101), a one-byte readBlock, then _readInode
+    # (:56-89), the 81 bytes cut at block boundaries by a clamping readBlock; the first error ends that inode.  The
+    # codecs override it with one engine call.
+    def _inode_get_bit(self, bitmap_block: int, total: int, bit_index: int) -> Expected[bool]:
+        if bit_index >= total:
+            return Expected.unexpected(FsError.Bitmap_IndexOutOfRange)
+        ds = self.dataSize()
+        byte = bit_index // 8
+        r = self.readBlock(DataLocation(bitmap_block + byte // ds, byte % ds), 1)
+        if not r:
+            return Expected.unexpected(r.error())
+        return Expected(((r.value()[0] >> (7 - bit_index % 8)) & 1) > 0)
+
+    def _inode_read(self, table_block: int, index: int) -> Expected[bytes]:
+        size, ds = INODE_DTYPE.itemsize, self.dataSize()
+        inode = bytearray()
+        start = DataLocation(table_block + index * size // ds, index * size % ds)
+        if ds - start.offset < size:  # does not fit in one block: the unaligned part first
+            r = self.readBlock(start, size)
+            if not r:
+                return Expected.unexpected(r.error())
+            start = DataLocation(start.block_index + 1, 0)
+            inode += r.value()
+        while len(inode) < size:
+            r = self.readBlock(start, size - len(inode))
+            if not r:
+                return Expected.unexpected(r.error())
+            inode += r.value()
+            start = DataLocation(start.block_index + 1, start.offset)
+        return Expected(bytes(inode))
+
+    def read_inodes(self, table, numbers) -> List[Tuple[Optional[np.void], Optional[FsError]]]:
+        """InodeManager::get per inode number, in batch order: (the INODE_DTYPE record, None) or (None, the error).
+        A set bit of the inode bitmap means free: InodeManager_NotFound.  table["check_bitmap"] == 0 skips the bit's
+        read, not the range check."""
+        t = np.asarray(table).reshape(-1)[0]
+        table_block, bitmap_block, total = int(t["table_block"]), int(t["bitmap_block"]), int(t["total_inodes"])
+        if self.dataSize() == 0:
+            raise ValueError("read_inodes: the codec has no payload")
+        out = []
+        for i in (int(x) for x in np.asarray(numbers).reshape(-1)):
+            if int(t["check_bitmap"]):
+                free = self._inode_get_bit(bitmap_block, total, i)
+                if not free:
+                    out.append((None, free.error()))
+                    continue
+                if free.value():
+                    out.append((None, FsError.InodeManager_NotFound))
+                    continue
+            elif i >= total:
+                out.append((None, FsError.Bitmap_IndexOutOfRange))
+                continue
+            r = self._inode_read(table_block, i)
+            out.append((np.frombuffer(r.value(), dtype=INODE_DTYPE)[0], None) if r else (None, r.error()))
+        return out
+
 
 
 def file_path_of(j: int, ipb: int):
@@ -984,6 +1049,61 @@ class _EngineDevice(IBlockDevice):
             else:
                 results[f] = (out[pos:pos + n].tobytes(), None)
         return results
+
+    def read_inodes(self, table, numbers) -> List[Tuple[Optional[np.void], Optional[FsError]]]:
+        """IBlockDevice.read_inodes as ONE engine call on the disk image (EccEngine.read_inodes_host).  Records and
+        errors equal the loop's.  The correction log equals it too: inodes in batch order, the bitmap block then the
+        pieces up to the first failing one, each block that some read of the call corrected logged where the loop
+        first touches it.  The pieces behind an inode's failing piece, which the loop does not read, have been read
+        (and corrected) as well."""
+        image = self._mapped_image()
+        nums = np.ascontiguousarray(np.asarray(numbers).reshape(-1), dtype=np.uint32)
+        if image is None or self._ds == 0 or self._ds > 0xFFFF or nums.size == 0:
+            return super().read_inodes(table, numbers)
+        eng, ds = self._engine, self._ds
+        t = np.ascontiguousarray(np.asarray(table).reshape(-1)[:1], dtype=INODE_TABLE_DTYPE)
+        table_block, bitmap_block, total = int(t["table_block"][0]), int(t["bitmap_block"][0]), int(t["total_inodes"][0])
+        n, W = int(nums.size), 1 + eng.inode_max_pieces
+        files, meta = np.zeros(n, dtype=FILE_DTYPE), np.zeros(n, dtype=INODE_META_DTYPE)
+        status, pieces = np.zeros(n, dtype=np.uint8), np.zeros(n * W, dtype=np.uint8)
+        wb = eng.ecc_type in (ECC_REED_SOLOMON, ECC_HAMMING)
+        eng.read_inodes_host(image, t, nums, files=files, meta=meta, status=status, piece_status=pieces, write_back=wb)
+        pieces = pieces.reshape(n, W)
+        # the blocks some read of the call corrected, then the loop's order of touching them
+        reads = []  # per inode: (block, status) of the reads the loop makes, in its order
+        for j, i in enumerate(int(x) for x in nums):
+            mine = []
+            if pieces[j, 0] != 255:
+                mine.append((bitmap_block + (i // 8) // ds, int(pieces[j, 0])))
+            for k in range(W - 1):
+                if pieces[j, 1 + k] == 255:
+                    break
+                mine.append((table_block + 81 * i // ds + k, int(pieces[j, 1 + k])))
+            reads.append(mine)
+        corrected = {b for mine in reads for b, st in mine if st == STATUS_CORRECTED}
+        logged = set()
+        out = []
+        for j, i in enumerate(int(x) for x in nums):
+            for b, st in reads[j]:
+                if st in (STATUS_CORRECTION_ERROR, STATUS_OUT_OF_BOUNDS):
+                    break
+                if b in corrected and b not in logged:
+                    logged.add(b)
+                    self._log(b)
+            st = int(status[j])
+            if st in (STATUS_OK, STATUS_CORRECTED):
+                rec = np.zeros(1, dtype=INODE_DTYPE)
+                rec["time_creation"], rec["time_modified"], rec["type"] = meta["time_creation"][j], meta["time_modified"][j], meta["type"][j]
+                for name in FILE_DTYPE.names:
+                    rec[name] = files[name][j]
+                out.append((rec[0], None))
+            elif i >= total:
+                out.append((None, FsError.Bitmap_IndexOutOfRange))
+            elif st == STATUS_NOT_ALLOCATED:
+                out.append((None, FsError.InodeManager_NotFound))
+            else:
+                out.append((None, FsError(st)))
+        return out
 
     def write_file(self, file, offset: int, data) -> Tuple[int, Optional[FsError]]:
         """IBlockDevice.write_file as write_files of one file."""

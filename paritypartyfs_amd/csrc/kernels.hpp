@@ -1,8 +1,9 @@
 // kernels.hpp -- the host-callable launchers of the kernel translation units, declared once:
 // rs_kernels.hip (Reed-Solomon and its servers), bit_kernels.hip (CRC, Hamming, parity and the bit
 // server) vote.hip (vote, copy, gather, patch list, inject, flag, block lists), alloc_scan.hip (bitmap
-// expansion, scrub tally) and files_walk.hip (the file walk's expansion, extents and merges).  The
-// three table-sizing functions are in host_tables.hpp, beside the builders that use them.
+// expansion, scrub tally), files_walk.hip (the file walk's expansion, extents and merges) and
+// inode_walk.hip (the inode reads' extents and merge).  The three table-sizing functions are in
+// host_tables.hpp, beside the builders that use them.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -127,4 +128,20 @@ hipError_t ppfs_files_written_init_launch(const ppfs_files_owner* owner, unsigne
 hipError_t ppfs_files_write_merge_launch(const ppfs_files_owner* owner, const uint8_t* path, const uint8_t* wst, uint64_t e0,
     uint64_t n, uint8_t* status_out, uint64_t ds, uint32_t* flags, unsigned long long* written, unsigned long long* counts,
     hipStream_t s);
+// the inode reads (inode_path.cpp; inode_walk.hip, arithmetic in inode_plan.hpp) over one piece of n inodes, at most
+// inodeplan::piece_inodes(ds); K = inodeplan::max_pieces(ds); table: a HOST pointer, travels by value.
+// bitmap_extents: number j = the little-endian uint32 at src + j * stride (any alignment, stride >= 4) -> ino[j]
+// (4-byte aligned) and ext[j] (8-byte aligned), the one-byte extent of its bitmap byte with pos = j, invalid when the
+// number is out of range or the bitmap is not checked.
+// table_extents: bm[j] / bst[j], the bitmap bytes and their read statuses -> ext[j * K + k], the pieces of the inodes
+// whose table is read with pos = 81 j + the bytes before piece k, every other one invalid.
+// merge: rows (81 n bytes) and pst[j * K + k], the pieces' read statuses -> files, meta, status, piece_status
+// (n * (1 + K) bytes) and the counts (five categories), each may be null.
+hipError_t ppfs_inode_bitmap_extents_launch(const void* src, uint64_t stride, uint64_t n, const ppfs_ecc_inode_table* table,
+    uint64_t ds, uint32_t* ino, ppfs_ecc_extent* ext, hipStream_t s);
+hipError_t ppfs_inode_table_extents_launch(const uint32_t* ino, const uint8_t* bm, const uint8_t* bst, uint64_t n,
+    const ppfs_ecc_inode_table* table, uint64_t ds, ppfs_ecc_extent* ext, hipStream_t s);
+hipError_t ppfs_inode_merge_launch(const uint32_t* ino, const uint8_t* bm, const uint8_t* bst, const uint8_t* rows,
+    const uint8_t* pst, uint64_t n, const ppfs_ecc_inode_table* table, uint64_t ds, ppfs_ecc_file* files, ppfs_ecc_inode_meta* meta,
+    uint8_t* status, uint8_t* piece_status, unsigned long long* counts, hipStream_t s);
 }

@@ -696,6 +696,97 @@ class EccEngine:
             self._u32_ptr(file_flags), written.ctypes.data, byref(rec), int(bool(write_back))))
         return FileCounts(*[int(getattr(rec, k)) for k in FILE_COUNT_FIELDS]), written[:n]
 
+    # ---------------- read inodes from the inode table (ppfs_ecc_inode_span, ppfs_ecc_read_inodes_*) ----------------
+    # `table` is one INODE_TABLE_DTYPE record in host memory (table_block, bitmap_block, total_inodes, check_bitmap).
+    # `numbers` names the inodes: a packed array of 32-bit numbers (device: a CUDA int32 tensor, read as unsigned; host:
+    # a numpy uint32 array), or a uint8 buffer with `n` and `stride`, number j being the little-endian uint32 at byte
+    # j * stride -- stride 128 over the payload of a directory as read_file(s) left it.  Outputs, each optional: files
+    # (64 n bytes: FILE_DTYPE records), meta (24 n bytes: INODE_META_DTYPE), status (n), piece_status
+    # (n * (1 + inode_max_pieces)), counts.
+    @staticmethod
+    def _inode_table(table) -> np.ndarray:
+        t = np.ascontiguousarray(table)
+        if t.dtype != _native.INODE_TABLE_DTYPE or t.size != 1:
+            raise ValueError("table: one record of INODE_TABLE_DTYPE")
+        return t.reshape(1)
+
+    @property
+    def inode_max_pieces(self) -> int:
+        """K(ds): the most table pieces one inode has, 2 + 79 // data_size."""
+        return 2 + 79 // self.data_size
+
+    def inode_span(self, table, ino: int):
+        """(block, offset, pieces) of inode `ino` in the inode table (ppfs_ecc_inode_span).  No GPU work."""
+        t = self._inode_table(table)
+        a, b, c = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        if not 0 <= int(ino) <= 0xFFFFFFFF:
+            raise ValueError("ino: an unsigned 32-bit number")
+        check(lib().ppfs_ecc_inode_span(self._h, t.ctypes.data, int(ino), byref(a), byref(b), byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
+    def _inodes_check(self, kind, image, table, numbers, n, stride, files, meta, status, piece_status):
+        t = self._inode_table(table)
+        if image is None:
+            raise ValueError("image: required")
+        if numbers is None:
+            raise ValueError("numbers: required")
+        _need("image", image, 0, kind)
+        _ptr(image)
+        packed = (numbers.dtype == np.uint32) if isinstance(numbers, np.ndarray) else (numbers.element_size() == 4)
+        if kind == "device":
+            if isinstance(numbers, np.ndarray) or not getattr(numbers, "is_cuda", False) or not numbers.is_contiguous():
+                raise ValueError("numbers: a contiguous CUDA tensor (int32 numbers, or uint8 bytes with n and stride)")
+            nbytes, addr = int(numbers.numel()) * numbers.element_size(), numbers.data_ptr()
+        else:
+            if not isinstance(numbers, np.ndarray) or not numbers.flags["C_CONTIGUOUS"]:
+                raise ValueError("numbers: a C-contiguous numpy array (uint32 numbers, or uint8 bytes with n and stride)")
+            nbytes, addr = int(numbers.nbytes), numbers.ctypes.data
+        if packed:
+            if n is None:
+                n = nbytes // 4
+            stride = 4 if stride is None else stride
+        elif n is None or stride is None:
+            raise ValueError("numbers: a byte buffer needs n and stride")
+        n, stride = int(n), int(stride)
+        if n < 0 or stride < 4:
+            raise ValueError("n >= 0 and stride >= 4")
+        if n and nbytes < (n - 1) * stride + 4:
+            raise ValueError(f"numbers: {nbytes} bytes < {(n - 1) * stride + 4} needed")
+        for name, x, per in (("files", files, 64), ("meta", meta, 24), ("status", status, 1),
+                             ("piece_status", piece_status, 1 + self.inode_max_pieces)):
+            if x is None:
+                continue
+            if kind == "device":
+                if isinstance(x, np.ndarray) or not getattr(x, "is_cuda", False) or not x.is_contiguous() \
+                        or x.numel() * x.element_size() < n * per:
+                    raise ValueError(f"{name}: a contiguous CUDA tensor of >= {n * per} bytes")
+            elif not isinstance(x, np.ndarray) or not x.flags["C_CONTIGUOUS"] or x.nbytes < n * per:
+                raise ValueError(f"{name}: a C-contiguous numpy array of >= {n * per} bytes")
+        return t, _size(image) // self.raw_block_size, addr if n else None, stride, n
+
+    def read_inodes(self, image, table, numbers, n=None, stride=None, files=None, meta=None, status=None, piece_status=None,
+                    counts=None, write_back: bool = True, stream=None):
+        """Device read of a batch of inodes (ppfs_ecc_read_inodes_device).  counts: None, True (a fresh CUDA int64
+        tensor of the eight words of INODE_COUNT_FIELDS) or such a tensor.  Never synchronises."""
+        t, blocks, addr, stride, n = self._inodes_check("device", image, table, numbers, n, stride, files, meta, status,
+                                                        piece_status)
+        d_counts = self._device_counts(counts)
+        check(lib().ppfs_ecc_read_inodes_device(
+            self._h, _ptr(image), blocks, t.ctypes.data, addr, stride, n, self._u32_ptr(files), self._u32_ptr(meta),
+            self._u32_ptr(status), self._u32_ptr(piece_status), None if d_counts is None else d_counts.data_ptr(),
+            int(bool(write_back)), _stream_handle(stream)))
+        return d_counts
+
+    def read_inodes_host(self, image: np.ndarray, table, numbers, n=None, stride=None, files=None, meta=None, status=None,
+                         piece_status=None, write_back: bool = True) -> "InodeCounts":
+        t, blocks, addr, stride, n = self._inodes_check("host", image, table, numbers, n, stride, files, meta, status,
+                                                        piece_status)
+        rec = _native.InodeCounts()
+        check(lib().ppfs_ecc_read_inodes_host(
+            self._h, _ptr(image), blocks, t.ctypes.data, addr, stride, n, self._u32_ptr(files), self._u32_ptr(meta),
+            self._u32_ptr(status), self._u32_ptr(piece_status), byref(rec), int(bool(write_back))))
+        return InodeCounts(*[int(getattr(rec, k)) for k in INODE_COUNT_FIELDS])
+
 
 # ppfs_ecc_scrub_counts: the host forms return it as this tuple, the device forms as a CUDA int64 tensor
 # in the same field order (ScrubCounts(*tensor.tolist()) after synchronising)
@@ -707,6 +798,11 @@ FILE_COUNT_FIELDS = ("ok", "corrected", "failed", "out_of_range", "index_ok", "i
                      "index_out_of_range")
 FileCounts = collections.namedtuple("FileCounts", FILE_COUNT_FIELDS)
 FILE_DTYPE = _native.FILE_DTYPE
+# ppfs_ecc_inode_counts, likewise: the five categories, then the three reserved words
+INODE_COUNT_FIELDS = ("ok", "corrected", "failed", "out_of_range", "not_allocated", "reserved0", "reserved1", "reserved2")
+InodeCounts = collections.namedtuple("InodeCounts", INODE_COUNT_FIELDS)
+INODE_TABLE_DTYPE = _native.INODE_TABLE_DTYPE
+INODE_META_DTYPE = _native.INODE_META_DTYPE
 
 
 class EccGroup:
@@ -853,4 +949,4 @@ def crc_implicit_to_explicit(p: int) -> int:
     return int(lib().ppfs_ecc_crc_implicit_to_explicit(ctypes.c_uint64(p)))
 
 
-__all__ = ["EccEngine", "ScrubCounts", "SCRUB_COUNT_FIELDS", "FileCounts", "FILE_COUNT_FIELDS", "FILE_DTYPE", "crc_implicit_to_explicit", "device_copy", "inject_bytes", "pinned", "vote3", "vote3_host", "_native"]
+__all__ = ["EccEngine", "ScrubCounts", "SCRUB_COUNT_FIELDS", "FileCounts", "FILE_COUNT_FIELDS", "FILE_DTYPE", "InodeCounts", "INODE_COUNT_FIELDS", "INODE_TABLE_DTYPE", "INODE_META_DTYPE", "crc_implicit_to_explicit", "device_copy", "inject_bytes", "pinned", "vote3", "vote3_host", "_native"]
