@@ -43,6 +43,13 @@
  * files' trees walked in one engine call.
  * writeFile / writeFiles are the in-place case of FileIO::writeFile from the same 64 bytes: a range inside the
  * file, or a batch of them, written without the iterator loop; nothing is allocated and no inode is updated.
+ *
+ * Every one of those overrides in EngineBlockDevice is built from the same few steps, each of which exists once:
+ * _wb (the engine calls' write_back flag), engine_image() (the mapped image, or null, for a batch engine call),
+ * status_error() / report() (engine statuses as per-entry FsError bytes, correction events and zeroed payloads),
+ * list_unmapped() (the list calls on a disk without a mapping) and FileBatch (the file calls' selection, plan and
+ * tree walk, and each file's events and first failing block).  The comment above each override states its one
+ * deviation from the per-block loop, which defines it.
  */
 #include <algorithm>
 #include <cstddef>
@@ -118,6 +125,7 @@ enum class FsError : uint8_t {
     Config_UnknownKey
 };
 static_assert((int)FsError::BlockDevice_CorrectionError == PPFS_ECC_CORRECTION_ERROR, "status 5");
+static_assert((int)FsError::Disk_OutOfBounds == PPFS_ECC_OUT_OF_BOUNDS, "status 9");
 
 // ------------------------------------------------------------------------------------------
 // std::expected<T, E> subset
@@ -1155,6 +1163,40 @@ private:
 // Shared plumbing of the four ECC codecs: the per-block RMW path and the batched path both go
 // through the engine's host entry points (pinned staging, chunked, H2D/kernel/D2H overlapped).
 class EngineBlockDevice : public IBlockDevice {
+protected:
+    // The steps every batch call below is made of, each in one place.
+
+    // The mapped disk image when a batch call may run the engine on it in place, else null: the disk is mapped,
+    // the code is no shortened RS code (whose write-back may run into the next block) and the engine exists.
+    // ppfs_ecc_create gives every codec a raw block of at least one byte, so _raw == 0 says that it failed.
+    // A condition only one call has (_ds, n, a file's range) stands at that call.
+    uint8_t* engine_image() { return !has_spill() && _raw ? _disk.mapped() : nullptr; }
+
+    // An engine status as the FsError byte the per-block call reports: ok and corrected are no error, and every
+    // other status is the FsError's own value (the static_asserts at FsError; 255, not allocated, stays 255).
+    static uint8_t status_error(uint8_t status) { return status <= PPFS_ECC_CORRECTED ? 0 : status; }
+
+    // The n statuses of an engine call as the per-block calls report them, in entry order: a correction event
+    // for every status 1 at block_of(i), err[i] (err may be null) 0 or the error, and, with `payloads`, zeros
+    // for a failed entry's dataSize() bytes.
+    template <class BlockOf> void report(const uint8_t* status, size_t n, BlockOf block_of, uint8_t* err, uint8_t* payloads = nullptr)
+    {
+        for (size_t i = 0; i < n; ++i) {
+            if (err)
+                err[i] = status_error(status[i]);
+            if (status[i] == PPFS_ECC_OK) // nearly every entry, and a scrub of a whole image walks 2^20 of them
+                continue;
+            if (status[i] == PPFS_ECC_CORRECTED)
+                log(block_of(i));
+            else if (payloads)
+                std::memset(payloads + i * _ds, 0, _ds);
+        }
+    }
+    // report's rules: entry i is block first + i / idx[i] / ext[i].block
+    static auto from(block_index_t first) { return [first](size_t i) { return first + (block_index_t)i; }; }
+    static auto of(const block_index_t* idx) { return [idx](size_t i) { return idx[i]; }; }
+    static auto of(const ppfs_ecc_extent* ext) { return [ext](size_t i) { return ext[i].block; }; }
+
 public:
     size_t rawBlockSize() const override { return _raw; }
     size_t dataSize() const override { return _ds; }
@@ -1232,6 +1274,9 @@ public:
     {
         if (err)
             std::memset(err, 0, count);
+        // Not engine_image(): that also asks for an engine, and here a device without one (_raw == 0) can be told
+        // from the outside.  On the image its null-context engine call fails for an empty range too, where the
+        // staged path below returns success, and the staged path makes a zero-byte disk read first.
         if (uint8_t* img = _disk.mapped(); img && !has_spill()) {
             // in place on the disk image: the engine writes corrected codewords back into it
             // (RS: whole codeword, Hamming: the flipped byte, as the reference's write-back)
@@ -1242,15 +1287,7 @@ public:
                                    1, nullptr),
                     "decode"))
                 return unexpected(FsError::Disk_IOError);
-            for (size_t i = 0; i < count; ++i) {
-                if (status[i] == PPFS_ECC_CORRECTION_ERROR) {
-                    if (err)
-                        err[i] = (uint8_t)FsError::BlockDevice_CorrectionError;
-                    std::memset(out + i * _ds, 0, _ds);
-                } else if (status[i] == PPFS_ECC_CORRECTED) {
-                    log(first + (block_index_t)i);
-                }
-            }
+            report(status.data(), count, from(first), err, out);
             return {};
         }
         size_t done = 0;
@@ -1270,9 +1307,9 @@ public:
             size_t i = 0;
             for (; i < nb; ++i) {
                 const block_index_t b = b0 + (block_index_t)i;
-                if (status[i] == PPFS_ECC_CORRECTION_ERROR) {
+                if (const uint8_t e = status_error(status[i])) {
                     if (err)
-                        err[done + i] = (uint8_t)FsError::BlockDevice_CorrectionError;
+                        err[done + i] = e;
                     std::memset(out + (done + i) * _ds, 0, _ds);
                     continue;
                 }
@@ -1309,30 +1346,23 @@ public:
             }
             return {};
         }
-        uint8_t* img = _disk.mapped();
+        uint8_t* img = _disk.mapped(); // as readBlocks: a device without an engine takes the path it took
         if (img && ((size_t)first + count) * _raw > _disk.size())
             return unexpected(FsError::Disk_OutOfBounds);
         std::vector<uint8_t> raw(img ? 0 : count * _raw), status(count);
-        if (img) { // in place on the disk image
-            if (!EccEngine::ok(
-                ppfs_ecc_write_host(_eng.ctx(), payloads, img + (size_t)first * _raw, status.data(), count), "write"))
-                return unexpected(FsError::Disk_IOError);
-        } else {
+        if (!img) {
             auto rr = detail::disk_read(_disk, (size_t)first * _raw, count * _raw, raw.data());
             if (!rr)
                 return unexpected(rr.error());
-            if (!EccEngine::ok(ppfs_ecc_write_host(_eng.ctx(), payloads, raw.data(), status.data(), count), "write"))
-                return unexpected(FsError::Disk_IOError);
         }
-        for (size_t i = 0; i < count; ++i) {
-            if (status[i] == PPFS_ECC_CORRECTION_ERROR) {
-                if (err)
-                    err[i] = (uint8_t)FsError::BlockDevice_CorrectionError;
-            } else if (status[i] == PPFS_ECC_CORRECTED) {
-                log(first + (block_index_t)i); // the old block's write-back is overwritten below
-            }
-        }
-        // blocks that failed their check were left untouched by the engine
+        // the rows: in place on the disk image, or the copy just read
+        if (!EccEngine::ok(
+                ppfs_ecc_write_host(_eng.ctx(), payloads, img ? img + (size_t)first * _raw : raw.data(), status.data(), count),
+                "write"))
+            return unexpected(FsError::Disk_IOError);
+        // a corrected old block's write-back is overwritten by the new block; blocks that failed their check
+        // were left untouched by the engine
+        report(status.data(), count, from(first), err);
         if (img)
             return {};
         auto w = detail::disk_write(_disk, (size_t)first * _raw, raw.data(), count * _raw);
@@ -1345,149 +1375,94 @@ public:
     // the next block): one ppfs_ecc_*_list_host call on the image, which gathers the listed rows,
     // cuts the list where an index repeats and copies the changed rows back.  Otherwise the rows are
     // read from the disk entry by entry, each stretch of the list without a repeated index goes
-    // through one contiguous engine call, and the write-backs go to the disk in list order.
+    // through one contiguous engine call, and the write-backs go to the disk in list order
+    // (list_unmapped; a shortened RS code and a device without an engine take the per-block loop there).
+    // The lists used to test for those two before they asked for the mapping and the other calls after;
+    // mapped() only hands out an address, so the order cannot be told and engine_image() serves both.
     expected<void> readBlockList(const block_index_t* idx, size_t count, uint8_t* out, uint8_t* err) override
     {
-        if (has_spill() || !_raw)
-            return IBlockDevice::readBlockList(idx, count, out, err);
         if (err)
             std::memset(err, 0, count);
-        if (uint8_t* img = _disk.mapped()) {
+        if (uint8_t* img = engine_image()) {
             std::vector<uint8_t> status(count);
             if (!EccEngine::ok(ppfs_ecc_decode_list_host(_eng.ctx(), img, _disk.size() / _raw, idx, count, out,
                                    status.data(), 1, nullptr),
                     "decode list"))
                 return unexpected(FsError::Disk_IOError);
-            for (size_t i = 0; i < count; ++i) {
-                if (status[i] == PPFS_ECC_OUT_OF_BOUNDS || status[i] == PPFS_ECC_CORRECTION_ERROR) {
-                    if (err)
-                        err[i] = (uint8_t)(status[i] == PPFS_ECC_OUT_OF_BOUNDS ? FsError::Disk_OutOfBounds
-                                                                               : FsError::BlockDevice_CorrectionError);
-                    std::memset(out + i * _ds, 0, _ds);
-                } else if (status[i] == PPFS_ECC_CORRECTED) {
-                    log(idx[i]);
-                }
-            }
+            report(status.data(), count, of(idx), err, out);
             return {};
         }
-        std::vector<uint8_t> raw, fixed, status, dec;
-        std::vector<size_t> pos;
-        for (size_t s = 0; s < count;) {
-            const size_t e = list_run_end(idx, count, s);
-            if (!list_rows(idx, s, e, pos, raw)) { // a row could not be read: block by block
-                auto r = IBlockDevice::readBlockList(idx + s, e - s, out + s * _ds, err ? err + s : nullptr);
-                if (!r)
-                    return r;
-                s = e;
-                continue;
-            }
-            for (size_t i = s, j = 0; i < e; ++i) { // off the disk: the per-block call's error
-                if (j < pos.size() && pos[j] == i) {
-                    ++j;
-                    continue;
-                }
-                auto r = IBlockDevice::readBlockList(idx + i, 1, out + i * _ds, err ? err + i : nullptr);
-                if (!r)
-                    return r;
-            }
-            const size_t m = pos.size();
-            if (m) {
+        std::vector<uint8_t> fixed, status, dec;
+        return list_unmapped(
+            idx, count,
+            [&](size_t i, size_t n) { return IBlockDevice::readBlockList(idx + i, n, out + i * _ds, err ? err + i : nullptr); },
+            [&](const std::vector<size_t>& pos, std::vector<uint8_t>& raw) {
+                const size_t m = pos.size();
                 fixed = raw;
                 status.assign(m, 0);
                 dec.assign(m * _ds, 0);
-                const int wb = (_type == PPFS_ECC_REED_SOLOMON || _type == PPFS_ECC_HAMMING) ? 1 : 0;
-                if (!EccEngine::ok(ppfs_ecc_decode_host(_eng.ctx(), fixed.data(), dec.data(), status.data(), m, wb, nullptr),
+                if (!EccEngine::ok(ppfs_ecc_decode_host(_eng.ctx(), fixed.data(), dec.data(), status.data(), m, _wb, nullptr),
                         "decode"))
-                    return unexpected(FsError::Disk_IOError);
-            }
-            for (size_t j = 0; j < m; ++j) {
-                const size_t i = pos[j];
-                if (status[j] == PPFS_ECC_CORRECTION_ERROR) {
-                    if (err)
-                        err[i] = (uint8_t)FsError::BlockDevice_CorrectionError;
-                    std::memset(out + i * _ds, 0, _ds);
-                    continue;
+                    return false;
+                for (size_t j = 0; j < m; ++j) {
+                    const size_t i = pos[j];
+                    if (const uint8_t e = status_error(status[j])) {
+                        if (err)
+                            err[i] = e;
+                        std::memset(out + i * _ds, 0, _ds);
+                        continue;
+                    }
+                    std::memcpy(out + i * _ds, dec.data() + j * _ds, _ds);
+                    if (status[j] == PPFS_ECC_CORRECTED) {
+                        auto wb = write_back(idx[i], raw.data() + j * _raw, fixed.data() + j * _raw, nullptr);
+                        if (!wb && err)
+                            err[i] = (uint8_t)wb.error();
+                    }
                 }
-                std::memcpy(out + i * _ds, dec.data() + j * _ds, _ds);
-                if (status[j] == PPFS_ECC_CORRECTED) {
-                    auto wb = write_back(idx[i], raw.data() + j * _raw, fixed.data() + j * _raw, nullptr);
-                    if (!wb && err)
-                        err[i] = (uint8_t)wb.error();
-                }
-            }
-            s = e;
-        }
-        return {};
+                return true;
+            });
     }
 
     expected<void> writeBlockList(const block_index_t* idx, size_t count, const uint8_t* payloads, uint8_t* err) override
     {
-        if (has_spill() || !_raw)
-            return IBlockDevice::writeBlockList(idx, count, payloads, err);
         if (err)
             std::memset(err, 0, count);
-        if (uint8_t* img = _disk.mapped()) {
+        if (uint8_t* img = engine_image()) {
             std::vector<uint8_t> status(count);
             if (!EccEngine::ok(ppfs_ecc_write_list_host(_eng.ctx(), payloads, img, _disk.size() / _raw, idx,
                                    status.data(), count),
                     "write list"))
                 return unexpected(FsError::Disk_IOError);
-            for (size_t i = 0; i < count; ++i) {
-                if (status[i] == PPFS_ECC_OUT_OF_BOUNDS || status[i] == PPFS_ECC_CORRECTION_ERROR) {
-                    if (err)
-                        err[i] = (uint8_t)(status[i] == PPFS_ECC_OUT_OF_BOUNDS ? FsError::Disk_OutOfBounds
-                                                                               : FsError::BlockDevice_CorrectionError);
-                } else if (status[i] == PPFS_ECC_CORRECTED) {
-                    log(idx[i]); // the old block's write-back was overwritten by the new block
-                }
-            }
+            report(status.data(), count, of(idx), err); // a corrected old block's write-back was overwritten by the new block
             return {};
         }
-        std::vector<uint8_t> raw, status, pay;
-        std::vector<size_t> pos;
-        for (size_t s = 0; s < count;) {
-            const size_t e = list_run_end(idx, count, s);
-            if (!list_rows(idx, s, e, pos, raw)) {
-                auto r = IBlockDevice::writeBlockList(idx + s, e - s, payloads + s * _ds, err ? err + s : nullptr);
-                if (!r)
-                    return r;
-                s = e;
-                continue;
-            }
-            for (size_t i = s, j = 0; i < e; ++i) {
-                if (j < pos.size() && pos[j] == i) {
-                    ++j;
-                    continue;
-                }
-                auto r = IBlockDevice::writeBlockList(idx + i, 1, payloads + i * _ds, err ? err + i : nullptr);
-                if (!r)
-                    return r;
-            }
-            const size_t m = pos.size();
-            if (m) {
+        std::vector<uint8_t> status, pay;
+        return list_unmapped(
+            idx, count,
+            [&](size_t i, size_t n) { return IBlockDevice::writeBlockList(idx + i, n, payloads + i * _ds, err ? err + i : nullptr); },
+            [&](const std::vector<size_t>& pos, std::vector<uint8_t>& raw) {
+                const size_t m = pos.size();
                 status.assign(m, 0);
                 pay.resize(m * _ds);
                 for (size_t j = 0; j < m; ++j)
                     std::memcpy(pay.data() + j * _ds, payloads + pos[j] * _ds, _ds);
                 if (!EccEngine::ok(ppfs_ecc_write_host(_eng.ctx(), pay.data(), raw.data(), status.data(), m), "write"))
-                    return unexpected(FsError::Disk_IOError);
-            }
-            for (size_t j = 0; j < m; ++j) {
-                const size_t i = pos[j];
-                if (status[j] == PPFS_ECC_CORRECTION_ERROR) {
-                    if (err)
-                        err[i] = (uint8_t)FsError::BlockDevice_CorrectionError; // block left untouched
-                    continue;
+                    return false;
+                for (size_t j = 0; j < m; ++j) {
+                    const size_t i = pos[j];
+                    if (const uint8_t e = status_error(status[j])) {
+                        if (err)
+                            err[i] = e; // block left untouched
+                        continue;
+                    }
+                    if (status[j] == PPFS_ECC_CORRECTED)
+                        log(idx[i]);
+                    auto w = detail::disk_write(_disk, (size_t)idx[i] * _raw, raw.data() + j * _raw, _raw);
+                    if (!w && err)
+                        err[i] = (uint8_t)w.error();
                 }
-                if (status[j] == PPFS_ECC_CORRECTED)
-                    log(idx[i]);
-                auto w = detail::disk_write(_disk, (size_t)idx[i] * _raw, raw.data() + j * _raw, _raw);
-                if (!w && err)
-                    err[i] = (uint8_t)w.error();
-            }
-            s = e;
-        }
-        return {};
+                return true;
+            });
     }
 
     // Extents.  With a mapped disk image and no shortened RS code: one ppfs_ecc_*_extents_host call on
@@ -1495,29 +1470,28 @@ public:
     // bytes of one block both land.  Otherwise the per-block loop.
     expected<void> readExtents(const ppfs_ecc_extent* ext, size_t n, uint8_t* out, size_t out_bytes, uint8_t* err) override
     {
-        uint8_t* img = _disk.mapped();
-        if (!img || has_spill() || !_raw || !n)
+        uint8_t* img = engine_image();
+        if (!img || !n)
             return IBlockDevice::readExtents(ext, n, out, out_bytes, err);
         std::vector<uint8_t> status(n);
-        const int wb = (_type == PPFS_ECC_REED_SOLOMON || _type == PPFS_ECC_HAMMING) ? 1 : 0;
         if (!EccEngine::ok(ppfs_ecc_read_extents_host(_eng.ctx(), img, _disk.size() / _raw, ext, n, out, out_bytes,
-                               status.data(), wb),
+                               status.data(), _wb),
                 "read extents"))
             return unexpected(FsError::Disk_IOError);
-        extent_errors(ext, n, status.data(), err);
+        report(status.data(), n, of(ext), err);
         return {};
     }
     expected<void> writeExtents(const ppfs_ecc_extent* ext, size_t n, const uint8_t* in, size_t in_bytes, uint8_t* err) override
     {
-        uint8_t* img = _disk.mapped();
-        if (!img || has_spill() || !_raw || !n)
+        uint8_t* img = engine_image();
+        if (!img || !n)
             return IBlockDevice::writeExtents(ext, n, in, in_bytes, err);
         std::vector<uint8_t> status(n);
         if (!EccEngine::ok(ppfs_ecc_write_extents_host(_eng.ctx(), in, in_bytes, img, _disk.size() / _raw, ext, n,
                                status.data()),
                 "write extents"))
             return unexpected(FsError::Disk_IOError);
-        extent_errors(ext, n, status.data(), err);
+        report(status.data(), n, of(ext), err);
         return {};
     }
 
@@ -1531,45 +1505,33 @@ public:
         const size_t base = (size_t)first * _raw;
         if (base + count * _raw > _disk.size())
             return unexpected(FsError::Disk_OutOfBounds);
-        if (uint8_t* img = _disk.mapped()) { // in place on the disk image
-            std::vector<uint8_t> status(count);
-            size_t c3[3] = { 0, 0, 0 };
-            if (!EccEngine::ok(
-                ppfs_ecc_scrub_host(_eng.ctx(), img + base, _disk.size() - base, count, status.data(), c3), "scrub"))
-                return unexpected(FsError::Disk_IOError);
-            for (size_t i = 0; i < count; ++i) {
-                if (status[i] == PPFS_ECC_CORRECTION_ERROR && err)
-                    err[i] = (uint8_t)FsError::BlockDevice_CorrectionError;
-                else if (status[i] == PPFS_ECC_CORRECTED)
-                    log(first + (block_index_t)i);
-            }
-            if (counts)
-                std::memcpy(counts, c3, sizeof c3);
-            return {};
+        // in place on the disk image (the call handles a shortened code itself, so the mapping is all it asks
+        // for); without one on a copy read from the disk, whose changed byte range goes back afterwards
+        uint8_t* const img = _disk.mapped();
+        const size_t bytes = _disk.size() - base;
+        std::vector<uint8_t> copy(img ? 0 : bytes), before, status(count);
+        if (!img) {
+            auto rr = detail::disk_read(_disk, base, bytes, copy.data());
+            if (!rr)
+                return unexpected(rr.error());
+            before = copy;
         }
-        std::vector<uint8_t> image(_disk.size() - base), status(count);
-        auto rr = detail::disk_read(_disk, base, image.size(), image.data());
-        if (!rr)
-            return unexpected(rr.error());
-        const std::vector<uint8_t> before = image;
+        uint8_t* const image = img ? img + base : copy.data();
         size_t c3[3] = { 0, 0, 0 };
-        if (!EccEngine::ok(ppfs_ecc_scrub_host(_eng.ctx(), image.data(), image.size(), count, status.data(), c3), "scrub"))
+        if (!EccEngine::ok(ppfs_ecc_scrub_host(_eng.ctx(), image, bytes, count, status.data(), c3), "scrub"))
             return unexpected(FsError::Disk_IOError);
-        for (size_t i = 0; i < count; ++i) {
-            if (status[i] == PPFS_ECC_CORRECTION_ERROR && err)
-                err[i] = (uint8_t)FsError::BlockDevice_CorrectionError;
-            else if (status[i] == PPFS_ECC_CORRECTED)
-                log(first + (block_index_t)i);
-        }
-        size_t lo = 0, hi = image.size();
-        while (lo < hi && image[lo] == before[lo])
-            ++lo;
-        while (hi > lo && image[hi - 1] == before[hi - 1])
-            --hi;
-        if (hi > lo) {
-            auto w = detail::disk_write(_disk, base + lo, image.data() + lo, hi - lo);
-            if (!w)
-                return unexpected(w.error());
+        report(status.data(), count, from(first), err);
+        if (!img) {
+            size_t lo = 0, hi = bytes;
+            while (lo < hi && copy[lo] == before[lo])
+                ++lo;
+            while (hi > lo && copy[hi - 1] == before[hi - 1])
+                --hi;
+            if (hi > lo) {
+                auto w = detail::disk_write(_disk, base + lo, copy.data() + lo, hi - lo);
+                if (!w)
+                    return unexpected(w.error());
+            }
         }
         if (counts)
             std::memcpy(counts, c3, sizeof c3);
@@ -1581,8 +1543,8 @@ public:
     // events the reads logged.
     expected<void> scrubList(const block_index_t* idx, size_t n, ppfs_ecc_scrub_counts* counts, uint8_t* err) override
     {
-        uint8_t* img = _disk.mapped();
-        if (!img || has_spill() || !_raw) {
+        uint8_t* img = engine_image();
+        if (!img) {
             const size_t logged = _logged;
             ppfs_ecc_scrub_counts c {};
             auto r = IBlockDevice::scrubList(idx, n, &c, err);
@@ -1598,12 +1560,7 @@ public:
         ppfs_ecc_scrub_counts c {};
         if (!EccEngine::ok(ppfs_ecc_scrub_list_host(_eng.ctx(), img, _disk.size() / _raw, idx, n, status.data(), &c), "scrub list"))
             return unexpected(FsError::Disk_IOError);
-        for (size_t i = 0; i < n; ++i) {
-            if (status[i] == PPFS_ECC_CORRECTED)
-                log(idx[i]);
-            if (err) // statuses 5 and 9 are FsError's BlockDevice_CorrectionError and Disk_OutOfBounds
-                err[i] = status[i] == PPFS_ECC_CORRECTED ? 0 : status[i];
-        }
+        report(status.data(), n, of(idx), err);
         if (counts)
             *counts = c;
         return {};
@@ -1614,8 +1571,8 @@ public:
     expected<void> scrubAllocated(block_index_t bitmap_block, block_index_t first_data_block, size_t nbits,
         ppfs_ecc_scrub_counts* counts, uint8_t* err, uint8_t* bitmap_err) override
     {
-        uint8_t* img = _disk.mapped();
-        if (!img || has_spill() || !_raw || !_ds) {
+        uint8_t* img = engine_image();
+        if (!img || !_ds) {
             const size_t logged = _logged;
             ppfs_ecc_scrub_counts c {};
             auto r = IBlockDevice::scrubAllocated(bitmap_block, first_data_block, nbits, &c, err, bitmap_err);
@@ -1635,18 +1592,8 @@ public:
                                nbits, status.data(), bst.data(), &c),
                 "scrub allocated"))
             return unexpected(FsError::Disk_OutOfBounds); // the only failures are the arguments': a range off the image
-        for (size_t b = 0; b < B; ++b) {
-            if (bst[b] == PPFS_ECC_CORRECTED)
-                log(bitmap_block + (block_index_t)b);
-            if (bitmap_err)
-                bitmap_err[b] = bst[b] == PPFS_ECC_CORRECTED ? 0 : bst[b];
-        }
-        for (size_t j = 0; j < nbits; ++j) {
-            if (status[j] == PPFS_ECC_CORRECTED)
-                log(first_data_block + (block_index_t)j);
-            if (err)
-                err[j] = status[j] == PPFS_ECC_CORRECTED ? 0 : status[j];
-        }
+        report(bst.data(), B, from(bitmap_block), bitmap_err);
+        report(status.data(), nbits, from(first_data_block), err); // a clear bit's 255 is no FsError and stays
         if (counts)
             *counts = c;
         return {};
@@ -1661,24 +1608,21 @@ public:
     // for a range the loop refuses partway (past the file or the tree), the per-block loop.
     expected<void> fileBlocks(const ppfs_ecc_file& file, uint64_t first, size_t count, block_index_t* idx, uint8_t* err) override
     {
-        uint8_t* img = file_image(file, first, count);
-        if (!img)
+        FileBatch b(*this);
+        b.add(0, file, first, count);
+        if (!b.img)
             return IBlockDevice::fileBlocks(file, first, count, idx, err);
-        std::vector<uint8_t> path(count);
-        std::vector<FileEvent> events;
-        if (!file_walk(img, file, first, count, idx, path.data(), events))
+        if (!b.walk_one(idx))
             return unexpected(FsError::Disk_IOError);
-        log_in_order(events);
-        size_t bad = 0;
-        while (bad < count && path[bad] == 0)
-            ++bad;
+        b.log(0);
+        uint8_t e = 0;
+        const size_t bad = b.first_failure(0, e);
         if (err) {
             std::memset(err, 0, bad);
-            if (bad < count)
-                std::memset(err + bad, path[bad], count - bad);
+            std::memset(err + bad, e, count - bad);
         }
-        if (bad < count)
-            return unexpected((FsError)path[bad]); // 5 and 9 are BlockDevice_CorrectionError and Disk_OutOfBounds
+        if (e)
+            return unexpected((FsError)e);
         return {};
     }
     expected<size_t> readFile(const ppfs_ecc_file& file, size_t offset, size_t bytes_to_read, uint8_t* out,
@@ -1687,48 +1631,19 @@ public:
         if (bytes_to_read == 0 || _ds == 0 || offset >= file.file_size)
             return IBlockDevice::readFile(file, offset, bytes_to_read, out, delivered);
         const size_t n = std::min<size_t>(bytes_to_read, file.file_size - offset);
-        const uint64_t first = offset / _ds;
-        const size_t count = (offset % _ds + n + _ds - 1) / _ds;
-        uint8_t* img = file_image(file, first, count);
-        if (!img)
+        FileBatch b(*this);
+        b.add_range(0, file, offset, n);
+        if (!b.img)
             return IBlockDevice::readFile(file, offset, bytes_to_read, out, delivered);
-        std::vector<block_index_t> idx(count);
-        std::vector<uint8_t> path(count), status(count, 0);
-        std::vector<FileEvent> events;
-        if (!file_walk(img, file, first, count, idx.data(), path.data(), events))
+        if (!b.walk_one() || !b.read_extents(out, n, "read file extents")) // straight into the caller's buffer
             return unexpected(FsError::Disk_IOError);
-        const std::vector<ppfs_ecc_extent> all = file_extents(idx.data(), count, offset % _ds, n, _ds);
-        std::vector<ppfs_ecc_extent> live;
-        std::vector<size_t> live_at;
-        for (size_t i = 0; i < count; ++i)
-            if (!path[i]) {
-                live.push_back(all[i]);
-                live_at.push_back(i);
-            }
-        if (!live.empty()) {
-            std::vector<uint8_t> st(live.size());
-            const int wb = (_type == PPFS_ECC_REED_SOLOMON || _type == PPFS_ECC_HAMMING) ? 1 : 0;
-            if (!EccEngine::ok(ppfs_ecc_read_extents_host(_eng.ctx(), img, _disk.size() / _raw, live.data(), live.size(), out, n,
-                                   st.data(), wb),
-                    "read file extents"))
-                return unexpected(FsError::Disk_IOError);
-            for (size_t k = 0; k < live.size(); ++k)
-                status[live_at[k]] = st[k];
-        }
-        for (size_t i = 0; i < count; ++i)
-            if (status[i] == PPFS_ECC_CORRECTED)
-                events.push_back(FileEvent { first + i, 3, idx[i] });
-        log_in_order(events);
+        b.log(0);
+        uint8_t e = 0;
+        const size_t done = b.delivered(0, b.first_failure(0, e));
         if (delivered)
-            *delivered = n;
-        for (size_t i = 0; i < count; ++i) {
-            const uint8_t e = path[i] ? path[i] : status[i] == PPFS_ECC_CORRECTED ? 0 : status[i];
-            if (e) {
-                if (delivered)
-                    *delivered = (size_t)all[i].pos;
-                return unexpected((FsError)e);
-            }
-        }
+            *delivered = done;
+        if (e)
+            return unexpected((FsError)e);
         return n;
     }
 
@@ -1740,106 +1655,37 @@ public:
     // one the loop refuses partway, the loop over readFile.
     void readFiles(FileRead* reads, size_t n) override
     {
-        struct Span {
-            size_t at, nbytes, count; // the read's number, its clamped bytes and its blocks
-            uint64_t first;
-        };
-        uint8_t* img = _disk.mapped();
-        bool engine = img && !has_spill() && _raw && _ds;
-        std::vector<Span> sel;
-        for (size_t i = 0; i < n && engine; ++i) {
-            const FileRead& r = reads[i];
-            if (r.bytes_to_read == 0 || r.offset >= r.file.file_size)
-                continue; // answered from the range alone
-            const size_t nbytes = std::min<size_t>(r.bytes_to_read, r.file.file_size - r.offset);
-            const Span s { i, nbytes, (r.offset % _ds + nbytes + _ds - 1) / _ds, r.offset / _ds };
-            engine = file_image(r.file, s.first, s.count) != nullptr;
-            sel.push_back(s);
-        }
-        if (!engine || sel.empty())
+        auto by_range = [](const FileRead& r) { return r.bytes_to_read == 0 || r.offset >= r.file.file_size; };
+        auto loop_one = [&](FileRead& r) { read_one(r, IBlockDevice::readFile(r.file, r.offset, r.bytes_to_read, r.out, &r.delivered)); };
+        FileBatch b(*this);
+        for (size_t i = 0; i < n; ++i)
+            if (!by_range(reads[i])) // else answered from the range alone
+                b.add_range(i, reads[i].file, reads[i].offset, std::min<size_t>(reads[i].bytes_to_read, reads[i].file.file_size - reads[i].offset));
+        if (!b.img || b.sel.empty())
             return IBlockDevice::readFiles(reads, n);
         for (size_t i = 0; i < n; ++i)
-            if (reads[i].bytes_to_read == 0 || reads[i].offset >= reads[i].file.file_size)
-                read_one(reads[i],
-                    IBlockDevice::readFile(reads[i].file, reads[i].offset, reads[i].bytes_to_read, reads[i].out, &reads[i].delivered));
+            if (by_range(reads[i]))
+                loop_one(reads[i]);
         auto fail_all = [&]() {
-            for (const Span& s : sel) {
+            for (const FileBatch::Span& s : b.sel) {
                 reads[s.at].delivered = 0;
                 read_one(reads[s.at], expected<size_t>(unexpected(FsError::Disk_IOError)));
             }
         };
-        const size_t m = sel.size(), image_blocks = _disk.size() / _raw;
-        std::vector<ppfs_ecc_file> files(m);
-        std::vector<ppfs_ecc_file_range> ranges(m);
-        for (size_t k = 0; k < m; ++k) {
-            files[k] = reads[sel[k].at].file;
-            ranges[k] = ppfs_ecc_file_range { reads[sel[k].at].offset, sel[k].nbytes };
-        }
-        std::vector<ppfs_ecc_files_slot> slots(m);
-        ppfs_ecc_files_totals tot {};
-        if (!EccEngine::ok(ppfs_ecc_files_plan(_eng.ctx(), files.data(), ranges.data(), m, slots.data(), &tot), "files plan"))
+        if (!b.walk(true))
             return fail_all();
-        std::vector<block_index_t> idx(tot.blocks), tidx(tot.tree_blocks);
-        std::vector<uint8_t> path(tot.blocks), status(tot.blocks, 0), tst(tot.tree_blocks), buf(tot.bytes);
-        const int wb = (_type == PPFS_ECC_REED_SOLOMON || _type == PPFS_ECC_HAMMING) ? 1 : 0;
-        if (!EccEngine::ok(ppfs_ecc_files_blocks_host(_eng.ctx(), img, image_blocks, files.data(), ranges.data(), m, idx.data(),
-                               path.data(), tidx.data(), tst.data(), nullptr, nullptr, wb),
-                "files blocks"))
+        std::vector<uint8_t> buf(b.tot.bytes);
+        for (size_t k = 0; k < b.sel.size(); ++k) // what no block writes stays the caller's
+            std::memcpy(buf.data() + b.slots[k].out_pos, reads[b.sel[k].at].out, b.ranges[k].nbytes);
+        if (!b.read_extents(buf.data(), buf.size(), "read files extents"))
             return fail_all();
-        std::vector<ppfs_ecc_extent> all, live;
-        std::vector<size_t> live_at;
-        for (size_t k = 0; k < m; ++k) {
-            const FileRead& r = reads[sel[k].at];
-            std::vector<ppfs_ecc_extent> own = file_extents(idx.data() + slots[k].block_pos, sel[k].count, r.offset % _ds, sel[k].nbytes, _ds);
-            std::memcpy(buf.data() + slots[k].out_pos, r.out, sel[k].nbytes); // what no block writes stays the caller's
-            for (ppfs_ecc_extent& e : own) {
-                e.pos += slots[k].out_pos;
-                all.push_back(e);
-            }
-        }
-        if (all.size() != tot.blocks)
-            return fail_all();
-        for (size_t i = 0; i < all.size(); ++i)
-            if (!path[i]) {
-                live.push_back(all[i]);
-                live_at.push_back(i);
-            }
-        if (!live.empty()) {
-            std::vector<uint8_t> st(live.size());
-            if (!EccEngine::ok(ppfs_ecc_read_extents_host(_eng.ctx(), img, image_blocks, live.data(), live.size(), buf.data(),
-                                   buf.size(), st.data(), wb),
-                    "read files extents"))
-                return fail_all();
-            for (size_t k = 0; k < live.size(); ++k)
-                status[live_at[k]] = st[k];
-        }
-        for (size_t k = 0; k < m; ++k) {
-            FileRead& r = reads[sel[k].at];
-            const ppfs_ecc_files_slot& s = slots[k];
-            std::vector<FileEvent> events;
-            std::vector<uint64_t> under[3];
-            file_tree_under(sel[k].first, sel[k].count, under);
-            for (int d = 0; d < 3; ++d)
-                for (size_t i = 0; i < under[d].size() && i < s.tree_n[d]; ++i)
-                    if (tst[s.tree_pos[d] + i] == PPFS_ECC_CORRECTED)
-                        events.push_back(FileEvent { under[d][i], d, tidx[s.tree_pos[d] + i] });
-            for (size_t i = 0; i < sel[k].count; ++i)
-                if (status[s.block_pos + i] == PPFS_ECC_CORRECTED)
-                    events.push_back(FileEvent { sel[k].first + i, 3, idx[s.block_pos + i] });
-            log_in_order(events);
-            std::memcpy(r.out, buf.data() + s.out_pos, sel[k].nbytes);
-            r.delivered = sel[k].nbytes;
-            expected<size_t> got(sel[k].nbytes);
-            for (size_t i = 0; i < sel[k].count; ++i) {
-                const uint8_t p = path[s.block_pos + i], st = status[s.block_pos + i];
-                const uint8_t e = p ? p : st == PPFS_ECC_CORRECTED ? 0 : st;
-                if (e) {
-                    r.delivered = (size_t)(all[s.block_pos + i].pos - s.out_pos);
-                    got = expected<size_t>(unexpected((FsError)e));
-                    break;
-                }
-            }
-            read_one(r, got);
+        for (size_t k = 0; k < b.sel.size(); ++k) {
+            FileRead& r = reads[b.sel[k].at];
+            b.log(k);
+            std::memcpy(r.out, buf.data() + b.slots[k].out_pos, b.ranges[k].nbytes);
+            uint8_t e = 0;
+            r.delivered = b.delivered(k, b.first_failure(k, e));
+            read_one(r, e ? expected<size_t>(unexpected((FsError)e)) : expected<size_t>((size_t)b.ranges[k].nbytes));
         }
     }
 
@@ -1850,16 +1696,15 @@ public:
     // as well: the one deviation.  Elsewhere, and for a shortened RS code, the per-inode loop.
     void readInodes(const InodeTable& table, const uint32_t* numbers, size_t n, InodeRead* out) override
     {
-        uint8_t* img = _disk.mapped();
-        if (!img || has_spill() || !_raw || !_ds || _ds > 0xFFFFu || !n)
+        uint8_t* img = engine_image();
+        if (!img || !_ds || _ds > 0xFFFFu || !n)
             return IBlockDevice::readInodes(table, numbers, n, out);
         const size_t K = 2 + 79 / _ds, W = 1 + K;
         std::vector<ppfs_ecc_file> files(n);
         std::vector<ppfs_ecc_inode_meta> meta(n);
         std::vector<uint8_t> status(n), pieces(n * W);
-        const int wb = (_type == PPFS_ECC_REED_SOLOMON || _type == PPFS_ECC_HAMMING) ? 1 : 0;
         if (!EccEngine::ok(ppfs_ecc_read_inodes_host(_eng.ctx(), img, _disk.size() / _raw, &table, numbers, 4, n, files.data(),
-                               meta.data(), status.data(), pieces.data(), nullptr, wb),
+                               meta.data(), status.data(), pieces.data(), nullptr, _wb),
                 "read inodes")) {
             for (size_t j = 0; j < n; ++j) {
                 out[j] = InodeRead {};
@@ -1930,24 +1775,13 @@ public:
     }
     void writeFiles(FileWrite* writes, size_t n) override
     {
-        struct Span {
-            size_t at, count; // the write's number and its blocks
-            uint64_t first;
-        };
         auto by_range = [](const FileWrite& w) { return w.n == 0 || w.offset + w.n < w.offset || w.offset + w.n > w.file.file_size; };
         auto loop_one = [&](FileWrite& w) { write_one(w, IBlockDevice::writeFile(w.file, w.offset, w.in, w.n, &w.written)); };
-        uint8_t* img = _disk.mapped();
-        bool engine = img && !has_spill() && _raw && _ds;
-        std::vector<Span> sel;
-        for (size_t i = 0; i < n && engine; ++i) {
-            const FileWrite& w = writes[i];
-            if (by_range(w))
-                continue; // answered from the range alone
-            const Span s { i, (w.offset % _ds + w.n + _ds - 1) / _ds, w.offset / _ds };
-            engine = file_image(w.file, s.first, s.count) != nullptr;
-            sel.push_back(s);
-        }
-        if (!engine || sel.empty()) {
+        FileBatch b(*this);
+        for (size_t i = 0; i < n; ++i)
+            if (!by_range(writes[i])) // else answered from the range alone
+                b.add_range(i, writes[i].file, writes[i].offset, writes[i].n);
+        if (!b.img || b.sel.empty()) {
             for (size_t i = 0; i < n; ++i)
                 loop_one(writes[i]);
             return;
@@ -1956,60 +1790,29 @@ public:
             if (by_range(writes[i]))
                 loop_one(writes[i]);
         auto fail_all = [&]() {
-            for (const Span& s : sel) {
+            for (const FileBatch::Span& s : b.sel) {
                 writes[s.at].written = 0;
                 write_one(writes[s.at], expected<size_t>(unexpected(FsError::Disk_IOError)));
             }
         };
-        const size_t m = sel.size(), image_blocks = _disk.size() / _raw;
-        std::vector<ppfs_ecc_file> files(m);
-        std::vector<ppfs_ecc_file_range> ranges(m);
-        for (size_t k = 0; k < m; ++k) {
-            files[k] = writes[sel[k].at].file;
-            ranges[k] = ppfs_ecc_file_range { writes[sel[k].at].offset, writes[sel[k].at].n };
-        }
-        std::vector<ppfs_ecc_files_slot> slots(m);
-        ppfs_ecc_files_totals tot {};
-        if (!EccEngine::ok(ppfs_ecc_files_plan(_eng.ctx(), files.data(), ranges.data(), m, slots.data(), &tot), "files plan"))
+        if (!b.walk(false)) // no path statuses: the write's own status holds the path's where that is non-zero
             return fail_all();
-        std::vector<block_index_t> idx(tot.blocks), tidx(tot.tree_blocks);
-        std::vector<uint8_t> status(tot.blocks, 0), tst(tot.tree_blocks), buf(tot.bytes);
+        const size_t m = b.sel.size();
+        std::vector<uint8_t> buf(b.tot.bytes);
         std::vector<uint64_t> done(m, 0);
-        const int wb = (_type == PPFS_ECC_REED_SOLOMON || _type == PPFS_ECC_HAMMING) ? 1 : 0;
-        if (!EccEngine::ok(ppfs_ecc_files_blocks_host(_eng.ctx(), img, image_blocks, files.data(), ranges.data(), m, idx.data(),
-                               nullptr, tidx.data(), tst.data(), nullptr, nullptr, wb),
-                "files blocks"))
-            return fail_all();
         for (size_t k = 0; k < m; ++k)
-            std::memcpy(buf.data() + slots[k].out_pos, writes[sel[k].at].in, writes[sel[k].at].n);
-        if (!EccEngine::ok(ppfs_ecc_write_files_host(_eng.ctx(), buf.data(), buf.size(), img, image_blocks, files.data(),
-                               ranges.data(), m, status.data(), nullptr, done.data(), nullptr, wb),
+            std::memcpy(buf.data() + b.slots[k].out_pos, writes[b.sel[k].at].in, writes[b.sel[k].at].n);
+        if (!EccEngine::ok(ppfs_ecc_write_files_host(_eng.ctx(), buf.data(), buf.size(), b.img, _disk.size() / _raw, b.files.data(),
+                               b.ranges.data(), m, b.status.data(), nullptr, done.data(), nullptr, _wb),
                 "write files"))
             return fail_all();
         for (size_t k = 0; k < m; ++k) {
-            FileWrite& w = writes[sel[k].at];
-            const ppfs_ecc_files_slot& s = slots[k];
-            std::vector<FileEvent> events;
-            std::vector<uint64_t> under[3];
-            file_tree_under(sel[k].first, sel[k].count, under);
-            for (int d = 0; d < 3; ++d)
-                for (size_t i = 0; i < under[d].size() && i < s.tree_n[d]; ++i)
-                    if (tst[s.tree_pos[d] + i] == PPFS_ECC_CORRECTED)
-                        events.push_back(FileEvent { under[d][i], d, tidx[s.tree_pos[d] + i] });
-            for (size_t i = 0; i < sel[k].count; ++i)
-                if (status[s.block_pos + i] == PPFS_ECC_CORRECTED)
-                    events.push_back(FileEvent { sel[k].first + i, 3, idx[s.block_pos + i] });
-            log_in_order(events);
+            FileWrite& w = writes[b.sel[k].at];
+            b.log(k);
             w.written = (size_t)done[k];
-            expected<size_t> got(w.n);
-            for (size_t i = 0; i < sel[k].count; ++i) {
-                const uint8_t st = status[s.block_pos + i];
-                if (st != 0 && st != PPFS_ECC_CORRECTED) {
-                    got = expected<size_t>(unexpected((FsError)st)); // 5 and 9 are BlockDevice_CorrectionError and Disk_OutOfBounds
-                    break;
-                }
-            }
-            write_one(w, got);
+            uint8_t e = 0;
+            b.first_failure(k, e);
+            write_one(w, e ? expected<size_t>(unexpected((FsError)e)) : expected<size_t>(w.n));
         }
     }
 
@@ -2039,54 +1842,176 @@ protected:
             prev = p;
         }
     }
-    void log_in_order(std::vector<FileEvent>& events)
-    {
-        std::stable_sort(events.begin(), events.end(),
-            [](const FileEvent& a, const FileEvent& b) { return a.at != b.at ? a.at < b.at : a.level < b.level; });
-        for (const FileEvent& e : events)
-            log(e.block);
-    }
-    // the mapped image when the engine walks [first, first + count) of the file, else null
-    uint8_t* file_image(const ppfs_ecc_file& file, uint64_t first, size_t count)
-    {
-        uint8_t* img = _disk.mapped();
-        if (!img || has_spill() || !_raw || !_ds || !count)
-            return nullptr;
-        if (first + count > file_occupied(file, _ds) || file_path(first + count - 1, _ds / 4).segment > 3)
-            return nullptr;
-        return img;
-    }
-    // one engine walk of the tree: the blocks, their path statuses, and the corrected index blocks' events
-    bool file_walk(uint8_t* img, const ppfs_ecc_file& file, uint64_t first, size_t count, block_index_t* idx, uint8_t* path,
-        std::vector<FileEvent>& events)
-    {
-        const long long T = ppfs_ecc_file_tree_blocks(_eng.ctx(), &file, first, count);
-        if (T < 0)
-            return false;
-        std::vector<block_index_t> tidx((size_t)T);
-        std::vector<uint8_t> tst((size_t)T);
-        const int wb = (_type == PPFS_ECC_REED_SOLOMON || _type == PPFS_ECC_HAMMING) ? 1 : 0;
-        if (!EccEngine::ok(ppfs_ecc_file_blocks_host(_eng.ctx(), img, _disk.size() / _raw, &file, first, count, idx, path,
-                               tidx.data(), tst.data(), nullptr, wb),
-                "file blocks"))
-            return false;
-        std::vector<uint64_t> under[3];
-        file_tree_under(first, count, under);
-        size_t k = 0;
-        for (int d = 0; d < 3; ++d)
-            for (uint64_t j : under[d]) {
-                if (k < (size_t)T && tst[k] == PPFS_ECC_CORRECTED)
-                    events.push_back(FileEvent { j, d, tidx[k] });
-                ++k;
+
+    // A batch of file ranges for the engine on the mapped image -- one range for fileBlocks and readFile.  Its
+    // three parts: which of a call's entries the engine takes (add: all of them or none); the files / ranges /
+    // slots arrays with the plan and the walk of all the trees, whose results lie in the per-block and per-tree-
+    // block arrays as ppfs_ecc_files_plan says (walk; walk_one is the single-file calls, its one slot filled in
+    // here); and per file its correction events, its first failing block and the bytes before that one.
+    struct FileBatch {
+        struct Span { // an entry the engine takes: its number in the call and its file blocks
+            size_t at;
+            uint64_t first;
+            size_t count;
+        };
+        EngineBlockDevice& dev;
+        uint8_t* img; // null: the call takes the per-block loop
+        std::vector<Span> sel;
+        std::vector<ppfs_ecc_file> files;
+        std::vector<ppfs_ecc_file_range> ranges;
+        std::vector<ppfs_ecc_files_slot> slots;
+        ppfs_ecc_files_totals tot {};
+        block_index_t* idx = nullptr; // own_idx, or the caller's array
+        std::vector<block_index_t> own_idx, tidx;
+        std::vector<uint8_t> path, tst, status; // path: empty unless the walk was asked for it; status: the data blocks'
+        std::vector<ppfs_ecc_extent> all;       // read_extents: every file block's extent, pos in the packed buffer
+
+        explicit FileBatch(EngineBlockDevice& d)
+            : dev(d)
+            , img(d._ds ? d.engine_image() : nullptr)
+        {
+        }
+        // Entry `at` of the call is the file blocks [first, first + count), the bytes `range`.  The engine takes
+        // it unless the loop refuses the range partway (past the file or the tree); then img becomes null.
+        void add(size_t at, const ppfs_ecc_file& file, uint64_t first, size_t count, ppfs_ecc_file_range range = { 0, 0 })
+        {
+            if (!img)
+                return;
+            if (!count || first + count > file_occupied(file, dev._ds) || file_path(first + count - 1, dev._ds / 4).segment > 3)
+                img = nullptr;
+            sel.push_back(Span { at, first, count });
+            files.push_back(file);
+            ranges.push_back(range);
+        }
+        void add_range(size_t at, const ppfs_ecc_file& file, size_t offset, size_t nbytes)
+        {
+            if (img)
+                add(at, file, offset / dev._ds, (offset % dev._ds + nbytes + dev._ds - 1) / dev._ds, ppfs_ecc_file_range { offset, nbytes });
+        }
+        // the plan, then all the trees in one engine call; false when the engine refuses
+        bool walk(bool want_path)
+        {
+            const size_t m = sel.size();
+            slots.resize(m);
+            if (!EccEngine::ok(ppfs_ecc_files_plan(dev._eng.ctx(), files.data(), ranges.data(), m, slots.data(), &tot), "files plan"))
+                return false;
+            own_idx.resize(tot.blocks);
+            idx = own_idx.data();
+            tidx.resize(tot.tree_blocks);
+            tst.resize(tot.tree_blocks);
+            status.assign(tot.blocks, 0);
+            if (want_path)
+                path.resize(tot.blocks);
+            return EccEngine::ok(ppfs_ecc_files_blocks_host(dev._eng.ctx(), img, dev._disk.size() / dev._raw, files.data(),
+                                     ranges.data(), m, idx, want_path ? path.data() : nullptr, tidx.data(), tst.data(), nullptr,
+                                     nullptr, dev._wb),
+                "files blocks");
+        }
+        // the one file through the single-file calls, its blocks into `into` if given
+        bool walk_one(block_index_t* into = nullptr)
+        {
+            const Span& s = sel[0];
+            const long long T = ppfs_ecc_file_tree_blocks(dev._eng.ctx(), &files[0], s.first, s.count);
+            if (T < 0)
+                return false;
+            own_idx.resize(into ? 0 : s.count);
+            idx = into ? into : own_idx.data();
+            tidx.resize((size_t)T);
+            tst.resize((size_t)T);
+            path.resize(s.count);
+            status.assign(s.count, 0);
+            if (!EccEngine::ok(ppfs_ecc_file_blocks_host(dev._eng.ctx(), img, dev._disk.size() / dev._raw, &files[0], s.first, s.count,
+                                   idx, path.data(), tidx.data(), tst.data(), nullptr, dev._wb),
+                    "file blocks"))
+                return false;
+            // its tree entries lie level after level, as many per level as the walk below expects
+            std::vector<uint64_t> under[3];
+            dev.file_tree_under(s.first, s.count, under);
+            slots.assign(1, ppfs_ecc_files_slot {});
+            size_t k = 0;
+            for (int d = 0; d < 3; ++d) {
+                slots[0].tree_pos[d] = k;
+                slots[0].tree_n[d] = under[d].size();
+                k += under[d].size();
             }
-        return k == (size_t)T;
-    }
+            return k == (size_t)T;
+        }
+        // One ppfs_ecc_read_extents_host over the blocks whose path held, file k's bytes at out + its out_pos;
+        // their statuses go to `status`.  false when the engine refuses.
+        bool read_extents(uint8_t* out, size_t out_bytes, const char* what)
+        {
+            for (size_t k = 0; k < sel.size(); ++k)
+                for (ppfs_ecc_extent e : file_extents(idx + slots[k].block_pos, sel[k].count, ranges[k].offset % dev._ds, ranges[k].nbytes, dev._ds)) {
+                    e.pos += slots[k].out_pos;
+                    all.push_back(e);
+                }
+            if (all.size() != status.size()) // one extent per block of the walk
+                return false;
+            std::vector<ppfs_ecc_extent> live;
+            std::vector<size_t> live_at;
+            for (size_t i = 0; i < all.size(); ++i)
+                if (!path[i]) {
+                    live.push_back(all[i]);
+                    live_at.push_back(i);
+                }
+            if (live.empty())
+                return true;
+            std::vector<uint8_t> st(live.size());
+            if (!EccEngine::ok(ppfs_ecc_read_extents_host(dev._eng.ctx(), img, dev._disk.size() / dev._raw, live.data(), live.size(), out,
+                                   out_bytes, st.data(), dev._wb),
+                    what))
+                return false;
+            for (size_t k = 0; k < live.size(); ++k)
+                status[live_at[k]] = st[k];
+            return true;
+        }
+        // File k's corrected blocks, logged in the loop's order: an index block immediately before the first
+        // requested file block under it, outer levels first, then that block itself.
+        void log(size_t k)
+        {
+            const Span& s = sel[k];
+            const ppfs_ecc_files_slot& t = slots[k];
+            std::vector<FileEvent> events;
+            std::vector<uint64_t> under[3];
+            dev.file_tree_under(s.first, s.count, under);
+            for (int d = 0; d < 3; ++d)
+                for (size_t i = 0; i < under[d].size() && i < t.tree_n[d]; ++i)
+                    if (tst[t.tree_pos[d] + i] == PPFS_ECC_CORRECTED)
+                        events.push_back(FileEvent { under[d][i], d, tidx[t.tree_pos[d] + i] });
+            for (size_t i = 0; i < s.count; ++i)
+                if (status[t.block_pos + i] == PPFS_ECC_CORRECTED)
+                    events.push_back(FileEvent { s.first + i, 3, idx[t.block_pos + i] });
+            std::stable_sort(events.begin(), events.end(),
+                [](const FileEvent& a, const FileEvent& b) { return a.at != b.at ? a.at < b.at : a.level < b.level; });
+            for (const FileEvent& e : events)
+                dev.log(e.block);
+        }
+        // File k's first failing block, counted from its first, and that block's error (its path's, else its own)
+        // in e; its count and 0 when none fails.
+        size_t first_failure(size_t k, uint8_t& e) const
+        {
+            for (size_t i = 0; i < sel[k].count; ++i) {
+                const size_t at = slots[k].block_pos + i;
+                e = !path.empty() && path[at] ? path[at] : status_error(status[at]);
+                if (e)
+                    return i;
+            }
+            e = 0;
+            return sel[k].count;
+        }
+        // the bytes of file k that lie before its block i (after read_extents)
+        size_t delivered(size_t k, size_t i) const
+        {
+            return i < sel[k].count ? (size_t)(all[slots[k].block_pos + i].pos - slots[k].out_pos) : (size_t)ranges[k].nbytes;
+        }
+    };
 
     EngineBlockDevice(IDisk& disk, std::shared_ptr<Logger> logger, uint32_t type, uint32_t bs, uint32_t t,
         uint64_t poly, int device, const char* log_name)
         : _disk(disk)
         , _logger(std::move(logger))
         , _type(type)
+        , _wb(type == PPFS_ECC_REED_SOLOMON || type == PPFS_ECC_HAMMING ? 1 : 0)
         , _eng(type, bs, t, poly, device)
         , _raw(_eng.raw())
         , _ds(_eng.data())
@@ -2094,22 +2019,6 @@ protected:
     {
     }
 
-    // an extent call's statuses as the per-block calls report them: FsError per entry, a correction
-    // event per status 1, in list order
-    void extent_errors(const ppfs_ecc_extent* ext, size_t n, const uint8_t* status, uint8_t* err)
-    {
-        for (size_t i = 0; i < n; ++i) {
-            uint8_t e = 0;
-            if (status[i] == PPFS_ECC_OUT_OF_BOUNDS)
-                e = (uint8_t)FsError::Disk_OutOfBounds;
-            else if (status[i] == PPFS_ECC_CORRECTION_ERROR)
-                e = (uint8_t)FsError::BlockDevice_CorrectionError;
-            else if (status[i] == PPFS_ECC_CORRECTED)
-                log(ext[i].block);
-            if (err)
-                err[i] = e;
-        }
-    }
     bool has_spill() const { return _type == PPFS_ECC_REED_SOLOMON && _raw > 0 && _raw < 255; }
     size_t spill_stride() const { return 256 - std::min<size_t>(_raw, 255); }
 
@@ -2135,6 +2044,42 @@ protected:
             if (!detail::disk_read(_disk, (size_t)idx[pos[j]] * _raw, _raw, rows.data() + j * _raw))
                 return false;
         return true;
+    }
+    // A list on a disk without a mapping, for readBlockList and writeBlockList.  Each stretch without a repeated
+    // index: its rows read from the disk; per_block(i, n), the per-block loop over the entries [i, i + n), for
+    // the whole stretch when a row could not be read and else for its entries off the disk; then packed(pos,
+    // rows), the call's one contiguous engine call on the packed rows and its epilogue per row in list order,
+    // false when the engine refuses.  A shortened RS code and a device without an engine take the per-block loop.
+    template <class PerBlock, class Packed>
+    expected<void> list_unmapped(const block_index_t* idx, size_t count, PerBlock per_block, Packed packed)
+    {
+        if (has_spill() || !_raw)
+            return per_block(0, count);
+        std::vector<uint8_t> raw;
+        std::vector<size_t> pos;
+        for (size_t s = 0; s < count;) {
+            const size_t e = list_run_end(idx, count, s);
+            if (!list_rows(idx, s, e, pos, raw)) { // a row could not be read: block by block
+                auto r = per_block(s, e - s);
+                if (!r)
+                    return r;
+                s = e;
+                continue;
+            }
+            for (size_t i = s, j = 0; i < e; ++i) { // off the disk: the per-block call's error
+                if (j < pos.size() && pos[j] == i) {
+                    ++j;
+                    continue;
+                }
+                auto r = per_block(i, 1);
+                if (!r)
+                    return r;
+            }
+            if (!pos.empty() && !packed(pos, raw))
+                return unexpected(FsError::Disk_IOError);
+            s = e;
+        }
+        return {};
     }
 
     void log(block_index_t b)
@@ -2178,14 +2123,13 @@ protected:
         uint8_t status = 0;
         if (has_spill())
             spill.assign(spill_stride(), 0);
-        const int wb = (_type == PPFS_ECC_REED_SOLOMON || _type == PPFS_ECC_HAMMING) ? 1 : 0;
-        if (!EccEngine::ok(ppfs_ecc_decode_host(_eng.ctx(), fixed.data(), dec, &status, 1, wb,
+        if (!EccEngine::ok(ppfs_ecc_decode_host(_eng.ctx(), fixed.data(), dec, &status, 1, _wb,
                                spill.empty() ? nullptr : spill.data()),
                 "decode"))
             return unexpected(FsError::Disk_IOError);
         if (status == PPFS_ECC_CORRECTION_ERROR)
             return unexpected(FsError::BlockDevice_CorrectionError);
-        if (status == PPFS_ECC_CORRECTED && wb) {
+        if (status == PPFS_ECC_CORRECTED && _wb) {
             auto w = write_back(b, raw, fixed.data(), spill.empty() ? nullptr : spill.data());
             if (!w)
                 return w;
@@ -2197,6 +2141,7 @@ protected:
     IDisk& _disk;
     std::shared_ptr<Logger> _logger;
     uint32_t _type;
+    const int _wb; // the engine calls' write_back: RS and Hamming write a corrected block back, CRC and parity only detect
     EccEngine _eng;
     size_t _raw, _ds;
     const char* _log_name;

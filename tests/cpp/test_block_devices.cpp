@@ -589,6 +589,119 @@ TEST(Differential, ReadBlocksStraddlingDiskEnd)
     }
 }
 
+// readBlocks / writeBlocks / scrub with every optional output null (err, counts) == the per-block loop:
+// payloads (zeros for a failed block), the disk image and the log in order.  The disk is 8 blocks, one
+// with a single flipped bit and one damaged past what the codec corrects, so the calls meet the
+// statuses ok, corrected and failed with nowhere to report them.
+struct SmallDisk : public IDisk { // sized once the device has said its raw block size
+    std::vector<uint8_t> bytes;
+    bool map;
+    explicit SmallDisk(bool m)
+        : map(m)
+    {
+    }
+    expected<void> read(size_t address, size_t size, static_vector<uint8_t>& data) override
+    {
+        if (address + size > bytes.size())
+            return unexpected(FsError::Disk_OutOfBounds);
+        if (data.capacity() < size)
+            return unexpected(FsError::Disk_InvalidRequest);
+        data.resize(size);
+        std::memcpy(data.data(), bytes.data() + address, size);
+        return {};
+    }
+    expected<size_t> write(size_t address, const static_vector<uint8_t>& data) override
+    {
+        if (address + data.size() > bytes.size())
+            return unexpected(FsError::Disk_OutOfBounds);
+        std::memcpy(bytes.data() + address, data.data(), data.size());
+        return data.size();
+    }
+    size_t size() override { return bytes.size(); }
+    uint8_t* mapped() override { return map ? bytes.data() : nullptr; }
+};
+
+static void null_outputs(const Cfg& c, bool map)
+{
+    constexpr size_t NB = 8;
+    SmallDisk disk(map);
+    auto lg = std::make_shared<Logger>();
+    auto dev = make_dev(c, disk, lg);
+    const size_t raw = dev->rawBlockSize(), ds = dev->dataSize();
+    ASSERT_TRUE(raw > 0);
+    disk.bytes.assign(NB * raw, 0);
+    std::vector<uint8_t> odisk(NB * raw, 0);
+    std::vector<int32_t> olog(1 << 8);
+    void* od = oracle_dev_create(c.type, c.bs, c.t, c.poly, odisk.data(), odisk.size(), olog.data(), olog.size());
+    std::mt19937_64 rng(4242 + (uint64_t)c.type);
+    auto same = [&]() {
+        if (std::memcmp(disk.bytes.data(), odisk.data(), odisk.size()) != 0 || lg->events.size() != oracle_dev_log_len(od))
+            return false;
+        for (size_t i = 0; i < lg->events.size(); ++i)
+            if ((int32_t)lg->events[i].block_index != olog[i])
+                return false;
+        return true;
+    };
+    std::vector<uint8_t> pl(NB * ds + 1), out(NB * ds + 1, 0xEE), obuf(4096), zeros(ds + 1, 0);
+    for (size_t b = 0; b < NB; ++b) {
+        EXPECT_TRUE(dev->formatBlock((unsigned)b).has_value());
+        oracle_dev_format(od, (unsigned)b);
+        for (size_t i = 0; i < ds; ++i)
+            pl[b * ds + i] = (uint8_t)rng();
+        static_vector<uint8_t> v(pl.data() + b * ds, ds, ds);
+        EXPECT_TRUE(dev->writeBlock(v, DataLocation((int)b, 0)).has_value());
+        size_t ow = 0;
+        oracle_dev_write(od, (int)b, 0, pl.data() + b * ds, ds, &ow);
+    }
+    EXPECT_TRUE(same());
+    // block 2: one bit; block 5: t + 2 bytes of an RS block, two bits of the others', in distinct bytes
+    std::vector<uint8_t> bad = disk.bytes;
+    bad[2 * raw + rng() % raw] ^= (uint8_t)(1u << (rng() % 8));
+    const size_t nbad = std::min<size_t>(raw, c.type == PPFS_ECC_REED_SOLOMON ? (size_t)c.t + 2 : 2);
+    for (size_t k = 0; k < nbad; ++k)
+        bad[5 * raw + k * (raw / nbad)] ^= c.type == PPFS_ECC_REED_SOLOMON ? (uint8_t)(1 + rng() % 255) : (uint8_t)(1u << (rng() % 8));
+    auto damaged = [&]() {
+        disk.bytes = bad;
+        odisk = bad;
+    };
+    auto loop_reads = [&](const uint8_t* got) { // readBlock of every block on the model; got: the payloads to compare
+        for (size_t i = 0; i < NB; ++i) {
+            size_t olen = 0;
+            const int orr = oracle_dev_read(od, (int)i, 0, ds, 4096, obuf.data(), &olen);
+            if (got)
+                EXPECT_TRUE(std::memcmp(got + i * ds, orr == 0 ? obuf.data() : zeros.data(), ds) == 0);
+        }
+    };
+    damaged();
+    EXPECT_TRUE(dev->readBlocks(0, NB, out.data(), nullptr).has_value());
+    loop_reads(out.data());
+    EXPECT_TRUE(same());
+
+    damaged();
+    for (size_t i = 0; i < NB * ds; ++i)
+        pl[i] = (uint8_t)rng();
+    EXPECT_TRUE(dev->writeBlocks(0, NB, pl.data(), nullptr).has_value());
+    for (size_t i = 0; i < NB; ++i) {
+        size_t ow = 0;
+        oracle_dev_write(od, (int)i, 0, pl.data() + i * ds, ds, &ow);
+    }
+    EXPECT_TRUE(same());
+
+    damaged();
+    EXPECT_TRUE(dev->scrub(0, NB, nullptr, nullptr).has_value());
+    loop_reads(nullptr);
+    EXPECT_TRUE(same());
+    oracle_dev_destroy(od);
+}
+
+TEST(Differential, BatchCallsWithoutOptionalOutputs)
+{
+    for (const Cfg& c : kCfgs) {
+        null_outputs(c, true);
+        null_outputs(c, false);
+    }
+}
+
 // An engine error reaches the caller as FsError::Disk_IOError (no throw, no abort): here the
 // engine cannot be created at all (no such device), so every call of the device fails that way.
 TEST(EngineErrors, PropagateAsDiskIOError)

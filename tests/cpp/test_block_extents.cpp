@@ -209,6 +209,63 @@ static void run_extents(Pair& p, std::mt19937& rng)
     }
 }
 
+// writeExtents with err == nullptr == the per-block loop: the disk image and the log in order.  The disk is
+// 8 blocks, mapped or not, one with a single flipped bit and one damaged past what the codec corrects; the
+// batch adds a block past the disk and a block named twice, so the call meets ok, corrected, failed and out of
+// bounds with nowhere to report them.
+class SmallDisk : public PlainDisk {
+public:
+    SmallDisk(size_t n, bool map) : PlainDisk(n), _map(map) {}
+    uint8_t* mapped() override { return _map ? bytes() : nullptr; }
+
+private:
+    bool _map;
+};
+
+static void run_null_outputs(const std::string& name, const MakeDevice& make, size_t raw)
+{
+    constexpr size_t NB = 8;
+    std::mt19937 rng(20241019 + (unsigned)raw); // its own: the other cases' draws stay what they were
+    const bool rs = name.compare(0, 2, "rs") == 0, corrects = rs || name.compare(0, 7, "hamming") == 0;
+    for (bool map : { true, false }) {
+        g_case = name + (map ? "/null-outputs/mapped" : "/null-outputs/plain");
+        SmallDisk da(NB * raw, map), db(NB * raw, map);
+        auto la = std::make_shared<Logger>(), lb = std::make_shared<Logger>();
+        auto a = make(da, la), b = make(db, lb);
+        const size_t ds = a->dataSize();
+        std::vector<uint8_t> payloads(NB * ds), err(NB);
+        for (auto& x : payloads)
+            x = (uint8_t)rng();
+        EXPECT_TRUE((bool)a->writeBlocks(0, NB, payloads.data(), err.data()));
+        da.bytes()[2 * raw + rng() % raw] ^= (uint8_t)(1u << (rng() % 8));
+        const size_t nbad = rs ? 5 : 2; // distinct bytes: past t = 3, past one bit
+        for (size_t k = 0; k < nbad; ++k)
+            da.bytes()[5 * raw + k * (raw / nbad)] ^= (uint8_t)(1u << (rng() % 8));
+        std::memcpy(db.bytes(), da.bytes(), NB * raw);
+        la->events.clear();
+
+        const uint16_t len = (uint16_t)std::min<size_t>(ds, 4), off = (uint16_t)std::min<size_t>(1, ds - 1);
+        std::vector<ppfs_ecc_extent> ext;
+        for (block_index_t blk : { 4u, 2u, (block_index_t)a->numOfBlocks(), 5u, 2u, 0u })
+            ext.push_back(ppfs_ecc_extent { (uint64_t)ext.size() * 4, blk, ext.size() % 2 ? off : (uint16_t)0, len });
+        std::vector<uint8_t> fresh(ext.size() * 4);
+        for (auto& x : fresh)
+            x = (uint8_t)rng();
+        EXPECT_TRUE((bool)a->writeExtents(ext.data(), ext.size(), fresh.data(), fresh.size(), nullptr));
+        size_t failed = 0;
+        for (const ppfs_ecc_extent& x : ext) {
+            const size_t n = std::min<size_t>(x.length, ds - x.offset);
+            static_vector<uint8_t> v(fresh.data() + x.pos, n, n);
+            failed += !b->writeBlock(v, DataLocation((int)x.block, x.offset));
+        }
+        EXPECT_TRUE(std::memcmp(da.bytes(), db.bytes(), NB * raw) == 0);
+        EXPECT_TRUE(same_log(*la, *lb));
+        // off the disk, and the damage -- except for RS, which never fails a block: it logs what its decoder made of it
+        EXPECT_TRUE(failed >= (rs || name == "raw255" ? 1u : 2u));
+        EXPECT_TRUE(!corrects || lb->events.size() >= 1);
+    }
+}
+
 int main()
 {
     const std::vector<std::pair<const char*, MakeDevice>> codecs = {
@@ -244,6 +301,8 @@ int main()
             for (int k = 0; k < 2; ++k)
                 p.dev[k] = make(*p.disk[k], p.log[k]);
             run_extents(p, rng);
+            if (kind[0] == 's' && p.dev[0]->rawBlockSize()) // once per codec, on 8-block disks of its own
+                run_null_outputs(name, make, p.dev[0]->rawBlockSize());
             p.dev[0].reset(); // devices before their disks
             p.dev[1].reset();
         }

@@ -211,6 +211,71 @@ static void run_lists(Pair& p, std::mt19937& rng)
     }
 }
 
+// scrubList / scrubAllocated with counts, err and bitmap_err null == the per-block loop: the disk image and
+// the log in order.  The disk is 8 blocks, mapped or not: the bitmap in block 0, blocks 1..7 its bits, one
+// allocated block with a single flipped bit and one damaged past what the codec corrects; the list adds an
+// index past the disk and a repeated one, so the calls meet ok, corrected, failed, out of bounds and not
+// allocated with nowhere to report them.
+class SmallDisk : public PlainDisk {
+public:
+    SmallDisk(size_t n, bool map) : PlainDisk(n), _map(map) {}
+    uint8_t* mapped() override { return _map ? bytes() : nullptr; }
+
+private:
+    bool _map;
+};
+
+static void run_null_outputs(const std::string& name, const MakeDevice& make, size_t raw)
+{
+    constexpr size_t NB = 8;
+    std::mt19937 rng(20240611 + (unsigned)raw); // its own: the other cases' draws stay what they were
+    const bool rs = name.compare(0, 2, "rs") == 0, corrects = rs || name.compare(0, 7, "hamming") == 0;
+    for (bool map : { true, false }) {
+        g_case = name + (map ? "/null-outputs/mapped" : "/null-outputs/plain");
+        SmallDisk da(NB * raw, map), db(NB * raw, map);
+        auto la = std::make_shared<Logger>(), lb = std::make_shared<Logger>();
+        auto a = make(da, la), b = make(db, lb);
+        const size_t ds = a->dataSize();
+        std::vector<uint8_t> payloads(NB * ds, 0), err(NB), one(ds);
+        for (size_t i = ds; i < payloads.size(); ++i)
+            payloads[i] = (uint8_t)rng();
+        payloads[0] = 0xDA; // bits 0, 1, 3, 4 and 6 set: blocks 1, 2, 4, 5 and 7 are allocated
+        EXPECT_TRUE((bool)a->writeBlocks(0, NB, payloads.data(), err.data()));
+        std::vector<uint8_t> bad(da.bytes(), da.bytes() + NB * raw);
+        bad[2 * raw + rng() % raw] ^= (uint8_t)(1u << (rng() % 8));
+        const size_t nbad = rs ? 5 : 2; // distinct bytes: past t = 3, past one bit
+        for (size_t k = 0; k < nbad; ++k)
+            bad[5 * raw + k * (raw / nbad)] ^= (uint8_t)(1u << (rng() % 8));
+        auto damaged = [&]() {
+            std::memcpy(da.bytes(), bad.data(), bad.size());
+            std::memcpy(db.bytes(), bad.data(), bad.size());
+            la->events.clear();
+            lb->events.clear();
+        };
+
+        damaged();
+        const std::vector<block_index_t> ix = { 4, 2, (block_index_t)a->numOfBlocks(), 5, 2, 0 };
+        EXPECT_TRUE((bool)a->scrubList(ix.data(), ix.size(), nullptr, nullptr));
+        size_t failed = 0;
+        for (block_index_t blk : ix)
+            failed += read_one(*b, blk, one) != 0;
+        EXPECT_TRUE(std::memcmp(da.bytes(), db.bytes(), NB * raw) == 0);
+        EXPECT_TRUE(same_log(*la, *lb));
+        // off the disk, and the damage -- except for RS, which never fails a block: it logs what its decoder made of it
+        EXPECT_TRUE(failed >= (rs || name == "raw255" ? 1u : 2u));
+        EXPECT_TRUE(!corrects || lb->events.size() >= 1);
+
+        damaged();
+        EXPECT_TRUE((bool)a->scrubAllocated(0, 1, NB - 1, nullptr, nullptr, nullptr));
+        EXPECT_TRUE(read_one(*b, 0, one) == 0 && one[0] == 0xDA); // the bitmap's block, then its set bits' blocks
+        for (block_index_t blk : { 1, 2, 4, 5, 7 })
+            (void)read_one(*b, blk, one);
+        EXPECT_TRUE(std::memcmp(da.bytes(), db.bytes(), NB * raw) == 0);
+        EXPECT_TRUE(same_log(*la, *lb));
+        EXPECT_TRUE(!corrects || lb->events.size() >= 1);
+    }
+}
+
 int main(int argc, char** argv)
 {
     const std::string dir = argc > 1 ? argv[1] : ".";
@@ -253,6 +318,8 @@ int main(int argc, char** argv)
             for (int k = 0; k < 2; ++k)
                 p.dev[k] = make(*p.disk[k], p.log[k]);
             run_lists(p, rng);
+            if (kind[0] == 's' && p.dev[0]->rawBlockSize()) // once per codec, on 8-block disks of its own
+                run_null_outputs(name, make, p.dev[0]->rawBlockSize());
             p.dev[0].reset(); // devices before their disks
             p.dev[1].reset();
         }
