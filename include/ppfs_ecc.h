@@ -720,6 +720,50 @@ int ppfs_ecc_read_inodes_host(ppfs_ecc_ctx* ctx, uint8_t* image, size_t image_bl
     uint8_t* piece_status, ppfs_ecc_inode_counts* counts, int write_back);
 
 /*
+ * Write inodes into the inode table: a batch of updates per call, the mirror of
+ * ppfs_ecc_read_inodes_*.  InodeManager::update (lib/inode_manager/src/inode_manager.cpp:142-159) is one Bitmap::getBit
+ * and _writeInode (:20-54), one writeBlock per piece of the 81 bytes.  ppfs_ecc_write_inodes_* is the per-inode loop
+ * update(ino[j], inode[j]) for j = 0 .. n-1 in the calls' batch form.  Engine extension.
+ *
+ * table, ino, ino_stride, status, piece_status (1 + K(ds) slots per inode) and counts keep the meaning, the alignment
+ * rules and the error rules of the reads.  files and meta are inputs, both required: inode j's 81 bytes on disk are
+ * meta[j].time_creation, meta[j].time_modified, the 64 bytes of files[j], meta[j].type; meta[j].pad is not looked at.
+ * Status of inode j.  Steps 1 and 2 are the reads': a number at or past total_inodes gives 9; with check_bitmap a
+ * bitmap read status of 5 or 9 stands and a set bit gives PPFS_ECC_NOT_ALLOCATED, and nothing of that inode is
+ * written.  Otherwise steps 3 and 4 run over the WRITE statuses of its pieces (ppfs_ecc_write_extents_*): the first
+ * piece with 5 or 9 gives that status, else 1 if the bitmap byte or a piece reported 1, else 0.
+ * What lands.  A table block whose old contents fail their check (5) stays untouched; one at or past image_blocks
+ * gives 9.  Every other block touched ends holding its old payload, corrected, with the bytes of every batch inode
+ * that passed steps 1-2 replaced, and the bits the codec leaves undefined kept.
+ * The one deviation from the loop is ppfs_ecc_write_files_*'s: every piece of an inode that passed steps 1-2 is
+ * written, where the loop stops an inode at its first failing piece.
+ * Repeats are the norm and exact for the table.  Where several entries touch one table block the result is the
+ * loop's in batch order: all their bytes land; where one number appears twice the later entry's bytes win; a
+ * corrected block reports 1 at its first toucher -- the lowest entry, within it the lowest piece -- and 0 at every
+ * later one, in both forms.  The bitmap byte is read as by ppfs_ecc_read_inodes_*: write_back applies to it and the
+ * device form follows the repeat rule of ppfs_ecc_read_extents_device.  piece_status slot 0 is the bitmap byte's read
+ * status, slots 1 .. pieces the pieces' write statuses under the first toucher rule, 255 in every slot that is
+ * unused or was never attempted.
+ * Errors: the -EINVAL set of the reads, before anything touches the GPU, and a null files or meta with n > 0.
+ * n == 0 returns 0 with zeroed counts.  A capturing stream gets PPFS_ECC_ENOTSUP.  Shortened RS is written as
+ * ppfs_ecc_write_extents_* writes it.
+ * Device form: never synchronises, reads nothing back, allocates nothing on the caller's stream; its scratch is the
+ * context's scrub scratch.  Per piece (as the reads', and never more slots than one piece of the extent calls):
+ * bitmap extents kernel, ppfs_ecc_read_extents_device (with check_bitmap), election tables cleared, elect kernel,
+ * extents kernel (one valid extent of length 0 per distinct block), the extent write with the overlay kernel between
+ * "old payloads" and "write", status kernel.
+ * Host form: the same plan on the CPU, the blocks grouped with a map: one ppfs_ecc_read_extents_host of the bitmap
+ * bytes, one of the per-block hulls of the batch's bytes (without write-back), one ppfs_ecc_write_extents_host with
+ * one entry per distinct block.
+ */
+int ppfs_ecc_write_inodes_device(ppfs_ecc_ctx* ctx, uint8_t* d_image, size_t image_blocks, const ppfs_ecc_inode_table* table,
+    const void* d_ino, size_t ino_stride, size_t n, const ppfs_ecc_file* d_files, const ppfs_ecc_inode_meta* d_meta,
+    uint8_t* d_status, uint8_t* d_piece_status, ppfs_ecc_inode_counts* d_counts, int write_back, void* stream);
+int ppfs_ecc_write_inodes_host(ppfs_ecc_ctx* ctx, uint8_t* image, size_t image_blocks, const ppfs_ecc_inode_table* table,
+    const void* ino, size_t ino_stride, size_t n, const ppfs_ecc_file* files, const ppfs_ecc_inode_meta* meta, uint8_t* status,
+    uint8_t* piece_status, ppfs_ecc_inode_counts* counts, int write_back);
+
+/*
  * 2-of-3 bitwise majority of nrec replicated records of rec_bytes each, replacing
  * SuperBlockManager::_performBitVoting (lib/super_block_manager/src/super_block_manager.cpp:133-165):
  *   out[i] = majority(a[i], b[i], c[i]) bit by bit;

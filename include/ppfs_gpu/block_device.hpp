@@ -47,8 +47,9 @@
  * Every one of those overrides in EngineBlockDevice is built from the same few steps, each of which exists once:
  * _wb (the engine calls' write_back flag), engine_image() (the mapped image, or null, for a batch engine call),
  * status_error() / report() (engine statuses as per-entry FsError bytes, correction events and zeroed payloads),
- * list_unmapped() (the list calls on a disk without a mapping) and FileBatch (the file calls' selection, plan and
- * tree walk, and each file's events and first failing block).  The comment above each override states its one
+ * list_unmapped() (the list calls on a disk without a mapping), FileBatch (the file calls' selection, plan and
+ * tree walk, and each file's events and first failing block) and inode_ok() / inode_log() (an inode call's statuses
+ * as the loop's results, and its correction log from piece_status, for readInodes and writeInodes).  The comment above each override states its one
  * deviation from the per-block loop, which defines it.
  */
 #include <algorithm>
@@ -957,6 +958,71 @@ public:
         }
     }
 
+    // The mirror (ppfs_ecc.h ppfs_ecc_write_inodes_*): n inodes written into one inode table in one call -- what
+    // follows a batch of file writes.  By definition the per-inode loop, InodeManager::update (inode_manager.cpp:
+    // 142-159): Bitmap::getBit as above, then _writeInode (:20-54), the 81 packed bytes cut at block boundaries by a
+    // clamping writeBlock.  The first error ends that inode.  The codecs write the whole batch in one engine call.
+    struct InodeWrite {
+        bool ok;
+        FsError error; // meaningful unless ok (Bitmap_IndexOutOfRange is FsError 0)
+    };
+    expected<void> writeInode(const InodeTable& table, uint32_t index, const PackedInode& inode)
+    {
+        const size_t ds = dataSize(), size = sizeof(PackedInode);
+        uint8_t* data = const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(&inode)); // static_vector only reads it
+        size_t bytes_written = 0;
+        DataLocation start((int)(table.table_block + (uint64_t)index * size / ds), (size_t)((uint64_t)index * size % ds));
+        if (ds - start.offset < size) { // does not fit in one block: the unaligned part first
+            static_vector<uint8_t> v(data, size, size);
+            auto r = writeBlock(v, start);
+            if (!r)
+                return unexpected(r.error());
+            bytes_written += *r;
+            start.offset = 0;
+            start.block_index++;
+        }
+        while (bytes_written < size) {
+            const size_t bytes_left = size - bytes_written;
+            static_vector<uint8_t> v(data + bytes_written, bytes_left, bytes_left);
+            auto r = writeBlock(v, start);
+            if (!r)
+                return unexpected(r.error());
+            start.block_index++;
+            bytes_written += *r;
+        }
+        return {};
+    }
+    virtual void writeInodes(const InodeTable& table, const uint32_t* numbers, size_t n, const PackedInode* inodes, InodeWrite* out)
+    {
+        for (size_t j = 0; j < n; ++j) {
+            InodeWrite& r = out[j];
+            r = InodeWrite {};
+            if (dataSize() == 0) {
+                r.error = FsError::Disk_InvalidRequest;
+                continue;
+            }
+            if (table.check_bitmap) {
+                auto is_free = inodeBit(table, numbers[j]);
+                if (!is_free) {
+                    r.error = is_free.error();
+                    continue;
+                }
+                if (*is_free) {
+                    r.error = FsError::InodeManager_NotFound;
+                    continue;
+                }
+            } else if (numbers[j] >= table.total_inodes) {
+                r.error = FsError::Bitmap_IndexOutOfRange;
+                continue;
+            }
+            auto put = writeInode(table, numbers[j], inodes[j]);
+            if (put)
+                r.ok = true;
+            else
+                r.error = put.error();
+        }
+    }
+
     // Write extension (ppfs_ecc.h ppfs_ecc_write_file_* / ppfs_ecc_write_files_*): the in-place case of
     // FileIO::writeFile (file_io.cpp:46-104).  The range must lie inside the file as the inode describes it --
     // offset + n <= file_size, else FileIO_OutOfBounds as readFile reports a range past the end; nothing is
@@ -1175,6 +1241,51 @@ protected:
     // An engine status as the FsError byte the per-block call reports: ok and corrected are no error, and every
     // other status is the FsError's own value (the static_asserts at FsError; 255, not allocated, stays 255).
     static uint8_t status_error(uint8_t status) { return status <= PPFS_ECC_CORRECTED ? 0 : status; }
+
+    // The status of one inode of an inode call as the per-inode loop reports it: true, or false and the FsError --
+    // out of range whatever else the status says, not found for a free inode, else the status' own value.
+    static bool inode_ok(const ppfs_ecc_inode_table& table, uint32_t number, uint8_t status, FsError& error)
+    {
+        if (status <= PPFS_ECC_CORRECTED)
+            return true;
+        error = number >= table.total_inodes     ? FsError::Bitmap_IndexOutOfRange
+            : status == PPFS_ECC_NOT_ALLOCATED ? FsError::InodeManager_NotFound
+                                               : (FsError)status_error(status);
+        return false;
+    }
+
+    // The correction log of an inode call from its piece_status (1 + K slots per inode), as the loop writes it: inodes
+    // in batch order, the bitmap block then the pieces up to the first failing one, each block that some access of
+    // the call corrected logged where the loop first touches it.
+    void inode_log(const ppfs_ecc_inode_table& table, const uint32_t* numbers, size_t n, const uint8_t* pieces)
+    {
+        const size_t K = 2 + 79 / _ds, W = 1 + K;
+        // the accesses the loop makes for inode j, in its order: fn(block, status) until it returns false
+        auto touches_of = [&](size_t j, auto fn) {
+            const uint8_t* ps = pieces + j * W;
+            const uint64_t i = numbers[j];
+            if (ps[0] != 255 && !fn((uint64_t)table.bitmap_block + (i / 8) / _ds, ps[0]))
+                return;
+            for (size_t k = 0; k < K && ps[1 + k] != 255; ++k)
+                if (!fn((uint64_t)table.table_block + 81 * i / _ds + k, ps[1 + k]))
+                    return;
+        };
+        std::unordered_set<uint64_t> corrected, logged;
+        for (size_t j = 0; j < n; ++j)
+            touches_of(j, [&](uint64_t b, uint8_t st) {
+                if (st == PPFS_ECC_CORRECTED)
+                    corrected.insert(b);
+                return true;
+            });
+        for (size_t j = 0; j < n; ++j)
+            touches_of(j, [&](uint64_t b, uint8_t st) {
+                if (st == PPFS_ECC_CORRECTION_ERROR || st == PPFS_ECC_OUT_OF_BOUNDS)
+                    return false;
+                if (corrected.count(b) && logged.insert(b).second)
+                    log((block_index_t)b);
+                return true;
+            });
+    }
 
     // The n statuses of an engine call as the per-block calls report them, in entry order: a correction event
     // for every status 1 at block_of(i), err[i] (err may be null) 0 or the error, and, with `payloads`, zeros
@@ -1699,7 +1810,7 @@ public:
         uint8_t* img = engine_image();
         if (!img || !_ds || _ds > 0xFFFFu || !n)
             return IBlockDevice::readInodes(table, numbers, n, out);
-        const size_t K = 2 + 79 / _ds, W = 1 + K;
+        const size_t W = 1 + (2 + 79 / _ds);
         std::vector<ppfs_ecc_file> files(n);
         std::vector<ppfs_ecc_inode_meta> meta(n);
         std::vector<uint8_t> status(n), pieces(n * W);
@@ -1712,47 +1823,47 @@ public:
             }
             return;
         }
-        // the reads the loop makes for inode j, in its order: fn(block, status) until it returns false
-        auto reads_of = [&](size_t j, auto fn) {
-            const uint8_t* ps = pieces.data() + j * W;
-            const uint64_t i = numbers[j];
-            if (ps[0] != 255 && !fn((uint64_t)table.bitmap_block + (i / 8) / _ds, ps[0]))
-                return;
-            for (size_t k = 0; k < K && ps[1 + k] != 255; ++k)
-                if (!fn((uint64_t)table.table_block + 81 * i / _ds + k, ps[1 + k]))
-                    return;
-        };
-        std::unordered_set<uint64_t> corrected, logged;
-        for (size_t j = 0; j < n; ++j)
-            reads_of(j, [&](uint64_t b, uint8_t st) {
-                if (st == PPFS_ECC_CORRECTED)
-                    corrected.insert(b);
-                return true;
-            });
+        inode_log(table, numbers, n, pieces.data());
         for (size_t j = 0; j < n; ++j) {
-            reads_of(j, [&](uint64_t b, uint8_t st) {
-                if (st == PPFS_ECC_CORRECTION_ERROR || st == PPFS_ECC_OUT_OF_BOUNDS)
-                    return false;
-                if (corrected.count(b) && logged.insert(b).second)
-                    log((block_index_t)b);
-                return true;
-            });
             InodeRead& r = out[j];
             r = InodeRead {};
-            const uint8_t st = status[j];
-            if (st == PPFS_ECC_OK || st == PPFS_ECC_CORRECTED) {
-                r.ok = true;
-                r.inode.time_creation = meta[j].time_creation;
-                r.inode.time_modified = meta[j].time_modified;
-                r.inode.file = files[j];
-                r.inode.type = meta[j].type;
-            } else if (numbers[j] >= table.total_inodes) {
-                r.error = FsError::Bitmap_IndexOutOfRange;
-            } else if (st == PPFS_ECC_NOT_ALLOCATED) {
-                r.error = FsError::InodeManager_NotFound;
-            } else {
-                r.error = (FsError)st; // 5 and 9 are BlockDevice_CorrectionError and Disk_OutOfBounds
-            }
+            if (!(r.ok = inode_ok(table, numbers[j], status[j], r.error)))
+                continue;
+            r.inode.time_creation = meta[j].time_creation;
+            r.inode.time_modified = meta[j].time_modified;
+            r.inode.file = files[j];
+            r.inode.type = meta[j].type;
+        }
+    }
+
+    // writeInodes as ONE ppfs_ecc_write_inodes_host on a mapped disk image, from the steps readInodes is made of.
+    // Errors equal the loop's, and so does the log: the first toucher of a corrected block reports it, and the log
+    // replays the loop's order up to each inode's first failing piece.  The pieces behind an inode's failing piece,
+    // which the loop does not write, have been written as well: the one deviation.  Elsewhere, and for a shortened
+    // RS code, the per-inode loop.
+    void writeInodes(const InodeTable& table, const uint32_t* numbers, size_t n, const PackedInode* inodes, InodeWrite* out) override
+    {
+        uint8_t* img = engine_image();
+        if (!img || !_ds || _ds > 0xFFFFu || !n)
+            return IBlockDevice::writeInodes(table, numbers, n, inodes, out);
+        const size_t W = 1 + (2 + 79 / _ds);
+        std::vector<ppfs_ecc_file> files(n);
+        std::vector<ppfs_ecc_inode_meta> meta(n);
+        for (size_t j = 0; j < n; ++j) {
+            files[j] = inodes[j].file;
+            meta[j] = ppfs_ecc_inode_meta { inodes[j].time_creation, inodes[j].time_modified, inodes[j].type, {} };
+        }
+        std::vector<uint8_t> status(n), pieces(n * W);
+        if (!EccEngine::ok(ppfs_ecc_write_inodes_host(_eng.ctx(), img, _disk.size() / _raw, &table, numbers, 4, n, files.data(),
+                               meta.data(), status.data(), pieces.data(), nullptr, _wb),
+                "write inodes")) {
+            std::fill(out, out + n, InodeWrite { false, FsError::Disk_IOError });
+            return;
+        }
+        inode_log(table, numbers, n, pieces.data());
+        for (size_t j = 0; j < n; ++j) {
+            out[j] = InodeWrite {};
+            out[j].ok = inode_ok(table, numbers[j], status[j], out[j].error);
         }
     }
 

@@ -8,7 +8,8 @@ loaded from the in-tree libppfs_ecc.so.  Python pieces:
                              from the 64 bytes of its inode (file_blocks / read_file: the index-block tree
                              is resolved on the GPU), a batch of files (files_blocks / read_files), and the
                              in-place write of a file range or a batch of them (write_file / write_files);
-                             a batch of inodes read out of the inode table (read_inodes)
+                             a batch of inodes read out of the inode table (read_inodes) or written into it
+                             (write_inodes)
   - ecc.EccGroup             the host calls sharded over several GPUs (one thread per device)
   - ecc.vote3 / vote3_host   2-of-3 bitwise voting of replicated records (superblock copies)
   - block_device.*           IBlockDevice mirror (ReedSolomon/Crc/Hamming/Parity/Raw devices)

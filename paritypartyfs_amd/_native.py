@@ -75,6 +75,8 @@ EXPORTED_SYMBOLS = (
     "ppfs_ecc_inode_span",
     "ppfs_ecc_read_inodes_device",
     "ppfs_ecc_read_inodes_host",
+    "ppfs_ecc_write_inodes_device",
+    "ppfs_ecc_write_inodes_host",
     "ppfs_vote3_device",
     "ppfs_vote3_host",
     "ppfs_copy_device",
@@ -326,6 +328,11 @@ def lib() -> ctypes.CDLL:
     L.ppfs_ecc_read_inodes_host.restype = c_int
     L.ppfs_ecc_read_inodes_host.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p,
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_int]
+    # inode writes: the reads' arguments, files and meta inputs
+    L.ppfs_ecc_write_inodes_device.restype = c_int
+    L.ppfs_ecc_write_inodes_device.argtypes = list(L.ppfs_ecc_read_inodes_device.argtypes)
+    L.ppfs_ecc_write_inodes_host.restype = c_int
+    L.ppfs_ecc_write_inodes_host.argtypes = list(L.ppfs_ecc_read_inodes_host.argtypes)
     L.ppfs_vote3_device.restype = c_int
     L.ppfs_vote3_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]
     L.ppfs_copy_device.restype = c_int

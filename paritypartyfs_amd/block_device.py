@@ -505,6 +505,69 @@ class IBlockDevice:
             out.append((np.frombuffer(r.value(), dtype=INODE_DTYPE)[0], None) if r else (None, r.error()))
         return out
 
+    # write inodes into the inode table (include/ppfs_ecc.h ppfs_ecc_write_inodes_*): the arguments of read_inodes, and
+    # per inode its FILE_DTYPE record and its INODE_META_DTYPE record.  The per-inode loop is the definition --
+    # InodeManager::update (inode_manager.cpp:142-159): Bitmap::getBit, then _writeInode (:20-54), the 81 bytes cut at
+    # block boundaries by a clamping writeBlock; the first error ends that inode.  The codecs override it with one
+    # engine call.
+    @staticmethod
+    def _inode_pack(files, meta, n: int) -> np.ndarray:
+        """The n packed Inodes (INODE_DTYPE) of the file records and the metadata; the metadata's padding is not used."""
+        files = np.ascontiguousarray(files).reshape(-1).view(FILE_DTYPE)
+        meta = np.ascontiguousarray(meta).reshape(-1).view(INODE_META_DTYPE)
+        if files.size < n or meta.size < n:
+            raise ValueError("write_inodes: one file record and one metadata record per inode number")
+        rec = np.zeros(n, dtype=INODE_DTYPE)
+        rec["time_creation"], rec["time_modified"], rec["type"] = meta["time_creation"][:n], meta["time_modified"][:n], meta["type"][:n]
+        for name in FILE_DTYPE.names:
+            rec[name] = files[name][:n]
+        return rec
+
+    def _inode_write(self, table_block: int, index: int, inode: bytes) -> Expected[None]:
+        size, ds = INODE_DTYPE.itemsize, self.dataSize()
+        written = 0
+        start = DataLocation(table_block + index * size // ds, index * size % ds)
+        if ds - start.offset < size:  # does not fit in one block: the unaligned part first
+            r = self.writeBlock(inode, start)
+            if not r:
+                return Expected.unexpected(r.error())
+            written += r.value()
+            start = DataLocation(start.block_index + 1, 0)
+        while written < size:
+            r = self.writeBlock(inode[written:], start)
+            if not r:
+                return Expected.unexpected(r.error())
+            written += r.value()
+            start = DataLocation(start.block_index + 1, start.offset)
+        return Expected(None)
+
+    def write_inodes(self, table, numbers, files, meta) -> List[Optional[FsError]]:
+        """InodeManager::update per inode number, in batch order: None or the error.  A set bit of the inode bitmap
+        means free: InodeManager_NotFound, nothing written.  table["check_bitmap"] == 0 skips the bit's read, not the
+        range check."""
+        t = np.asarray(table).reshape(-1)[0]
+        table_block, bitmap_block, total = int(t["table_block"]), int(t["bitmap_block"]), int(t["total_inodes"])
+        if self.dataSize() == 0:
+            raise ValueError("write_inodes: the codec has no payload")
+        nums = [int(x) for x in np.asarray(numbers).reshape(-1)]
+        rec = self._inode_pack(files, meta, len(nums))
+        out = []
+        for j, i in enumerate(nums):
+            if int(t["check_bitmap"]):
+                free = self._inode_get_bit(bitmap_block, total, i)
+                if not free:
+                    out.append(free.error())
+                    continue
+                if free.value():
+                    out.append(FsError.InodeManager_NotFound)
+                    continue
+            elif i >= total:
+                out.append(FsError.Bitmap_IndexOutOfRange)
+                continue
+            r = self._inode_write(table_block, i, rec[j].tobytes())
+            out.append(None if r else r.error())
+        return out
+
 
 
 def file_path_of(j: int, ipb: int):
@@ -1103,6 +1166,60 @@ class _EngineDevice(IBlockDevice):
                 out.append((None, FsError.InodeManager_NotFound))
             else:
                 out.append((None, FsError(st)))
+        return out
+
+    def write_inodes(self, table, numbers, files, meta) -> List[Optional[FsError]]:
+        """IBlockDevice.write_inodes as ONE engine call on the disk image (EccEngine.write_inodes_host).  Errors equal
+        the loop's.  The correction log equals it too: inodes in batch order, the bitmap block then the pieces up to
+        the first failing one, each block that the call corrected logged where the loop first touches it.  The pieces
+        behind an inode's failing piece, which the loop does not write, have been written as well."""
+        image = self._mapped_image()
+        nums = np.ascontiguousarray(np.asarray(numbers).reshape(-1), dtype=np.uint32)
+        if image is None or self._ds == 0 or self._ds > 0xFFFF or nums.size == 0:
+            return super().write_inodes(table, numbers, files, meta)
+        eng, ds = self._engine, self._ds
+        t = np.ascontiguousarray(np.asarray(table).reshape(-1)[:1], dtype=INODE_TABLE_DTYPE)
+        table_block, bitmap_block, total = int(t["table_block"][0]), int(t["bitmap_block"][0]), int(t["total_inodes"][0])
+        n, W = int(nums.size), 1 + eng.inode_max_pieces
+        rec = self._inode_pack(files, meta, n)  # checks the sizes
+        f = np.zeros(n, dtype=FILE_DTYPE)
+        m = np.zeros(n, dtype=INODE_META_DTYPE)
+        for name in FILE_DTYPE.names:
+            f[name] = rec[name]
+        m["time_creation"], m["time_modified"], m["type"] = rec["time_creation"], rec["time_modified"], rec["type"]
+        status, pieces = np.zeros(n, dtype=np.uint8), np.zeros(n * W, dtype=np.uint8)
+        wb = eng.ecc_type in (ECC_REED_SOLOMON, ECC_HAMMING)
+        eng.write_inodes_host(image, t, nums, f, m, status=status, piece_status=pieces, write_back=wb)
+        pieces = pieces.reshape(n, W)
+        touches = []  # per inode: (block, status) of the accesses the loop makes, in its order
+        for j, i in enumerate(int(x) for x in nums):
+            mine = []
+            if pieces[j, 0] != 255:
+                mine.append((bitmap_block + (i // 8) // ds, int(pieces[j, 0])))
+            for k in range(W - 1):
+                if pieces[j, 1 + k] == 255:
+                    break
+                mine.append((table_block + 81 * i // ds + k, int(pieces[j, 1 + k])))
+            touches.append(mine)
+        corrected = {b for mine in touches for b, st in mine if st == STATUS_CORRECTED}
+        logged = set()
+        out = []
+        for j, i in enumerate(int(x) for x in nums):
+            for b, st in touches[j]:
+                if st in (STATUS_CORRECTION_ERROR, STATUS_OUT_OF_BOUNDS):
+                    break
+                if b in corrected and b not in logged:
+                    logged.add(b)
+                    self._log(b)
+            st = int(status[j])
+            if st in (STATUS_OK, STATUS_CORRECTED):
+                out.append(None)
+            elif i >= total:
+                out.append(FsError.Bitmap_IndexOutOfRange)
+            elif st == STATUS_NOT_ALLOCATED:
+                out.append(FsError.InodeManager_NotFound)
+            else:
+                out.append(FsError(st))
         return out
 
     def write_file(self, file, offset: int, data) -> Tuple[int, Optional[FsError]]:

@@ -111,14 +111,14 @@ extern "C" int ppfs_ecc_read_extents_device(ppfs_ecc_ctx* c, uint8_t* d_image, s
     return call.end(r, "read extents (async)");
 }
 
-extern "C" int ppfs_ecc_write_extents_device(ppfs_ecc_ctx* c, const uint8_t* d_in, size_t in_bytes, uint8_t* d_image,
-    size_t image_blocks, const ppfs_ecc_extent* d_ext, size_t n, uint8_t* d_status, void* stream)
+// The write piece loop, its overlay step a parameter (list_call.hpp): between "old payloads" and "write" the caller
+// puts its bytes onto P.  buf_bytes: the packed buffer the entries' pos and length are checked against.
+int ppfs::write_extents_pieces(ppfs_ecc_ctx* c, uint8_t* d_image, size_t image_blocks, const ppfs_ecc_extent* d_ext, size_t n,
+    size_t buf_bytes, uint8_t* d_status, void* stream, const ExtOverlay& overlay, const char* what)
 {
-    int r = entry_args(c, d_image, image_blocks, d_ext, 8, n, d_in, in_bytes != 0, "write extents: null or misaligned argument");
-    if (r || n == 0)
-        return r;
     ListCall call { c, stream, n, "extent", true };
-    if ((r = call.begin()))
+    int r = call.begin();
+    if (r)
         return r;
     if (!(r = ensure_ext_stage(c))) {
         const ExtStage x(c, call.s());
@@ -128,13 +128,29 @@ extern "C" int ppfs_ecc_write_extents_device(ppfs_ecc_ctx* c, const uint8_t* d_i
             const ppfs_ecc_extent* ex = d_ext + off;
             uint8_t* st = x.status_for(d_status, off);
             uint8_t* out_st = d_status ? d_status + off : nullptr;
-            (void)((r = x.index(ex, nb, io.blocks, in_bytes)) || (r = io.fetch(x.idx, nb))
-                || (r = io.old_payloads(x.idx, nb, x.P, st)) || (r = x.copy(1, ex, nullptr, nb, d_in, in_bytes))
+            (void)((r = x.index(ex, nb, io.blocks, buf_bytes)) || (r = io.fetch(x.idx, nb))
+                || (r = io.old_payloads(x.idx, nb, x.P, st))
+                || (r = overlay(ExtPiece { ex, x.idx, nb, x.P, c->ext_index_off, off, call.s() }))
                 || (r = io.write(x.idx, nb, c->data ? x.P : nullptr, st)) || (r = x.status_out(st, out_st, nb))
                 || (r = io.marks(x.idx, nb, out_st, nullptr)));
         }
     }
-    return call.end(r, "write extents (async)");
+    return call.end(r, what);
+}
+
+extern "C" int ppfs_ecc_write_extents_device(ppfs_ecc_ctx* c, const uint8_t* d_in, size_t in_bytes, uint8_t* d_image,
+    size_t image_blocks, const ppfs_ecc_extent* d_ext, size_t n, uint8_t* d_status, void* stream)
+{
+    int r = entry_args(c, d_image, image_blocks, d_ext, 8, n, d_in, in_bytes != 0, "write extents: null or misaligned argument");
+    if (r || n == 0)
+        return r;
+    // the caller's bytes: extent_copy<true>, nothing where there are none
+    const ExtOverlay overlay = [&](const ExtPiece& p) {
+        return check_hip(ppfs_extent_copy_launch(1, p.ex, p.idx, nullptr, p.nb, c->data, p.P, p.P_cap, const_cast<uint8_t*>(d_in),
+                             in_bytes, p.s),
+            "extent overlay");
+    };
+    return write_extents_pieces(c, d_image, image_blocks, d_ext, n, in_bytes, d_status, stream, overlay, "write extents (async)");
 }
 
 // ---------------------------------------------------------------------------------------

@@ -1,4 +1,5 @@
-// inode_walk.hip -- the kernels of the inode reads (inode_path.cpp; include/ppfs_ecc.h ppfs_ecc_read_inodes_*).
+// inode_walk.hip -- the kernels of the inode reads (inode_path.cpp; include/ppfs_ecc.h ppfs_ecc_read_inodes_*) and,
+// in the second half, of the inode writes (ppfs_ecc_write_inodes_*).
 //
 // InodeManager::get (lib/inode_manager/src/inode_manager.cpp:127-138) is one byte of the inode bitmap, then the 81
 // bytes of the packed Inode out of the inode table, cut at block boundaries.  For a piece of a batch of inode
@@ -18,6 +19,7 @@
 
 #include "dbg.hpp"
 #include "inode_plan.hpp"
+#include "inode_wplan.hpp"
 #include "kernels.hpp"
 #include "status_tally.hpp"
 #include <stdint.h>
@@ -169,6 +171,165 @@ __global__ __launch_bounds__(256) void inode_merge_kernel(const uint32_t* __rest
     tally_flush(free_c, counts, SLOT_NOT_ALLOCATED, 1);
 }
 
+// ---- the inode writes (inode_path.cpp ppfs_ecc_write_inodes_device; the grouping step of inode_wplan.hpp) ----
+//   inode_elect_kernel          one lane per slot (entry j, piece k): a slot that takes part claims its block's key and
+//                               lowers the block's owner to its slot index; piece 0 claims the inode number's key and
+//                               raises its winner to j
+//   inode_owner_extents_kernel  the owner slot of each block emits {pos 0, block, 0, 0}, every other slot the invalid
+//                               extent
+//   inode_overlay_kernel        inside the extent write, after the old payloads: the slots of winning entries store
+//                               their bytes of the composed row into their block's owner row of P
+//   inode_write_status_kernel   one lane per inode: the pieces' write statuses under the first toucher rule, the status
+//                               rule, status, piece_status, the tally
+// The tables were cleared to 0xFF on the stream before the elect kernel.  No lane waits for another: claim() and
+// find() end after at most cap probes.
+using namespace inodewplan;
+
+// the memory operations of inode_wplan.hpp on the device: a[i], i < cap
+struct DeviceOps {
+    __device__ static uint32_t load(const uint32_t* a, uint32_t i, uint32_t cap)
+    {
+        return i < cap && PPFS_DBG_OK(a + i, 4, a, (uint64_t)cap * 4) ? a[i] : EMPTY;
+    }
+    __device__ static uint32_t cas(uint32_t* a, uint32_t i, uint32_t cap, uint32_t expect, uint32_t v)
+    {
+        return i < cap && PPFS_DBG_OK(a + i, 4, a, (uint64_t)cap * 4) ? atomicCAS(a + i, expect, v) : 0u;
+    }
+    __device__ static void min_u32(uint32_t* a, uint32_t i, uint32_t cap, uint32_t v)
+    {
+        if (i < cap && PPFS_DBG_OK(a + i, 4, a, (uint64_t)cap * 4))
+            atomicMin(a + i, v);
+    }
+    __device__ static void max_i32(uint32_t* a, uint32_t i, uint32_t cap, uint32_t v)
+    {
+        if (i < cap && PPFS_DBG_OK(a + i, 4, a, (uint64_t)cap * 4))
+            atomicMax((int*)(a + i), (int)v);
+    }
+};
+
+// what slot `slot` < n * K of the piece does, from the scratch; *ino_out and *entry: its inode number and entry
+__device__ inline Slot slot_from_scratch(const uint32_t* __restrict__ ino_in, const uint8_t* __restrict__ bm,
+    const uint8_t* __restrict__ bst, uint64_t n, const InodeTable& t, uint64_t ds, uint32_t K, uint64_t slot, uint32_t* ino_out,
+    uint32_t* entry)
+{
+    const uint64_t j = slot / K;
+    *entry = (uint32_t)j;
+    *ino_out = 0;
+    if (j >= n || !PPFS_DBG_OK(ino_in + j, 4, ino_in, n * 4))
+        return Slot { false, NO_BLOCK, 0, 0, 0 };
+    const uint32_t ino = ino_in[j];
+    *ino_out = ino;
+    uint32_t bitmap_status;
+    const uint32_t verdict = verdict_of(t, ino, bm, bst, j, n, 0x80u >> (ino % 8u), &bitmap_status);
+    return slot_of(t.table_block, ino, (uint32_t)(slot - j * K), verdict, ds);
+}
+
+// tab: the two tables, table_bytes(cap) bytes, cleared
+__global__ __launch_bounds__(256) void inode_elect_kernel(const uint32_t* __restrict__ ino_in, const uint8_t* __restrict__ bm,
+    const uint8_t* __restrict__ bst, uint64_t n, InodeTable t, uint64_t ds, uint32_t K, uint32_t* tab, uint32_t cap)
+{
+    const Tables T = tables_at(tab, cap);
+    for (uint64_t s = (uint64_t)blockIdx.x * 256u + threadIdx.x; s < n * K; s += (uint64_t)gridDim.x * 256u) {
+        uint32_t ino, j;
+        const Slot sl = slot_from_scratch(ino_in, bm, bst, n, t, ds, K, s, &ino, &j);
+        elect<DeviceOps>(T, sl, ino, j, (uint32_t)(s - (uint64_t)j * K), (uint32_t)s);
+    }
+}
+
+// ext[s] for s < n * K
+__global__ __launch_bounds__(256) void inode_owner_extents_kernel(const uint32_t* __restrict__ ino_in, const uint8_t* __restrict__ bm,
+    const uint8_t* __restrict__ bst, uint64_t n, InodeTable t, uint64_t ds, uint32_t K, uint32_t* tab, uint32_t cap,
+    ppfs_ecc_extent* __restrict__ ext)
+{
+    const Tables T = tables_at(tab, cap);
+    for (uint64_t s = (uint64_t)blockIdx.x * 256u + threadIdx.x; s < n * K; s += (uint64_t)gridDim.x * 256u) {
+        uint32_t ino, j;
+        const Slot sl = slot_from_scratch(ino_in, bm, bst, n, t, ds, K, s, &ino, &j);
+        ppfs_ecc_extent e;
+        invalid_extent(e);
+        if (sl.takes_part && owner_of<DeviceOps>(T, sl.block) == (uint32_t)s)
+            e.block = sl.block; // pos, offset and length 0: the block is checked and encoded again
+        if (PPFS_DBG_OK(ext + s, 16, ext, n * K * 16))
+            ext[s] = e;
+    }
+}
+
+// files: 64 n bytes, meta: 3 n 64-bit words; idx[r], r < n * K: the staged index of extent r, whose payload is row r
+// of P (stride ds, P_cap bytes)
+__global__ __launch_bounds__(256) void inode_overlay_kernel(const uint32_t* __restrict__ ino_in, const uint8_t* __restrict__ bm,
+    const uint8_t* __restrict__ bst, uint64_t n, InodeTable t, uint64_t ds, uint32_t K, uint32_t* tab, uint32_t cap,
+    const uint8_t* __restrict__ files, const unsigned long long* __restrict__ meta, const uint32_t* __restrict__ idx, uint8_t* P,
+    uint64_t P_cap)
+{
+    const Tables T = tables_at(tab, cap);
+    for (uint64_t s = (uint64_t)blockIdx.x * 256u + threadIdx.x; s < n * K; s += (uint64_t)gridDim.x * 256u) {
+        uint32_t ino, j;
+        const Slot sl = slot_from_scratch(ino_in, bm, bst, n, t, ds, K, s, &ino, &j);
+        if (!sl.takes_part || winner_of<DeviceOps>(T, ino) != j)
+            continue;
+        const uint32_t row = owner_of<DeviceOps>(T, sl.block);
+        if (row >= n * K || !PPFS_DBG_OK(idx + row, 4, idx, n * K * 4) || idx[row] != sl.block)
+            continue; // the block is not in the image: nothing is written
+        const uint64_t at = (uint64_t)row * ds + sl.offset;
+        if (sl.offset + (uint64_t)sl.length > ds || at + sl.length > P_cap || sl.pos + sl.length > INODE_BYTES
+            || !PPFS_DBG_OK(P + at, sl.length, P, P_cap) || !PPFS_DBG_OK(meta + 3ull * j, 24, meta, n * 24)
+            || !PPFS_DBG_OK(files + 64ull * j, 64, files, n * 64))
+            continue;
+        const uint64_t tc = meta[3ull * j], tm = meta[3ull * j + 1u];
+        const uint32_t type = (uint32_t)meta[3ull * j + 2u] & 0xFFu;
+        const uint8_t* f = files + 64ull * j;
+        for (uint32_t b = 0; b < sl.length; ++b)
+            P[at + b] = (uint8_t)row_byte(tc, tm, type, [&](uint32_t i) -> uint32_t { return f[i]; }, sl.pos + b);
+    }
+}
+
+// wst[r], r < n * K: the write status of extent r.  status, piece_status (n * (1 + K) bytes), counts: each may be null
+__global__ __launch_bounds__(256) void inode_write_status_kernel(const uint32_t* __restrict__ ino_in, const uint8_t* __restrict__ bm,
+    const uint8_t* __restrict__ bst, const uint8_t* __restrict__ wst, uint64_t n, InodeTable t, uint64_t ds, uint32_t K, uint32_t* tab,
+    uint32_t cap, uint8_t* __restrict__ status, uint8_t* __restrict__ piece_status, unsigned long long* __restrict__ counts)
+{
+    const Tables T = tables_at(tab, cap);
+    uint32_t c[4] = { 0, 0, 0, 0 }, free_c[4] = { 0, 0, 0, 0 };
+    const uint64_t W = 1u + K;
+    for (uint64_t w0 = (uint64_t)blockIdx.x * 256u; w0 < n; w0 += (uint64_t)gridDim.x * 256u) {
+        const uint64_t j = w0 + threadIdx.x;
+        int slot = -1;
+        if (j < n && PPFS_DBG_OK(ino_in + j, 4, ino_in, n * 4)) {
+            const uint32_t ino = ino_in[j];
+            uint32_t bitmap_status;
+            const uint32_t verdict = verdict_of(t, ino, bm, bst, j, n, 0x80u >> (ino % 8u), &bitmap_status);
+            const bool bit_read = ino < t.total_inodes && t.check_bitmap;
+            const uint32_t np = verdict == 0u ? pieces(ino, ds) : 0u;
+            auto piece_st = [&](uint32_t k) -> uint32_t {
+                const Slot sl = slot_of(t.table_block, ino, k, verdict, ds);
+                if (!sl.takes_part)
+                    return ST_OUT;
+                const uint32_t row = owner_of<DeviceOps>(T, sl.block);
+                if (row >= n * K || !PPFS_DBG_OK(wst + row, 1, wst, n * K))
+                    return ST_OUT;
+                return seen_status(wst[row], (uint32_t)(j * K + k), row);
+            };
+            const uint32_t st = verdict ? verdict : table_status(bit_read ? bitmap_status : 0u, np, piece_st);
+            slot = count_slot(st);
+            if (status && PPFS_DBG_OK(status + j, 1, status, n))
+                status[j] = (uint8_t)st;
+            if (piece_status) {
+                uint8_t* ps = piece_status + j * W;
+                if (PPFS_DBG_OK(ps, W, piece_status, n * W)) {
+                    ps[0] = (uint8_t)(bit_read ? bitmap_status : ST_UNUSED);
+                    for (uint32_t k = 0; k < K; ++k)
+                        ps[1u + k] = (uint8_t)(k < np ? piece_st(k) : ST_UNUSED);
+                }
+            }
+        }
+        tally_add(c, slot);
+        tally_add(free_c, slot == SLOT_NOT_ALLOCATED ? 0 : -1);
+    }
+    tally_flush(c, counts, 0, 4);
+    __syncthreads(); // the two flushes share their LDS words
+    tally_flush(free_c, counts, SLOT_NOT_ALLOCATED, 1);
+}
+
 // grid-stride, at most 2,048 workgroups
 static uint32_t grid_of(uint64_t n)
 {
@@ -218,6 +379,60 @@ extern "C" hipError_t ppfs_inode_merge_launch(const uint32_t* ino, const uint8_t
     const InodeTable t { table->table_block, table->bitmap_block, table->total_inodes, table->check_bitmap };
     hipLaunchKernelGGL(inode_merge_kernel, dim3(grid_of(n)), dim3(256), 0, s, ino, bm, bst, rows, pst, n, t, ds, max_pieces(ds),
         (uint32_t*)files, (unsigned long long*)meta, status, piece_status, counts);
+    return hipGetLastError();
+}
+
+// the inode writes: n inodes of K slots each, n * K <= 2 * PIECE_INODES; tab: 4-byte aligned, table_bytes(cap) bytes
+static bool wshape_ok(uint64_t n, uint64_t ds, const void* tab, uint32_t cap)
+{
+    return shape_ok(n, ds) && n * max_pieces(ds) <= 2u * PIECE_INODES && tab && !((uintptr_t)tab & 3u) && cap >= 2u
+        && (cap & (cap - 1u)) == 0u && (uint64_t)cap >= 2u * n * max_pieces(ds);
+}
+
+extern "C" hipError_t ppfs_inode_elect_launch(const uint32_t* ino, const uint8_t* bm, const uint8_t* bst, uint64_t n,
+    const ppfs_ecc_inode_table* table, uint64_t ds, uint32_t* tab, uint32_t cap, ppfs_ecc_extent* ext, hipStream_t s)
+{
+    if (n == 0)
+        return hipSuccess;
+    if (!ino || !bm || !bst || !table || !ext || ((uintptr_t)ino & 3u) || ((uintptr_t)ext & 7u) || !wshape_ok(n, ds, tab, cap))
+        return hipErrorInvalidValue;
+    const InodeTable t { table->table_block, table->bitmap_block, table->total_inodes, table->check_bitmap };
+    const uint32_t K = max_pieces(ds);
+    hipLaunchKernelGGL(inode_elect_kernel, dim3(grid_of(n * K)), dim3(256), 0, s, ino, bm, bst, n, t, ds, K, tab, cap);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(inode_owner_extents_kernel, dim3(grid_of(n * K)), dim3(256), 0, s, ino, bm, bst, n, t, ds, K, tab, cap, ext);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t ppfs_inode_overlay_launch(const uint32_t* ino, const uint8_t* bm, const uint8_t* bst, uint64_t n,
+    const ppfs_ecc_inode_table* table, uint64_t ds, uint32_t* tab, uint32_t cap, const ppfs_ecc_file* files,
+    const ppfs_ecc_inode_meta* meta, const uint32_t* idx, uint8_t* P, uint64_t P_cap, hipStream_t s)
+{
+    if (n == 0)
+        return hipSuccess;
+    if (!ino || !bm || !bst || !table || !files || !meta || !idx || !P || ((uintptr_t)ino & 3u) || ((uintptr_t)idx & 3u)
+        || ((uintptr_t)meta & 7u) || !wshape_ok(n, ds, tab, cap))
+        return hipErrorInvalidValue;
+    const InodeTable t { table->table_block, table->bitmap_block, table->total_inodes, table->check_bitmap };
+    const uint32_t K = max_pieces(ds);
+    hipLaunchKernelGGL(inode_overlay_kernel, dim3(grid_of(n * K)), dim3(256), 0, s, ino, bm, bst, n, t, ds, K, tab, cap,
+        (const uint8_t*)files, (const unsigned long long*)meta, idx, P, P_cap);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t ppfs_inode_write_status_launch(const uint32_t* ino, const uint8_t* bm, const uint8_t* bst, const uint8_t* wst,
+    uint64_t n, const ppfs_ecc_inode_table* table, uint64_t ds, uint32_t* tab, uint32_t cap, uint8_t* status, uint8_t* piece_status,
+    unsigned long long* counts, hipStream_t s)
+{
+    if (n == 0 || (!status && !piece_status && !counts))
+        return hipSuccess;
+    if (!ino || !bm || !bst || !wst || !table || ((uintptr_t)ino & 3u) || ((uintptr_t)counts & 7u) || !wshape_ok(n, ds, tab, cap))
+        return hipErrorInvalidValue;
+    const InodeTable t { table->table_block, table->bitmap_block, table->total_inodes, table->check_bitmap };
+    hipLaunchKernelGGL(inode_write_status_kernel, dim3(grid_of(n)), dim3(256), 0, s, ino, bm, bst, wst, n, t, ds, max_pieces(ds), tab,
+        cap, status, piece_status, counts);
     return hipGetLastError();
 }
 

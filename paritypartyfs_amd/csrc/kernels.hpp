@@ -2,8 +2,8 @@
 // rs_kernels.hip (Reed-Solomon and its servers), bit_kernels.hip (CRC, Hamming, parity and the bit
 // server) vote.hip (vote, copy, gather, patch list, inject, flag, block lists), alloc_scan.hip (bitmap
 // expansion, scrub tally), files_walk.hip (the file walk's expansion, extents and merges) and
-// inode_walk.hip (the inode reads' extents and merge).  The three table-sizing functions are in
-// host_tables.hpp, beside the builders that use them.
+// inode_walk.hip (the inode reads' extents and merge, the inode writes' election, overlay and statuses).
+// The three table-sizing functions are in host_tables.hpp, beside the builders that use them.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -144,4 +144,21 @@ hipError_t ppfs_inode_table_extents_launch(const uint32_t* ino, const uint8_t* b
 hipError_t ppfs_inode_merge_launch(const uint32_t* ino, const uint8_t* bm, const uint8_t* bst, const uint8_t* rows,
     const uint8_t* pst, uint64_t n, const ppfs_ecc_inode_table* table, uint64_t ds, ppfs_ecc_file* files, ppfs_ecc_inode_meta* meta,
     uint8_t* status, uint8_t* piece_status, unsigned long long* counts, hipStream_t s);
+// the inode writes (inode_path.cpp; the grouping step of inode_wplan.hpp) over one piece of n inodes, n * K slots, at
+// most 2 * inodeplan::PIECE_INODES of them; ino, bm, bst: the scratch the bitmap steps above left; tab: the two
+// election tables, inodewplan::table_bytes(cap) bytes cleared to 0xFF on the stream, cap = inodewplan::capacity(n * K).
+// elect: the elect kernel, then the extents kernel: ext[slot] (8-byte aligned), the owner slot of each distinct block
+// {pos 0, block, 0, 0}, every other slot invalid.
+// overlay: the bytes of the winning entries' rows (files: 64 n bytes, meta: 24 n bytes, 8-byte aligned) into their
+// blocks' owner rows of P (stride ds, P_cap bytes); idx: the staged indices of the n * K extents.
+// write_status: wst[slot], the extents' write statuses -> status, piece_status (n * (1 + K) bytes) and the counts, each
+// may be null.
+hipError_t ppfs_inode_elect_launch(const uint32_t* ino, const uint8_t* bm, const uint8_t* bst, uint64_t n,
+    const ppfs_ecc_inode_table* table, uint64_t ds, uint32_t* tab, uint32_t cap, ppfs_ecc_extent* ext, hipStream_t s);
+hipError_t ppfs_inode_overlay_launch(const uint32_t* ino, const uint8_t* bm, const uint8_t* bst, uint64_t n,
+    const ppfs_ecc_inode_table* table, uint64_t ds, uint32_t* tab, uint32_t cap, const ppfs_ecc_file* files,
+    const ppfs_ecc_inode_meta* meta, const uint32_t* idx, uint8_t* P, uint64_t P_cap, hipStream_t s);
+hipError_t ppfs_inode_write_status_launch(const uint32_t* ino, const uint8_t* bm, const uint8_t* bst, const uint8_t* wst,
+    uint64_t n, const ppfs_ecc_inode_table* table, uint64_t ds, uint32_t* tab, uint32_t cap, uint8_t* status, uint8_t* piece_status,
+    unsigned long long* counts, hipStream_t s);
 }

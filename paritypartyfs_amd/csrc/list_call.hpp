@@ -3,6 +3,9 @@
 // rows that a call decodes, encodes or writes.  Defined in list_path.cpp.
 #pragma once
 
+#include <functional>
+
+#include "../../include/ppfs_ecc.h"
 #include "ctx.hpp"
 
 #pragma GCC visibility push(hidden)
@@ -63,6 +66,25 @@ private:
     uint8_t* rows() const { return c->d_list; }
     uint8_t* own_status() const { return c->d_list + c->list_status_off; }
 };
+
+// The write piece loop of the byte-extent calls (extent_path.cpp) with its overlay step as a parameter.  Per piece of at
+// most piece_of(c) entries: index, fetch, old payloads into P, overlay(piece), write, status out, marks.  The overlay
+// queues on s whatever puts the new bytes onto the decoded payloads: row i of P (stride data size, P_cap bytes in
+// all) is entry first + i of the list, idx[i] its staged index (0xFFFFFFFF: invalid, the row is not written).
+// ppfs_ecc_write_extents_device passes the copy of the caller's packed bytes; the inode write (inode_path.cpp) passes
+// its own kernel and a buf_bytes of 0.  The caller has checked its arguments (entry_args) and n > 0.
+struct ExtPiece {
+    const ppfs_ecc_extent* ex;
+    const uint32_t* idx;
+    uint32_t nb;
+    uint8_t* P;
+    size_t P_cap;
+    size_t first;
+    hipStream_t s;
+};
+using ExtOverlay = std::function<int(const ExtPiece&)>;
+int write_extents_pieces(ppfs_ecc_ctx* c, uint8_t* d_image, size_t image_blocks, const ppfs_ecc_extent* d_ext, size_t n,
+    size_t buf_bytes, uint8_t* d_status, void* stream, const ExtOverlay& overlay, const char* what);
 
 // The context's scrub scratch (scrub_path.cpp), which the scrubs of named blocks and the file walk
 // (files_path.cpp) use: at least `bytes` of it for work queued on s, after a wait for its previous user;

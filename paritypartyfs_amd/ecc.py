@@ -787,6 +787,38 @@ class EccEngine:
             self._u32_ptr(status), self._u32_ptr(piece_status), byref(rec), int(bool(write_back))))
         return InodeCounts(*[int(getattr(rec, k)) for k in INODE_COUNT_FIELDS])
 
+    # ---------------- write inodes into the inode table (ppfs_ecc_write_inodes_*) ----------------
+    # InodeManager::update over a batch: the reads' arguments with `files` (64 n bytes) and `meta` (24 n bytes) as
+    # required inputs; status, piece_status and counts are the outputs.
+    def write_inodes(self, image, table, numbers, files, meta, n=None, stride=None, status=None, piece_status=None,
+                     counts=None, write_back: bool = True, stream=None):
+        """Device write of a batch of inodes (ppfs_ecc_write_inodes_device): inode j's 81 bytes are meta[j]'s two
+        times, the 64 bytes of files[j] and meta[j]'s type.  Several inodes of one table block and repeated numbers
+        are the norm: the result is the per-inode loop's in batch order.  counts as for read_inodes.  Never
+        synchronises."""
+        if files is None or meta is None:
+            raise ValueError("files and meta: required")
+        t, blocks, addr, stride, n = self._inodes_check("device", image, table, numbers, n, stride, files, meta, status,
+                                                        piece_status)
+        d_counts = self._device_counts(counts)
+        check(lib().ppfs_ecc_write_inodes_device(
+            self._h, _ptr(image), blocks, t.ctypes.data, addr, stride, n, self._u32_ptr(files), self._u32_ptr(meta),
+            self._u32_ptr(status), self._u32_ptr(piece_status), None if d_counts is None else d_counts.data_ptr(),
+            int(bool(write_back)), _stream_handle(stream)))
+        return d_counts
+
+    def write_inodes_host(self, image: np.ndarray, table, numbers, files, meta, n=None, stride=None, status=None,
+                          piece_status=None, write_back: bool = True) -> "InodeCounts":
+        if files is None or meta is None:
+            raise ValueError("files and meta: required")
+        t, blocks, addr, stride, n = self._inodes_check("host", image, table, numbers, n, stride, files, meta, status,
+                                                        piece_status)
+        rec = _native.InodeCounts()
+        check(lib().ppfs_ecc_write_inodes_host(
+            self._h, _ptr(image), blocks, t.ctypes.data, addr, stride, n, self._u32_ptr(files), self._u32_ptr(meta),
+            self._u32_ptr(status), self._u32_ptr(piece_status), byref(rec), int(bool(write_back))))
+        return InodeCounts(*[int(getattr(rec, k)) for k in INODE_COUNT_FIELDS])
+
 
 # ppfs_ecc_scrub_counts: the host forms return it as this tuple, the device forms as a CUDA int64 tensor
 # in the same field order (ScrubCounts(*tensor.tolist()) after synchronising)
