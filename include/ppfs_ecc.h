@@ -764,6 +764,81 @@ int ppfs_ecc_write_inodes_host(ppfs_ecc_ctx* ctx, uint8_t* image, size_t image_b
     uint8_t* piece_status, ppfs_ecc_inode_counts* counts, int write_back);
 
 /*
+ * Look up names in directories: a batch of (directory, key) per call.  Every path
+ * operation starts with DirectoryManager::getInodeByName (lib/directory_manager/src/directory_manager.cpp:135-163):
+ * a loop of readFile over batches of 256 DirectoryEntry records and a strlen / strncmp pass over each
+ * (_findEntryByName, :189-199).  The search inside removeEntry (:67-90, _findEntryByInode :201-210) is the same loop
+ * with the inode number as the key.  ppfs_ecc_lookup_* is that loop for nq queries over ndirs directories, each
+ * directory read ONCE and whole.  Engine extension; read-only apart from the codec's write-back.
+ *
+ * Entries.  Directory d, a ppfs_ecc_file record, has n_d = file_size / 128 entries; trailing bytes are never read.
+ * Entry e is the 128 bytes at 128 e of the payload (directory.hpp:8-12): bytes [0, 4) the little-endian inode
+ * number, bytes [4, 128) the 124 name bytes.
+ * Queries.  queries[q] = {dir, key}.  mode 0 (name): the key is names[128 q, 128 q + 128), a record at any
+ * alignment whose name starts at byte 0 and whose length L is the position of its first NUL; `key` is not read.
+ * mode 1 (inode number): the key is `key`; names is not read and may be NULL.
+ * Name match.  The entry's name length is the position of the first NUL in its 124 name bytes; the query matches
+ * when that length is L and the L bytes are equal.  Bytes behind the entry's NUL are not looked at.  L = 0 matches
+ * an entry whose first name byte is NUL.  A query with L >= 124 or with no NUL matches nothing.  DEVIATION: an
+ * entry with no NUL in its 124 name bytes matches nothing; the reference's strlen would run on into the next entry.
+ * Inode match.  Entry bytes [0, 4) equal the key.
+ * First match.  m is the lowest matching entry below n_d: duplicates resolve to the first.
+ * Failures, the loop's rule.  The loop reads batch b, entries [256 b, min(256 b + 256, n_d)), with one readFile,
+ * which fails as a whole if any file block under those bytes fails -- blocks under entries behind a match in the
+ * same batch included.  With B = m / 256 for a match and the last batch otherwise, last(B) is the last file block
+ * that batch B's bytes touch.  If a file block j <= last(B) has final read status 5 or 9 (the path status where
+ * that is non-zero, as ppfs_ecc_read_files_* reports it), the query's status is that of the lowest such j and it
+ * reports no inode.  Otherwise the status is 0 with inode and entry, or PPFS_ECC_NOT_FOUND without a match.  A
+ * failing block behind last(B) does not matter.  n_d = 0 is PPFS_ECC_NOT_FOUND, and nothing of that directory is
+ * read.  Corrections (status 1) are no per-query result: they are reported per block and per directory.
+ *
+ * ppfs_ecc_lookup_plan: ppfs_ecc_files_plan over the ranges (0, 128 n_d) -- how large the entries buffer
+ * (totals.bytes) and the block status array (totals.blocks) are and where each directory's entries lie (slots[d].
+ * out_pos, block_pos).  slots and totals may be NULL.  No GPU work.
+ * Buffers.  entries (entries_bytes >= totals.bytes) and block_status (totals.blocks bytes) are the call's working
+ * memory and the caller's to keep: after the call they hold every directory's entries and final block statuses
+ * exactly as ppfs_ecc_read_files_* over those ranges leaves them, so entries is a ready `ino` source at stride 128
+ * for ppfs_ecc_read_inodes_*.  Both are required in the device form; the host form uses buffers of its own where
+ * they are NULL.  dir_flags (ndirs words) and file_counts are ppfs_ecc_read_files_*' flags and counts, and may be
+ * NULL.  hits: nq records, inode and entry 0xFFFFFFFF unless the status is 0.  counts (may be NULL): the nq statuses
+ * tallied; out_of_range counts status 9.
+ * Errors: -EINVAL, before anything touches the GPU, for a null ctx, image, dirs, queries or hits, null names in
+ * mode 0, a mode other than 0 or 1, a `dir` at or past ndirs (ppfs_ecc_last_error names the query), hits or
+ * dir_flags not 4-byte or a counts record not 8-byte aligned, buffers that are short (or, in the device form,
+ * null), 2^32 - 1 or more queries, and whatever ppfs_ecc_files_plan rejects.  nq == 0 returns 0 with zeroed counts
+ * and reads nothing.  A capturing stream gets PPFS_ECC_ENOTSUP.
+ * Device form: never synchronises `stream`, reads nothing back, allocates and frees nothing on the caller's
+ * stream.  dirs and queries are HOST pointers.  One ppfs_ecc_read_files_device; then the per-directory table (entry
+ * count, out_pos, block_pos, blocks) and the query records go into the context's scrub scratch through the page-
+ * locked staging of the file batch's tables, released behind an event; the hit records are set to 0xFF; the match
+ * kernel, one wave per (query, 256 entries), lowers each query's `entry` word to its first match with one atomicMin
+ * per wave; the finish kernel, one wave per query, applies the failure rule and tallies.
+ * Host form: ppfs_ecc_read_files_host, then the same rule on the CPU.
+ */
+#define PPFS_ECC_NOT_FOUND 2 /* status of a query whose loop ran to its end without a match (engine extension) */
+
+typedef struct ppfs_ecc_lookup_query { /* 8 bytes */
+    uint32_t dir, key;
+} ppfs_ecc_lookup_query;
+typedef struct ppfs_ecc_lookup_hit { /* 16 bytes */
+    uint32_t inode, entry, status, reserved;
+} ppfs_ecc_lookup_hit;
+typedef struct ppfs_ecc_lookup_counts { /* 64 bytes, overwritten by each call */
+    uint64_t found, not_found, failed, out_of_range, reserved[4];
+} ppfs_ecc_lookup_counts;
+
+int ppfs_ecc_lookup_plan(const ppfs_ecc_ctx* ctx, const ppfs_ecc_file* dirs, size_t ndirs, ppfs_ecc_files_slot* slots,
+    ppfs_ecc_files_totals* totals);
+int ppfs_ecc_lookup_device(ppfs_ecc_ctx* ctx, uint8_t* d_image, size_t image_blocks, const ppfs_ecc_file* dirs, size_t ndirs,
+    const ppfs_ecc_lookup_query* queries, const uint8_t* d_names, size_t nq, int mode, uint8_t* d_entries, size_t entries_bytes,
+    uint8_t* d_block_status, uint32_t* d_dir_flags, ppfs_ecc_lookup_hit* d_hits, ppfs_ecc_lookup_counts* d_counts,
+    ppfs_ecc_file_counts* d_file_counts, int write_back, void* stream);
+int ppfs_ecc_lookup_host(ppfs_ecc_ctx* ctx, uint8_t* image, size_t image_blocks, const ppfs_ecc_file* dirs, size_t ndirs,
+    const ppfs_ecc_lookup_query* queries, const uint8_t* names, size_t nq, int mode, uint8_t* entries, size_t entries_bytes,
+    uint8_t* block_status, uint32_t* dir_flags, ppfs_ecc_lookup_hit* hits, ppfs_ecc_lookup_counts* counts,
+    ppfs_ecc_file_counts* file_counts, int write_back);
+
+/*
  * 2-of-3 bitwise majority of nrec replicated records of rec_bytes each, replacing
  * SuperBlockManager::_performBitVoting (lib/super_block_manager/src/super_block_manager.cpp:133-165):
  *   out[i] = majority(a[i], b[i], c[i]) bit by bit;

@@ -127,6 +127,11 @@ enum class FsError : uint8_t {
 };
 static_assert((int)FsError::BlockDevice_CorrectionError == PPFS_ECC_CORRECTION_ERROR, "status 5");
 static_assert((int)FsError::Disk_OutOfBounds == PPFS_ECC_OUT_OF_BOUNDS, "status 9");
+// a lookup's "ran to the end without a match" is no FsError of a block: the adapter turns it into PpFS_NotFound /
+// DirectoryManager_NotFound, and it collides with no status a block can have
+static_assert(PPFS_ECC_NOT_FOUND == 2 && PPFS_ECC_NOT_FOUND != PPFS_ECC_CORRECTED && PPFS_ECC_NOT_FOUND != PPFS_ECC_CORRECTION_ERROR
+        && PPFS_ECC_NOT_FOUND != PPFS_ECC_OUT_OF_BOUNDS && PPFS_ECC_NOT_FOUND != PPFS_ECC_NOT_ALLOCATED && PPFS_ECC_NOT_FOUND != 0,
+    "status 2: not found");
 
 // ------------------------------------------------------------------------------------------
 // std::expected<T, E> subset
@@ -957,6 +962,76 @@ public:
             r.inode = inode;
         }
     }
+
+    // Lookup extension (ppfs_ecc.h ppfs_ecc_lookup_*): nq (directory, key) queries over ndirs directories in one call
+    // -- one path component of many paths, the uniqueness test before many creates.  By definition the loop of
+    // DirectoryManager::getInodeByName (directory_manager.cpp:135-163) for lookupNames and of removeEntry's search
+    // (:67-90, up to and including the found_entry decision) for lookupInodes: _readDirectoryData (:165-187), a
+    // readFile of at most 256 DirectoryEntry records, then _findEntryByName (:189-199) / _findEntryByInode (:201-210).
+    // A name is a 128-byte record, NUL-terminated within its first 124 bytes (else it matches nothing).  DEVIATION:
+    // an entry whose 124 name bytes hold no NUL matches nothing; the reference's strlen would run on into the next
+    // entry.  The codecs read every directory once and whole in one engine call.
+    static constexpr size_t kDirEntryBytes = 128, kDirEntryBatch = 256, kDirNameBytes = 124;
+    struct Lookup {
+        uint32_t dir;        // a number into the call's directories
+        uint32_t key;        // lookupInodes: the inode number
+        const uint8_t* name; // lookupNames: the 128-byte record
+        bool ok;
+        FsError error; // the failing block's, PpFS_NotFound (names) or DirectoryManager_NotFound (inodes)
+        uint32_t inode, entry; // 0xFFFFFFFF unless ok
+    };
+    // the position of the first NUL among the first cap bytes, cap when there is none
+    static size_t lookup_strnlen(const uint8_t* p, size_t cap)
+    {
+        const void* at = std::memchr(p, 0, cap);
+        return at ? (size_t)((const uint8_t*)at - p) : cap;
+    }
+    void lookup_loop(const ppfs_ecc_file* dirs, size_t ndirs, Lookup* queries, size_t nq, bool by_name)
+    {
+        std::vector<uint8_t> buffer(kDirEntryBatch * kDirEntryBytes);
+        for (size_t q = 0; q < nq; ++q) {
+            Lookup& r = queries[q];
+            r.ok = false;
+            r.inode = r.entry = 0xFFFFFFFFu;
+            r.error = by_name ? FsError::PpFS_NotFound : FsError::DirectoryManager_NotFound;
+            if (r.dir >= ndirs) {
+                r.error = FsError::DirectoryManager_InvalidRequest;
+                continue;
+            }
+            const ppfs_ecc_file& dir = dirs[r.dir];
+            const size_t L = by_name ? lookup_strnlen(r.name, 128) : 0;
+            const size_t num_entries = dir.file_size / kDirEntryBytes;
+            size_t checked = 0;
+            bool done = false;
+            while (checked < num_entries && !done) {
+                const size_t size = std::min(kDirEntryBatch, num_entries - checked);
+                auto read_res = readFile(dir, checked * kDirEntryBytes, size * kDirEntryBytes, buffer.data());
+                if (!read_res) {
+                    r.error = read_res.error();
+                    break;
+                }
+                const size_t got = *read_res / kDirEntryBytes;
+                for (size_t i = 0; i < got && !done; ++i) {
+                    const uint8_t* e = buffer.data() + i * kDirEntryBytes;
+                    uint32_t inode;
+                    std::memcpy(&inode, e, 4);
+                    const bool hit = by_name ? L < kDirNameBytes && lookup_strnlen(e + 4, kDirNameBytes) == L && std::memcmp(e + 4, r.name, L) == 0
+                                             : inode == r.key;
+                    if (hit) {
+                        r.ok = done = true;
+                        r.error = FsError {};
+                        r.inode = inode;
+                        r.entry = (uint32_t)(checked + i);
+                    }
+                }
+                checked += got;
+                if (got == 0)
+                    break;
+            }
+        }
+    }
+    virtual void lookupNames(const ppfs_ecc_file* dirs, size_t ndirs, Lookup* queries, size_t nq) { lookup_loop(dirs, ndirs, queries, nq, true); }
+    virtual void lookupInodes(const ppfs_ecc_file* dirs, size_t ndirs, Lookup* queries, size_t nq) { lookup_loop(dirs, ndirs, queries, nq, false); }
 
     // The mirror (ppfs_ecc.h ppfs_ecc_write_inodes_*): n inodes written into one inode table in one call -- what
     // follows a batch of file writes.  By definition the per-inode loop, InodeManager::update (inode_manager.cpp:
@@ -1834,6 +1909,109 @@ public:
             r.inode.file = files[j];
             r.inode.type = meta[j].type;
         }
+    }
+
+    // lookupNames / lookupInodes as ONE ppfs_ecc_lookup_host on a mapped disk image, behind the FileBatch walk of the
+    // directories' trees that the log needs (which image block each file block and index block is).  Results equal
+    // the loop's for every query.  The log holds the loop's events first and in the loop's order: queries in order,
+    // each block at its first read, an index block in front of the first file block under it.  The engine reads every
+    // directory whole, so directory blocks that no query's loop reached -- behind last(B), or behind a failing block
+    // -- may additionally have been corrected; they are logged after the loop's events in (directory, block) order,
+    // and the disk is the loop's with exactly those blocks corrected as well: readFile's deviation.  Elsewhere, for a
+    // shortened RS code and for a directory past its tree's capacity, the loop.
+    void lookupNames(const ppfs_ecc_file* dirs, size_t ndirs, Lookup* queries, size_t nq) override { lookup_engine(dirs, ndirs, queries, nq, true); }
+    void lookupInodes(const ppfs_ecc_file* dirs, size_t ndirs, Lookup* queries, size_t nq) override { lookup_engine(dirs, ndirs, queries, nq, false); }
+    void lookup_engine(const ppfs_ecc_file* dirs, size_t ndirs, Lookup* queries, size_t nq, bool by_name)
+    {
+        auto loop = [&]() { IBlockDevice::lookup_loop(dirs, ndirs, queries, nq, by_name); };
+        if (!nq || _ds > 0xFFFFu)
+            return loop();
+        // the directories that have entries, as a batch of ranges (0, 128 n); slot[d]: directory d's number in it
+        FileBatch b(*this);
+        std::vector<uint32_t> slot(ndirs, 0xFFFFFFFFu);
+        for (size_t d = 0; d < ndirs; ++d) {
+            const size_t n = dirs[d].file_size / kDirEntryBytes;
+            if (n) {
+                slot[d] = (uint32_t)b.sel.size();
+                b.add_range(d, dirs[d], 0, n * kDirEntryBytes);
+            }
+        }
+        for (size_t q = 0; q < nq; ++q)
+            if (queries[q].dir >= ndirs)
+                return loop();
+        if (!b.img)
+            return loop();
+        if (b.sel.empty()) // nothing to read: the loop answers from the sizes alone
+            return loop();
+        auto fail_all = [&]() {
+            for (size_t q = 0; q < nq; ++q) {
+                queries[q].ok = false;
+                queries[q].error = FsError::Disk_IOError;
+                queries[q].inode = queries[q].entry = 0xFFFFFFFFu;
+            }
+        };
+        if (!b.walk(true))
+            return fail_all();
+        // the engine gets the queries on directories that have entries; at[q]: query q's number among them
+        std::vector<size_t> at(nq, (size_t)-1);
+        std::vector<ppfs_ecc_lookup_query> qs;
+        std::vector<uint8_t> names;
+        for (size_t q = 0; q < nq; ++q) {
+            if (slot[queries[q].dir] == 0xFFFFFFFFu)
+                continue; // an empty directory: not found, nothing read
+            at[q] = qs.size();
+            qs.push_back(ppfs_ecc_lookup_query { slot[queries[q].dir], queries[q].key });
+            if (by_name)
+                names.insert(names.end(), queries[q].name, queries[q].name + 128);
+        }
+        std::vector<ppfs_ecc_lookup_hit> hits(qs.size());
+        std::vector<uint8_t> entries(b.tot.bytes + 1);
+        if (!EccEngine::ok(ppfs_ecc_lookup_host(_eng.ctx(), b.img, _disk.size() / _raw, b.files.data(), b.files.size(), qs.data(),
+                               by_name ? names.data() : nullptr, qs.size(), by_name ? 0 : 1, entries.data(), b.tot.bytes, b.status.data(),
+                               nullptr, hits.data(), nullptr, nullptr, _wb),
+                "lookup"))
+            return fail_all();
+        // per directory its corrected blocks in the loop's order, and its first failing file block
+        std::vector<std::vector<FileEvent>> events(b.sel.size());
+        std::vector<size_t> cursor(b.sel.size(), 0), failing(b.sel.size());
+        for (size_t k = 0; k < b.sel.size(); ++k) {
+            const ppfs_ecc_files_slot& t = b.slots[k];
+            std::vector<uint64_t> under[3];
+            file_tree_under(0, b.sel[k].count, under);
+            for (int d = 0; d < 3; ++d)
+                for (size_t i = 0; i < under[d].size() && i < t.tree_n[d]; ++i)
+                    if (b.tst[t.tree_pos[d] + i] == PPFS_ECC_CORRECTED)
+                        events[k].push_back(FileEvent { under[d][i], d, b.tidx[t.tree_pos[d] + i] });
+            for (size_t i = 0; i < b.sel[k].count; ++i)
+                if (b.status[t.block_pos + i] == PPFS_ECC_CORRECTED)
+                    events[k].push_back(FileEvent { i, 3, b.idx[t.block_pos + i] });
+            std::stable_sort(events[k].begin(), events[k].end(),
+                [](const FileEvent& x, const FileEvent& y) { return x.at != y.at ? x.at < y.at : x.level < y.level; });
+            uint8_t e = 0;
+            failing[k] = b.first_failure(k, e);
+        }
+        auto log_upto = [&](size_t k, uint64_t last) { // the loop's reads of file blocks [0, last] of directory k
+            for (; cursor[k] < events[k].size() && events[k][cursor[k]].at <= last; ++cursor[k])
+                log(events[k][cursor[k]].block);
+        };
+        for (size_t q = 0; q < nq; ++q) {
+            Lookup& r = queries[q];
+            const ppfs_ecc_lookup_hit h = at[q] != (size_t)-1 ? hits[at[q]] : ppfs_ecc_lookup_hit { 0xFFFFFFFFu, 0xFFFFFFFFu, PPFS_ECC_NOT_FOUND, 0 };
+            const size_t n = dirs[r.dir].file_size / kDirEntryBytes;
+            if (n) {
+                const size_t k = slot[r.dir], B = h.status == PPFS_ECC_OK ? h.entry / kDirEntryBatch : (n - 1) / kDirEntryBatch;
+                const uint64_t last = (std::min((B + 1) * kDirEntryBatch, n) * kDirEntryBytes - 1) / _ds;
+                log_upto(k, std::min<uint64_t>(last, failing[k]));
+            }
+            r.ok = n && h.status == PPFS_ECC_OK;
+            r.inode = r.ok ? h.inode : 0xFFFFFFFFu;
+            r.entry = r.ok ? h.entry : 0xFFFFFFFFu;
+            r.error = r.ok                                     ? FsError {}
+                : !n || h.status == PPFS_ECC_NOT_FOUND ? (by_name ? FsError::PpFS_NotFound : FsError::DirectoryManager_NotFound)
+                                                       : (FsError)status_error((uint8_t)h.status);
+        }
+        for (size_t k = 0; k < b.sel.size(); ++k) // what the engine corrected beyond the loop's reach
+            log_upto(k, ~0ull);
     }
 
     // writeInodes as ONE ppfs_ecc_write_inodes_host on a mapped disk image, from the steps readInodes is made of.

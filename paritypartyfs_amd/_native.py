@@ -21,6 +21,7 @@ ECC_NONE, ECC_CRC, ECC_HAMMING, ECC_PARITY, ECC_REED_SOLOMON = 0, 1, 2, 3, 4
 STATUS_OK, STATUS_CORRECTED, STATUS_CORRECTION_ERROR = 0, 1, 5
 STATUS_OUT_OF_BOUNDS = 9  # a block-list entry past the image (FsError::Disk_OutOfBounds)
 STATUS_NOT_ALLOCATED = 255  # scrub_allocated: the block's bit is clear, the block was not read
+STATUS_NOT_FOUND = 2  # lookup: the query's loop ran to its end without a match (PPFS_ECC_NOT_FOUND)
 
 # every symbol include/ppfs_ecc.h declares
 EXPORTED_SYMBOLS = (
@@ -77,6 +78,9 @@ EXPORTED_SYMBOLS = (
     "ppfs_ecc_read_inodes_host",
     "ppfs_ecc_write_inodes_device",
     "ppfs_ecc_write_inodes_host",
+    "ppfs_ecc_lookup_plan",
+    "ppfs_ecc_lookup_device",
+    "ppfs_ecc_lookup_host",
     "ppfs_vote3_device",
     "ppfs_vote3_host",
     "ppfs_copy_device",
@@ -119,6 +123,13 @@ INODE_TABLE_DTYPE = np.dtype([("table_block", "<u4"), ("bitmap_block", "<u4"), (
 INODE_META_DTYPE = np.dtype([("time_creation", "<u8"), ("time_modified", "<u8"), ("type", "u1"), ("pad", "u1", (7,))])
 INODE_PIECE = 16384  # PPFS_ECC_INODE_PIECE: inodes per piece of a device call
 
+# ppfs_ecc_lookup_query: one (directory, key) of a lookup (8 bytes), and ppfs_ecc_lookup_hit: its answer (16 bytes);
+# a name key is a 128-byte record of its own (LOOKUP_NAME_BYTES), NUL-terminated within its first 124 bytes
+LOOKUP_QUERY_DTYPE = np.dtype([("dir", "<u4"), ("key", "<u4")])
+LOOKUP_HIT_DTYPE = np.dtype([("inode", "<u4"), ("entry", "<u4"), ("status", "<u4"), ("reserved", "<u4")])
+LOOKUP_NAME_BYTES = 128
+LOOKUP_NONE = 0xFFFFFFFF  # inode and entry of a hit whose status is not 0
+
 
 class EccParams(ctypes.Structure):
     _fields_ = [
@@ -146,6 +157,12 @@ class InodeCounts(ctypes.Structure):
     """ppfs_ecc_inode_counts: the statuses of a batch of inode reads (64 bytes, overwritten by each call)."""
     _fields_ = [(n, c_uint64) for n in ("ok", "corrected", "failed", "out_of_range", "not_allocated", "reserved0",
                                         "reserved1", "reserved2")]
+
+
+class LookupCounts(ctypes.Structure):
+    """ppfs_ecc_lookup_counts: the statuses of a batch of lookups (64 bytes, overwritten by each call)."""
+    _fields_ = [(n, c_uint64) for n in ("found", "not_found", "failed", "out_of_range", "reserved0", "reserved1",
+                                        "reserved2", "reserved3")]
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -333,6 +350,15 @@ def lib() -> ctypes.CDLL:
     L.ppfs_ecc_write_inodes_device.argtypes = list(L.ppfs_ecc_read_inodes_device.argtypes)
     L.ppfs_ecc_write_inodes_host.restype = c_int
     L.ppfs_ecc_write_inodes_host.argtypes = list(L.ppfs_ecc_read_inodes_host.argtypes)
+    # lookups: plan (ctx, dirs, ndirs, slots, totals); lookup (ctx, image, image_blocks, dirs, ndirs, queries, names, nq,
+    # mode, entries, entries_bytes, block_status, dir_flags, hits, counts, file_counts, write_back[, stream])
+    L.ppfs_ecc_lookup_plan.restype = c_int
+    L.ppfs_ecc_lookup_plan.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
+    L.ppfs_ecc_lookup_device.restype = c_int
+    L.ppfs_ecc_lookup_device.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int,
+                                         c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]
+    L.ppfs_ecc_lookup_host.restype = c_int
+    L.ppfs_ecc_lookup_host.argtypes = list(L.ppfs_ecc_lookup_device.argtypes[:-1])
     L.ppfs_vote3_device.restype = c_int
     L.ppfs_vote3_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]
     L.ppfs_copy_device.restype = c_int

@@ -26,8 +26,8 @@ from typing import Generic, List, Optional, Tuple, TypeVar
 
 import numpy as np
 
-from ._native import (ECC_CRC, ECC_HAMMING, ECC_NONE, ECC_PARITY, ECC_REED_SOLOMON, EXTENT_DTYPE, FILE_DTYPE, INODE_META_DTYPE, INODE_TABLE_DTYPE, STATUS_CORRECTED,
-                      STATUS_CORRECTION_ERROR, STATUS_NOT_ALLOCATED, STATUS_OK, STATUS_OUT_OF_BOUNDS)
+from ._native import (ECC_CRC, ECC_HAMMING, ECC_NONE, ECC_PARITY, ECC_REED_SOLOMON, EXTENT_DTYPE, FILE_DTYPE, INODE_META_DTYPE, INODE_TABLE_DTYPE, LOOKUP_QUERY_DTYPE, STATUS_CORRECTED,
+                      STATUS_CORRECTION_ERROR, STATUS_NOT_ALLOCATED, STATUS_NOT_FOUND, STATUS_OK, STATUS_OUT_OF_BOUNDS, EccError)
 from .ecc import EccEngine, ScrubCounts
 
 MAX_BLOCK_SIZE = 4096  # iblock_device.hpp:3
@@ -56,6 +56,7 @@ class FsError(enum.IntEnum):  # lib/common/include/ppfs/common/types.hpp:11-80 (
     Disk_InvalidRequest = 10
     Disk_IOError = 11
     FileIO_OutOfBounds = 12
+    PpFS_NotFound = 19
     InodeManager_NotFound = 26
 
 
@@ -566,6 +567,69 @@ class IBlockDevice:
                 continue
             r = self._inode_write(table_block, i, rec[j].tobytes())
             out.append(None if r else r.error())
+        return out
+
+    # look up names in directories (include/ppfs_ecc.h ppfs_ecc_lookup_*): `dirs` is an array of FILE_DTYPE records,
+    # `queries` one of LOOKUP_QUERY_DTYPE (dir: a number into dirs), `names` the queries' 128-byte name records (an
+    # (n, 128) uint8 array; unused in inode mode).  The loop is the definition -- DirectoryManager::getInodeByName
+    # (directory_manager.cpp:135-163) for mode 0, removeEntry's search (:67-90) up to and including the found_entry
+    # decision for mode 1, both over _readDirectoryData (:165-187), a readFile of at most 256 entries.  DEVIATION: an
+    # entry whose 124 name bytes hold no NUL matches nothing (the reference's strlen would run on).  The codecs override
+    # it with one engine call.
+    DIR_ENTRY_BYTES, DIR_ENTRY_BATCH = 128, 256
+
+    @staticmethod
+    def _c_string(b: bytes, cap: int) -> Optional[bytes]:
+        """The bytes before the first NUL among the first cap bytes; None when there is no NUL."""
+        at = bytes(b[:cap]).find(b"\0")
+        return None if at < 0 else bytes(b[:at])
+
+    def _read_directory_data(self, dir_inode, offset: int, size: int):  # :165-187
+        max_entries = int(dir_inode["file_size"][0]) // self.DIR_ENTRY_BYTES
+        if offset >= max_entries:
+            return [], None
+        size = min(size, max_entries - offset)
+        data, err = self.read_file(dir_inode, offset * self.DIR_ENTRY_BYTES, size * self.DIR_ENTRY_BYTES)
+        if err is not None:
+            return None, err
+        E = self.DIR_ENTRY_BYTES
+        return [data[E * i:E * i + E] for i in range(len(data) // E)], None
+
+    def lookup(self, dirs, queries, names=None, mode: int = 0) -> List[Tuple[Optional[int], Optional[int], Optional[FsError]]]:
+        """Per query (inode, entry, None), or (None, None, error): the failing block's FsError, PpFS_NotFound (mode 0)
+        or DirectoryManager_NotFound (mode 1); DirectoryManager_InvalidRequest for a `dir` at or past the directories."""
+        dirs = np.asarray(dirs).reshape(-1)
+        out = []
+        for q, query in enumerate(np.asarray(queries).reshape(-1)):
+            if int(query["dir"]) >= dirs.size:  # names no directory of the call
+                out.append((None, None, FsError.DirectoryManager_InvalidRequest))
+                continue
+            dir_inode, key = dirs[int(query["dir"]):int(query["dir"]) + 1], int(query["key"])
+            name = None
+            if mode == 0:
+                name = self._c_string(bytes(np.asarray(names[q], dtype=np.uint8).tobytes()), 128)
+                if name is not None and len(name) >= 124:
+                    name = None  # matches nothing
+            num_entries = int(dir_inode["file_size"][0]) // self.DIR_ENTRY_BYTES
+            checked, found, error = 0, None, None
+            while checked < num_entries:
+                entries, error = self._read_directory_data(dir_inode, checked, self.DIR_ENTRY_BATCH)
+                if error is not None:
+                    break
+                for i, e in enumerate(entries):  # _findEntryByName (:189-199) / _findEntryByInode (:201-210)
+                    inode = int.from_bytes(e[:4], "little")
+                    if (mode == 0 and name is not None and self._c_string(e[4:], 124) == name) or (mode != 0 and inode == key):
+                        found = (inode, checked + i)
+                        break
+                if found is not None:
+                    break
+                checked += len(entries)
+            if error is not None:
+                out.append((None, None, error))
+            elif found is None:
+                out.append((None, None, FsError.PpFS_NotFound if mode == 0 else FsError.DirectoryManager_NotFound))
+            else:
+                out.append((found[0], found[1], None))
         return out
 
 
@@ -1166,6 +1230,86 @@ class _EngineDevice(IBlockDevice):
                 out.append((None, FsError.InodeManager_NotFound))
             else:
                 out.append((None, FsError(st)))
+        return out
+
+    def lookup(self, dirs, queries, names=None, mode: int = 0) -> List[Tuple[Optional[int], Optional[int], Optional[FsError]]]:
+        """IBlockDevice.lookup as ONE EccEngine.lookup_host call on the disk image (after a walk without write-back,
+        EccEngine.files_blocks_host, that tells which image block each file block and index block is, for the log).
+        Results equal the loop's for every query.  The log holds the loop's events first and in the loop's order --
+        queries in order, each block at its first read, an index block in front of the first file block under it.
+        The engine reads every directory whole, so directory blocks that no query's loop reached -- behind last(B), or
+        behind a failing block -- may additionally have been corrected: they are logged after the loop's events in
+        (directory, block) order, and the disk is the loop's with exactly those blocks corrected as well."""
+        image, ds = self._mapped_image(), self._ds
+        dirs = np.ascontiguousarray(dirs, dtype=FILE_DTYPE).reshape(-1)
+        q = np.ascontiguousarray(queries, dtype=LOOKUP_QUERY_DTYPE).reshape(-1)
+        if image is None or ds == 0 or ds > 0xFFFF or q.size == 0 or int(q["dir"].max()) >= dirs.size:
+            return super().lookup(dirs, queries, names, mode)
+        eng = self._engine
+        try:
+            slots, totals = eng.lookup_plan(dirs)
+        except EccError:  # a directory past its tree's capacity: the loop is the definition
+            return super().lookup(dirs, queries, names, mode)
+        wb = eng.ecc_type in (ECC_REED_SOLOMON, ECC_HAMMING)
+        E, batch = self.DIR_ENTRY_BYTES, self.DIR_ENTRY_BATCH
+        n_entries = dirs["file_size"].astype(np.int64) // E
+        ranges = np.stack([np.zeros(dirs.size, np.uint64), (n_entries * E).astype(np.uint64)], axis=1)
+        nb, T = int(totals["blocks"]), int(totals["tree_blocks"])
+        ix, ps = np.zeros(nb, dtype=np.uint32), np.zeros(nb, dtype=np.uint8)
+        ti, ts = np.zeros(T, dtype=np.uint32), np.zeros(T, dtype=np.uint8)
+        if nb:
+            eng.files_blocks_host(image, dirs, ranges, ix, ps, ti, ts, write_back=False)
+        entries, bst = np.zeros(int(totals["bytes"]), dtype=np.uint8), np.zeros(nb, dtype=np.uint8)
+        nm = None if mode != 0 else np.ascontiguousarray(np.asarray(names, dtype=np.uint8).reshape(q.size, 128))
+        hits, _, _ = eng.lookup_host(image, dirs, q, nm, mode, entries, bst, write_back=wb)
+        # per directory, per file block: the tree entries above it, outermost first, as indices into ti / ts
+        ipb, above = ds // 4, []
+        for d, s in enumerate(slots):
+            levels, rows = [{}, {}, {}], []
+            for j in range(int(s["blocks"])):
+                p = file_path_of(j, ipb)
+                rows.append([int(s["tree_pos"][lv]) + levels[lv].setdefault(p[:lv + 1], len(levels[lv])) for lv in range(p[0])])
+            above.append(rows)
+        logged = set()
+
+        def walk(d, upto):  # the reads of file blocks [0, upto] of directory d, until the first failing one
+            at = int(slots[d]["block_pos"])
+            for j in range(min(upto + 1, int(slots[d]["blocks"]))):
+                for k in above[d][j]:
+                    if ts[k] in (STATUS_CORRECTION_ERROR, STATUS_OUT_OF_BOUNDS):
+                        return
+                    if ts[k] == STATUS_CORRECTED and ("t", k) not in logged:
+                        logged.add(("t", k))
+                        self._log(int(ti[k]))
+                if bst[at + j] in (STATUS_CORRECTION_ERROR, STATUS_OUT_OF_BOUNDS):
+                    return
+                if bst[at + j] == STATUS_CORRECTED and ("d", at + j) not in logged:
+                    logged.add(("d", at + j))
+                    self._log(int(ix[at + j]))
+
+        out = []
+        for h, d in zip(hits, (int(x) for x in q["dir"])):
+            n, st = int(n_entries[d]), int(h["status"])
+            if n:
+                B = int(h["entry"]) // batch if st == STATUS_OK else (n - 1) // batch
+                walk(d, (min((B + 1) * batch, n) * E - 1) // ds)
+            if st == STATUS_OK:
+                out.append((int(h["inode"]), int(h["entry"]), None))
+            elif st == STATUS_NOT_FOUND:
+                out.append((None, None, FsError.PpFS_NotFound if mode == 0 else FsError.DirectoryManager_NotFound))
+            else:
+                out.append((None, None, FsError(st)))
+        if wb:  # what the engine corrected beyond the loop's reach
+            for d, s in enumerate(slots):
+                at = int(s["block_pos"])
+                for j in range(int(s["blocks"])):
+                    for k in above[d][j]:
+                        if ts[k] == STATUS_CORRECTED and ("t", k) not in logged:
+                            logged.add(("t", k))
+                            self._log(int(ti[k]))
+                    if bst[at + j] == STATUS_CORRECTED and ("d", at + j) not in logged:
+                        logged.add(("d", at + j))
+                        self._log(int(ix[at + j]))
         return out
 
     def write_inodes(self, table, numbers, files, meta) -> List[Optional[FsError]]:

@@ -577,7 +577,7 @@ extern "C" const char* ppfs_ecc_list_encode_kernel_name(const ppfs_ecc_ctx* c)
 #define PPFS_DBG_UNITS(X) X(ppfs_dbg_faults_rs_t2) X(ppfs_dbg_faults_rs_t4) X(ppfs_dbg_faults_rs_t6) \
     X(ppfs_dbg_faults_rs_t8) X(ppfs_dbg_faults_rs_t10) X(ppfs_dbg_faults_rs_t16) X(ppfs_dbg_faults_rs_t32)   \
     X(ppfs_dbg_faults_rs_generic) X(ppfs_dbg_faults_bit) X(ppfs_dbg_faults_bitfast) X(ppfs_dbg_faults_vote) \
-    X(ppfs_dbg_alloc_faults) X(ppfs_dbg_files_faults) X(ppfs_dbg_inode_faults)
+    X(ppfs_dbg_alloc_faults) X(ppfs_dbg_files_faults) X(ppfs_dbg_inode_faults) X(ppfs_dbg_lookup_faults)
 #define PPFS_DBG_DECL(f) extern "C" long long f(void);
 PPFS_DBG_UNITS(PPFS_DBG_DECL)
 extern "C" long long ppfs_ecc_debug_faults(void)

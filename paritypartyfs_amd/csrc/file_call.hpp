@@ -2,6 +2,8 @@
 // of a call whose arguments are checked and whose plan is built.  Defined in files_path.cpp.
 #pragma once
 
+#include <functional>
+
 #include "ctx.hpp"
 #pragma GCC visibility push(hidden) // the plan's out-of-line inlines are no part of the library's ABI
 #include "files_plan.hpp"
@@ -38,6 +40,12 @@ struct FileCall {
 // queues the whole walk on the stream, in the context's scrub scratch; queued: call_queued's label
 int file_call_device(const FileCall& a, void* stream, const char* queued);
 int file_call_host(const FileCall& a);
+
+// Host-built tables into device memory on s, the way of every call that plans on the host (the file batch, the
+// directory lookups): fill() writes `bytes` bytes into a page-locked buffer, one copy takes them to d_dst, and the
+// buffer returns to the cache once an event recorded behind that copy has completed -- looked at by every later
+// staged call, drained at destroy.  The caller's stream is never waited for.  who: the call, for the error text
+int stage_upload(ppfs_ecc_ctx* c, uint8_t* d_dst, size_t bytes, hipStream_t s, const char* who, const std::function<void(uint8_t*)>& fill);
 
 } // namespace ppfs
 #pragma GCC visibility pop

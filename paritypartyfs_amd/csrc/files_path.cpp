@@ -183,27 +183,6 @@ size_t scratch_layout(const PlanView& p, size_t table_bytes, size_t ds, size_t p
     return bytes;
 }
 
-// page-locked buffers of earlier batch calls whose copy has completed go back to the cache
-void reap_stages(ppfs_ecc_ctx* c)
-{
-    auto& v = c->files_stage;
-    for (size_t i = 0; i < v.size();) {
-        const hipError_t e = hipEventQuery(v[i].done);
-        if (e == hipErrorNotReady) {
-            ++i;
-            continue;
-        }
-        if (e != hipSuccess) { // a failed query says nothing about the copy: wait for it
-            (void)hipGetLastError();
-            (void)hipEventSynchronize(v[i].done);
-        }
-        (void)hipEventDestroy(v[i].done);
-        pin_free(v[i].buf, v[i].bytes, kPinStage);
-        v[i] = v.back();
-        v.pop_back();
-    }
-}
-
 // what a failed launch is reported under: the texts of the single-file calls and of the batch calls
 struct Steps {
     const char *expand, *extents, *tree_merge, *blocks_merge, *read_merge, *write_merge, *written_init;
@@ -236,10 +215,8 @@ struct DeviceWalk {
     // buffer that outlives the copy
     int setup(size_t piece, bool io)
     {
-        if (!one) {
-            reap_stages(a.c);
+        if (!one)
             tl = table_layout(plan);
-        }
         uint8_t* scratch = nullptr;
         int r = scrub_scratch(a.c, scratch_layout(plan, tl.bytes, ds, piece, io, nullptr, nullptr), s(), &scratch);
         if (r)
@@ -249,32 +226,11 @@ struct DeviceWalk {
     }
     int upload()
     {
-        ppfs_ecc_ctx* c = a.c;
-        size_t cap = 4096; // few distinct sizes, so that the cache of page-locked buffers hits
-        while (cap < tl.bytes)
-            cap *= 2;
-        uint8_t* pin = nullptr;
-        if (pin_alloc((void**)&pin, cap, kPinStage) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(PPFS_ECC_ENOMEM, "files: page-locked staging of the tables");
-        }
-        std::memcpy(pin + tl.recs, plan.recs, plan.nfiles * sizeof(FileRec));
-        for (int l = 0; l < filesplan::LEVELS; ++l)
-            std::memcpy(pin + tl.rows[l], plan.rows[l], (plan.nrows[l] + 1) * sizeof(Row));
-        hipError_t e = dma_async(x.tables, pin, tl.bytes, hipMemcpyHostToDevice, s());
-        hipEvent_t done = nullptr;
-        if (e == hipSuccess && (e = hipEventCreateWithFlags(&done, hipEventDisableTiming)) == hipSuccess
-            && (e = hipEventRecord(done, s())) == hipSuccess) {
-            c->files_stage.push_back(ppfs_ecc_ctx::FilesStage { pin, cap, done });
-            return 0;
-        }
-        // nothing to tell the copy's end by: drain the stream, then the buffer is free
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(s());
-        if (done)
-            (void)hipEventDestroy(done);
-        pin_free(pin, cap, kPinStage);
-        return fail(PPFS_ECC_EHIP, "files: table upload", e);
+        return stage_upload(a.c, x.tables, tl.bytes, s(), "files", [&](uint8_t* pin) {
+            std::memcpy(pin + tl.recs, plan.recs, plan.nfiles * sizeof(FileRec));
+            for (int l = 0; l < filesplan::LEVELS; ++l)
+                std::memcpy(pin + tl.rows[l], plan.rows[l], (plan.nrows[l] + 1) * sizeof(Row));
+        });
     }
     int expand(int level, uint64_t e0, uint64_t n, uint32_t* pointer, uint8_t* inherited) const
     {
@@ -357,6 +313,55 @@ void slots_out(const Plan& plan, ppfs_ecc_files_slot* slots, ppfs_ecc_files_tota
 }
 
 } // namespace
+
+// page-locked buffers of earlier staged calls whose copy has completed go back to the cache
+static void reap_stages(ppfs_ecc_ctx* c)
+{
+    auto& v = c->files_stage;
+    for (size_t i = 0; i < v.size();) {
+        const hipError_t e = hipEventQuery(v[i].done);
+        if (e == hipErrorNotReady) {
+            ++i;
+            continue;
+        }
+        if (e != hipSuccess) { // a failed query says nothing about the copy: wait for it
+            (void)hipGetLastError();
+            (void)hipEventSynchronize(v[i].done);
+        }
+        (void)hipEventDestroy(v[i].done);
+        pin_free(v[i].buf, v[i].bytes, kPinStage);
+        v[i] = v.back();
+        v.pop_back();
+    }
+}
+
+int ppfs::stage_upload(ppfs_ecc_ctx* c, uint8_t* d_dst, size_t bytes, hipStream_t s, const char* who, const std::function<void(uint8_t*)>& fill)
+{
+    reap_stages(c);
+    size_t cap = 4096; // few distinct sizes, so that the cache of page-locked buffers hits
+    while (cap < bytes)
+        cap *= 2;
+    uint8_t* pin = nullptr;
+    if (pin_alloc((void**)&pin, cap, kPinStage) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PPFS_ECC_ENOMEM, (std::string(who) + ": page-locked staging of the tables").c_str());
+    }
+    fill(pin);
+    hipError_t e = dma_async(d_dst, pin, bytes, hipMemcpyHostToDevice, s);
+    hipEvent_t done = nullptr;
+    if (e == hipSuccess && (e = hipEventCreateWithFlags(&done, hipEventDisableTiming)) == hipSuccess
+        && (e = hipEventRecord(done, s)) == hipSuccess) {
+        c->files_stage.push_back(ppfs_ecc_ctx::FilesStage { pin, cap, done });
+        return 0;
+    }
+    // nothing to tell the copy's end by: drain the stream, then the buffer is free
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(s);
+    if (done)
+        (void)hipEventDestroy(done);
+    pin_free(pin, cap, kPinStage);
+    return fail(PPFS_ECC_EHIP, (std::string(who) + ": table upload").c_str(), e);
+}
 
 int ppfs::file_call_device(const FileCall& a, void* stream, const char* queued)
 {

@@ -1,8 +1,9 @@
 // kernels.hpp -- the host-callable launchers of the kernel translation units, declared once:
 // rs_kernels.hip (Reed-Solomon and its servers), bit_kernels.hip (CRC, Hamming, parity and the bit
 // server) vote.hip (vote, copy, gather, patch list, inject, flag, block lists), alloc_scan.hip (bitmap
-// expansion, scrub tally), files_walk.hip (the file walk's expansion, extents and merges) and
-// inode_walk.hip (the inode reads' extents and merge, the inode writes' election, overlay and statuses).
+// expansion, scrub tally), files_walk.hip (the file walk's expansion, extents and merges),
+// inode_walk.hip (the inode reads' extents and merge, the inode writes' election, overlay and statuses) and
+// dir_walk.hip (the directory lookups' match and finish).
 // The three table-sizing functions are in host_tables.hpp, beside the builders that use them.
 #pragma once
 
@@ -161,4 +162,16 @@ hipError_t ppfs_inode_overlay_launch(const uint32_t* ino, const uint8_t* bm, con
 hipError_t ppfs_inode_write_status_launch(const uint32_t* ino, const uint8_t* bm, const uint8_t* bst, const uint8_t* wst,
     uint64_t n, const ppfs_ecc_inode_table* table, uint64_t ds, uint32_t* tab, uint32_t cap, uint8_t* status, uint8_t* piece_status,
     unsigned long long* counts, hipStream_t s);
+// the directory lookups (lookup_path.cpp; dir_walk.hip, the rule in lookup_plan.hpp).  dirs: ndirs lookupplan::DirRec,
+// queries: nq lookupplan::Query, both in device memory, 8-byte aligned; names: nq records of 128 bytes at any alignment
+// (mode 1: not read, may be null); entries (entries_bytes) and block_status (total_blocks) as ppfs_ecc_read_files_*
+// left them; hits: nq ppfs_ecc_lookup_hit, 4-byte aligned.
+// match: lowers the `entry` word of every query's hit record, set to 0xFFFFFFFF on the stream before, to its first
+// matching entry; max_entries: the longest directory's entries (0: no launch).
+// finish: the failure rule over the block statuses -> the hit records and the counts (8-byte aligned, may be null).
+hipError_t ppfs_lookup_match_launch(const void* dirs, uint64_t ndirs, const void* queries, const uint8_t* names, uint64_t nq,
+    int mode, const uint8_t* entries, uint64_t entries_bytes, uint64_t max_entries, void* hits, hipStream_t s);
+hipError_t ppfs_lookup_finish_launch(const void* dirs, uint64_t ndirs, const void* queries, uint64_t nq, const uint8_t* entries,
+    uint64_t entries_bytes, const uint8_t* block_status, uint64_t total_blocks, uint64_t ds, void* hits, unsigned long long* counts,
+    hipStream_t s);
 }

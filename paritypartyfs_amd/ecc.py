@@ -819,6 +819,100 @@ class EccEngine:
             self._u32_ptr(status), self._u32_ptr(piece_status), byref(rec), int(bool(write_back))))
         return InodeCounts(*[int(getattr(rec, k)) for k in INODE_COUNT_FIELDS])
 
+    # ---------------- look up names in directories (ppfs_ecc_lookup_*) ----------------
+    # DirectoryManager::getInodeByName (mode 0) or the search of removeEntry (mode 1) over a batch: `dirs` is a
+    # FILE_DTYPE array in host memory, `queries` a LOOKUP_QUERY_DTYPE array in host memory, `names` the nq 128-byte name
+    # records (lookup_names packs them).  Every directory is read once and whole: `entries` and `block_status`, sized by
+    # lookup_plan, are the call's working memory and hold the entries and final block statuses afterwards as read_files
+    # leaves them, so `entries` is a ready `numbers` source at stride 128 for read_inodes.
+    @staticmethod
+    def lookup_names(names) -> np.ndarray:
+        """An (n, 128) uint8 array of name records out of bytes / str names of at most 123 bytes."""
+        out = np.zeros((len(names), _native.LOOKUP_NAME_BYTES), dtype=np.uint8)
+        for i, name in enumerate(names):
+            b = name.encode() if isinstance(name, str) else bytes(name)
+            if len(b) > 123 or 0 in b:
+                raise ValueError("a name holds at most 123 bytes and no NUL")
+            out[i, :len(b)] = np.frombuffer(b, dtype=np.uint8)
+        return out
+
+    def lookup_plan(self, dirs):
+        """(slots, totals) of the directories' entries (ppfs_ecc_lookup_plan): files_plan over the ranges
+        (0, 128 * entries).  totals["bytes"] sizes the entries buffer, totals["blocks"] the block statuses.  No GPU work."""
+        f, _ = self._files(dirs, None)
+        slots, totals = np.zeros(f.size, _native.FILES_SLOT_DTYPE), np.zeros(1, _native.FILES_TOTALS_DTYPE)
+        check(lib().ppfs_ecc_lookup_plan(self._h, f.ctypes.data if f.size else None, f.size,
+                                         slots.ctypes.data if f.size else None, totals.ctypes.data))
+        return slots, totals[0]
+
+    def _lookup_check(self, kind, image, dirs, queries, names, mode, entries, block_status, dir_flags):
+        f, _ = self._files(dirs, None)
+        q = np.ascontiguousarray(queries)
+        if q.dtype != _native.LOOKUP_QUERY_DTYPE or q.ndim > 1:
+            raise ValueError("queries: a 1-D array of LOOKUP_QUERY_DTYPE records")
+        q = q.reshape(-1)
+        if mode not in (0, 1):
+            raise ValueError("mode: 0 (name) or 1 (inode number)")
+        if image is None:
+            raise ValueError("image: required")
+        _, totals = self.lookup_plan(f)
+        _need("image", image, 0, kind)
+        if mode == 0:
+            if names is None and q.size:
+                raise ValueError("names: required in name mode")
+            _need("names", names, q.size * _native.LOOKUP_NAME_BYTES, kind)
+        _need("entries", entries, int(totals["bytes"]), kind)
+        _need("block_status", block_status, int(totals["blocks"]), kind)
+        _ptr(image), _ptr(names), _ptr(entries), _ptr(block_status)  # contiguous uint8
+        if dir_flags is not None:
+            if kind == "device":
+                import torch
+
+                if isinstance(dir_flags, np.ndarray) or not getattr(dir_flags, "is_cuda", False) or dir_flags.dtype != torch.int32 \
+                        or not dir_flags.is_contiguous() or dir_flags.numel() < f.size:
+                    raise ValueError(f"dir_flags: a contiguous CUDA torch.int32 tensor of >= {f.size} elements")
+            elif not isinstance(dir_flags, np.ndarray) or dir_flags.dtype != np.uint32 or not dir_flags.flags["C_CONTIGUOUS"] \
+                    or dir_flags.size < f.size:
+                raise ValueError(f"dir_flags: a C-contiguous numpy uint32 array of >= {f.size} elements")
+        return f, q, _size(image) // self.raw_block_size
+
+    def lookup(self, image, dirs, queries, names, mode: int, entries, block_status, hits, dir_flags=None, counts=None,
+               file_counts=None, write_back: bool = True, stream=None):
+        """Device lookup (ppfs_ecc_lookup_device).  names: a CUDA uint8 tensor of 128 bytes per query (mode 1: None);
+        entries, block_status: CUDA uint8 tensors, required; hits: a contiguous CUDA int32 tensor of 4 words per query
+        (LOOKUP_HIT_DTYPE once on the host).  counts / file_counts: None, True or a CUDA int64 tensor of 8 words
+        (LOOKUP_COUNT_FIELDS / FILE_COUNT_FIELDS).  Returns (counts, file_counts).  Never synchronises."""
+        f, q, blocks = self._lookup_check("device", image, dirs, queries, names, mode, entries, block_status, dir_flags)
+        if entries is None or block_status is None:
+            raise ValueError("entries and block_status: the call's working memory, required in the device form")
+        import torch
+
+        if hits is None or isinstance(hits, np.ndarray) or not getattr(hits, "is_cuda", False) or hits.dtype != torch.int32 \
+                or not hits.is_contiguous() or hits.numel() < 4 * q.size:
+            raise ValueError(f"hits: a contiguous CUDA torch.int32 tensor of >= {4 * q.size} elements")
+        d_counts, d_file_counts = self._device_counts(counts), self._device_counts(file_counts)
+        check(lib().ppfs_ecc_lookup_device(
+            self._h, _ptr(image), blocks, f.ctypes.data if f.size else None, f.size, q.ctypes.data if q.size else None,
+            _ptr(names), q.size, int(mode), _ptr(entries), _size(entries), _ptr(block_status), self._u32_ptr(dir_flags),
+            hits.data_ptr(), None if d_counts is None else d_counts.data_ptr(),
+            None if d_file_counts is None else d_file_counts.data_ptr(), int(bool(write_back)), _stream_handle(stream)))
+        return d_counts, d_file_counts
+
+    def lookup_host(self, image: np.ndarray, dirs, queries, names, mode: int = 0, entries: Optional[np.ndarray] = None,
+                    block_status: Optional[np.ndarray] = None, dir_flags: Optional[np.ndarray] = None,
+                    write_back: bool = True):
+        """Host lookup (ppfs_ecc_lookup_host): (hits, LookupCounts, FileCounts), hits a LOOKUP_HIT_DTYPE array.
+        entries and block_status may be None: the call then uses buffers of its own."""
+        f, q, blocks = self._lookup_check("host", image, dirs, queries, names, mode, entries, block_status, dir_flags)
+        hits = np.zeros(q.size, _native.LOOKUP_HIT_DTYPE)
+        rec, frec = _native.LookupCounts(), _native.FileCounts()
+        check(lib().ppfs_ecc_lookup_host(
+            self._h, _ptr(image), blocks, f.ctypes.data if f.size else None, f.size, q.ctypes.data if q.size else None,
+            _ptr(names), q.size, int(mode), _ptr(entries), 0 if entries is None else _size(entries), _ptr(block_status),
+            self._u32_ptr(dir_flags), hits.ctypes.data if q.size else None, byref(rec), byref(frec), int(bool(write_back))))
+        return (hits, LookupCounts(*[int(getattr(rec, k)) for k in LOOKUP_COUNT_FIELDS]),
+                FileCounts(*[int(getattr(frec, k)) for k in FILE_COUNT_FIELDS]))
+
 
 # ppfs_ecc_scrub_counts: the host forms return it as this tuple, the device forms as a CUDA int64 tensor
 # in the same field order (ScrubCounts(*tensor.tolist()) after synchronising)
@@ -835,6 +929,11 @@ INODE_COUNT_FIELDS = ("ok", "corrected", "failed", "out_of_range", "not_allocate
 InodeCounts = collections.namedtuple("InodeCounts", INODE_COUNT_FIELDS)
 INODE_TABLE_DTYPE = _native.INODE_TABLE_DTYPE
 INODE_META_DTYPE = _native.INODE_META_DTYPE
+# ppfs_ecc_lookup_counts, likewise: the four categories, then the four reserved words
+LOOKUP_COUNT_FIELDS = ("found", "not_found", "failed", "out_of_range", "reserved0", "reserved1", "reserved2", "reserved3")
+LookupCounts = collections.namedtuple("LookupCounts", LOOKUP_COUNT_FIELDS)
+LOOKUP_QUERY_DTYPE = _native.LOOKUP_QUERY_DTYPE
+LOOKUP_HIT_DTYPE = _native.LOOKUP_HIT_DTYPE
 
 
 class EccGroup:
@@ -981,4 +1080,4 @@ def crc_implicit_to_explicit(p: int) -> int:
     return int(lib().ppfs_ecc_crc_implicit_to_explicit(ctypes.c_uint64(p)))
 
 
-__all__ = ["EccEngine", "ScrubCounts", "SCRUB_COUNT_FIELDS", "FileCounts", "FILE_COUNT_FIELDS", "FILE_DTYPE", "InodeCounts", "INODE_COUNT_FIELDS", "INODE_TABLE_DTYPE", "INODE_META_DTYPE", "crc_implicit_to_explicit", "device_copy", "inject_bytes", "pinned", "vote3", "vote3_host", "_native"]
+__all__ = ["EccEngine", "ScrubCounts", "SCRUB_COUNT_FIELDS", "FileCounts", "FILE_COUNT_FIELDS", "FILE_DTYPE", "InodeCounts", "INODE_COUNT_FIELDS", "INODE_TABLE_DTYPE", "INODE_META_DTYPE", "LookupCounts", "LOOKUP_COUNT_FIELDS", "LOOKUP_QUERY_DTYPE", "LOOKUP_HIT_DTYPE", "crc_implicit_to_explicit", "device_copy", "inject_bytes", "pinned", "vote3", "vote3_host", "_native"]
