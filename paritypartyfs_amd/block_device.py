@@ -1177,59 +1177,67 @@ class _EngineDevice(IBlockDevice):
                 results[f] = (out[pos:pos + n].tobytes(), None)
         return results
 
-    def read_inodes(self, table, numbers) -> List[Tuple[Optional[np.void], Optional[FsError]]]:
-        """IBlockDevice.read_inodes as ONE engine call on the disk image (EccEngine.read_inodes_host).  Records and
-        errors equal the loop's.  The correction log equals it too: inodes in batch order, the bitmap block then the
-        pieces up to the first failing one, each block that some read of the call corrected logged where the loop
-        first touches it.  The pieces behind an inode's failing piece, which the loop does not read, have been read
-        (and corrected) as well."""
-        image = self._mapped_image()
-        nums = np.ascontiguousarray(np.asarray(numbers).reshape(-1), dtype=np.uint32)
-        if image is None or self._ds == 0 or self._ds > 0xFFFF or nums.size == 0:
-            return super().read_inodes(table, numbers)
-        eng, ds = self._engine, self._ds
-        t = np.ascontiguousarray(np.asarray(table).reshape(-1)[:1], dtype=INODE_TABLE_DTYPE)
-        table_block, bitmap_block, total = int(t["table_block"][0]), int(t["bitmap_block"][0]), int(t["total_inodes"][0])
-        n, W = int(nums.size), 1 + eng.inode_max_pieces
-        files, meta = np.zeros(n, dtype=FILE_DTYPE), np.zeros(n, dtype=INODE_META_DTYPE)
-        status, pieces = np.zeros(n, dtype=np.uint8), np.zeros(n * W, dtype=np.uint8)
-        wb = eng.ecc_type in (ECC_REED_SOLOMON, ECC_HAMMING)
-        eng.read_inodes_host(image, t, nums, files=files, meta=meta, status=status, piece_status=pieces, write_back=wb)
-        pieces = pieces.reshape(n, W)
-        # the blocks some read of the call corrected, then the loop's order of touching them
-        reads = []  # per inode: (block, status) of the reads the loop makes, in its order
-        for j, i in enumerate(int(x) for x in nums):
+    def _inode_log(self, t, nums, pieces) -> None:
+        """The correction log of an inode call from its piece_status (rows of 1 + K slots), as the loop writes it:
+        inodes in batch order, the bitmap block then the pieces up to the first failing one, each block that some
+        access of the call corrected logged where the loop first touches it."""
+        table_block, bitmap_block, ds = int(t["table_block"][0]), int(t["bitmap_block"][0]), self._ds
+        touches = []  # per inode: (block, status) of the accesses the loop makes, in its order
+        for i, ps in zip((int(x) for x in nums), pieces):
             mine = []
-            if pieces[j, 0] != 255:
-                mine.append((bitmap_block + (i // 8) // ds, int(pieces[j, 0])))
-            for k in range(W - 1):
-                if pieces[j, 1 + k] == 255:
+            if ps[0] != 255:
+                mine.append((bitmap_block + (i // 8) // ds, int(ps[0])))
+            for k, st in enumerate(ps[1:]):
+                if st == 255:
                     break
-                mine.append((table_block + 81 * i // ds + k, int(pieces[j, 1 + k])))
-            reads.append(mine)
-        corrected = {b for mine in reads for b, st in mine if st == STATUS_CORRECTED}
+                mine.append((table_block + 81 * i // ds + k, int(st)))
+            touches.append(mine)
+        corrected = {b for mine in touches for b, st in mine if st == STATUS_CORRECTED}
         logged = set()
-        out = []
-        for j, i in enumerate(int(x) for x in nums):
-            for b, st in reads[j]:
+        for mine in touches:
+            for b, st in mine:
                 if st in (STATUS_CORRECTION_ERROR, STATUS_OUT_OF_BOUNDS):
                     break
                 if b in corrected and b not in logged:
                     logged.add(b)
                     self._log(b)
-            st = int(status[j])
-            if st in (STATUS_OK, STATUS_CORRECTED):
+
+    @staticmethod
+    def _inode_error(number: int, status: int, total: int) -> Optional[FsError]:
+        """An inode call's status as the loop's result: None, or the loop's error."""
+        if status in (STATUS_OK, STATUS_CORRECTED):
+            return None
+        if number >= total:
+            return FsError.Bitmap_IndexOutOfRange
+        return FsError.InodeManager_NotFound if status == STATUS_NOT_ALLOCATED else FsError(status)
+
+    def read_inodes(self, table, numbers) -> List[Tuple[Optional[np.void], Optional[FsError]]]:
+        """IBlockDevice.read_inodes as ONE engine call on the disk image (EccEngine.read_inodes_host).  Records and
+        errors equal the loop's, and so does the correction log (_inode_log).  The pieces behind an inode's failing
+        piece, which the loop does not read, have been read (and corrected) as well."""
+        image = self._mapped_image()
+        nums = np.ascontiguousarray(np.asarray(numbers).reshape(-1), dtype=np.uint32)
+        if image is None or self._ds == 0 or self._ds > 0xFFFF or nums.size == 0:
+            return super().read_inodes(table, numbers)
+        eng = self._engine
+        t = np.ascontiguousarray(np.asarray(table).reshape(-1)[:1], dtype=INODE_TABLE_DTYPE)
+        n, W, total = int(nums.size), 1 + eng.inode_max_pieces, int(t["total_inodes"][0])
+        files, meta = np.zeros(n, dtype=FILE_DTYPE), np.zeros(n, dtype=INODE_META_DTYPE)
+        status, pieces = np.zeros(n, dtype=np.uint8), np.zeros(n * W, dtype=np.uint8)
+        wb = eng.ecc_type in (ECC_REED_SOLOMON, ECC_HAMMING)
+        eng.read_inodes_host(image, t, nums, files=files, meta=meta, status=status, piece_status=pieces, write_back=wb)
+        self._inode_log(t, nums, pieces.reshape(n, W))
+        out = []
+        for j in range(n):
+            error = self._inode_error(int(nums[j]), int(status[j]), total)
+            rec = None
+            if error is None:
                 rec = np.zeros(1, dtype=INODE_DTYPE)
                 rec["time_creation"], rec["time_modified"], rec["type"] = meta["time_creation"][j], meta["time_modified"][j], meta["type"][j]
                 for name in FILE_DTYPE.names:
                     rec[name] = files[name][j]
-                out.append((rec[0], None))
-            elif i >= total:
-                out.append((None, FsError.Bitmap_IndexOutOfRange))
-            elif st == STATUS_NOT_ALLOCATED:
-                out.append((None, FsError.InodeManager_NotFound))
-            else:
-                out.append((None, FsError(st)))
+                rec = rec[0]
+            out.append((rec, error))
         return out
 
     def lookup(self, dirs, queries, names=None, mode: int = 0) -> List[Tuple[Optional[int], Optional[int], Optional[FsError]]]:
@@ -1314,17 +1322,15 @@ class _EngineDevice(IBlockDevice):
 
     def write_inodes(self, table, numbers, files, meta) -> List[Optional[FsError]]:
         """IBlockDevice.write_inodes as ONE engine call on the disk image (EccEngine.write_inodes_host).  Errors equal
-        the loop's.  The correction log equals it too: inodes in batch order, the bitmap block then the pieces up to
-        the first failing one, each block that the call corrected logged where the loop first touches it.  The pieces
-        behind an inode's failing piece, which the loop does not write, have been written as well."""
+        the loop's, and so does the correction log (_inode_log).  The pieces behind an inode's failing piece, which the
+        loop does not write, have been written as well."""
         image = self._mapped_image()
         nums = np.ascontiguousarray(np.asarray(numbers).reshape(-1), dtype=np.uint32)
         if image is None or self._ds == 0 or self._ds > 0xFFFF or nums.size == 0:
             return super().write_inodes(table, numbers, files, meta)
-        eng, ds = self._engine, self._ds
+        eng = self._engine
         t = np.ascontiguousarray(np.asarray(table).reshape(-1)[:1], dtype=INODE_TABLE_DTYPE)
-        table_block, bitmap_block, total = int(t["table_block"][0]), int(t["bitmap_block"][0]), int(t["total_inodes"][0])
-        n, W = int(nums.size), 1 + eng.inode_max_pieces
+        n, W, total = int(nums.size), 1 + eng.inode_max_pieces, int(t["total_inodes"][0])
         rec = self._inode_pack(files, meta, n)  # checks the sizes
         f = np.zeros(n, dtype=FILE_DTYPE)
         m = np.zeros(n, dtype=INODE_META_DTYPE)
@@ -1334,37 +1340,8 @@ class _EngineDevice(IBlockDevice):
         status, pieces = np.zeros(n, dtype=np.uint8), np.zeros(n * W, dtype=np.uint8)
         wb = eng.ecc_type in (ECC_REED_SOLOMON, ECC_HAMMING)
         eng.write_inodes_host(image, t, nums, f, m, status=status, piece_status=pieces, write_back=wb)
-        pieces = pieces.reshape(n, W)
-        touches = []  # per inode: (block, status) of the accesses the loop makes, in its order
-        for j, i in enumerate(int(x) for x in nums):
-            mine = []
-            if pieces[j, 0] != 255:
-                mine.append((bitmap_block + (i // 8) // ds, int(pieces[j, 0])))
-            for k in range(W - 1):
-                if pieces[j, 1 + k] == 255:
-                    break
-                mine.append((table_block + 81 * i // ds + k, int(pieces[j, 1 + k])))
-            touches.append(mine)
-        corrected = {b for mine in touches for b, st in mine if st == STATUS_CORRECTED}
-        logged = set()
-        out = []
-        for j, i in enumerate(int(x) for x in nums):
-            for b, st in touches[j]:
-                if st in (STATUS_CORRECTION_ERROR, STATUS_OUT_OF_BOUNDS):
-                    break
-                if b in corrected and b not in logged:
-                    logged.add(b)
-                    self._log(b)
-            st = int(status[j])
-            if st in (STATUS_OK, STATUS_CORRECTED):
-                out.append(None)
-            elif i >= total:
-                out.append(FsError.Bitmap_IndexOutOfRange)
-            elif st == STATUS_NOT_ALLOCATED:
-                out.append(FsError.InodeManager_NotFound)
-            else:
-                out.append(FsError(st))
-        return out
+        self._inode_log(t, nums, pieces.reshape(n, W))
+        return [self._inode_error(int(nums[j]), int(status[j]), total) for j in range(n)]
 
     def write_file(self, file, offset: int, data) -> Tuple[int, Optional[FsError]]:
         """IBlockDevice.write_file as write_files of one file."""

@@ -1,8 +1,9 @@
 #pragma once
-// inode_plan.hpp -- the arithmetic of the inode reads (inode_path.cpp, inode_walk.hip): where the reference's
-// InodeManager::get (lib/inode_manager/src/inode_manager.cpp:127-138) finds inode i, as plain numbers.  For host
-// and device alike, so the kernels, the host form and tests/cpp/test_inode_plan.cpp (the same plan against a
-// literal restatement of the reference's loops, under the sanitizers) decide identically.
+// inode_plan.hpp -- the arithmetic and the per-inode rule of the inode reads and writes (inode_path.cpp,
+// inode_walk.hip): where the reference's InodeManager::get and update (lib/inode_manager/src/inode_manager.cpp:127-159)
+// find inode i, and what they decide about it, as plain numbers.  For host and device alike, so the kernels, the host
+// forms and tests/cpp/test_inode_plan.cpp (the same plan against a literal restatement of the reference's loops, under
+// the sanitizers) decide identically.
 //
 // The packed Inode (inode.hpp:18-41) is INODE_BYTES = 81 bytes: time_creation [0, 8), time_modified [8, 16),
 // direct[12] [16, 64), indirect 64, doubly_indirect 68, trebly_indirect 72, file_size 76, type 80.  ppfs_ecc_file is
@@ -97,6 +98,65 @@ PPFS_HD inline uint32_t table_status(uint32_t bitmap_status, uint32_t npieces, P
         corrected |= s == ST_CORRECTED ? 1u : 0u;
     }
     return corrected ? ST_CORRECTED : ST_OK;
+}
+
+// ppfs_ecc_inode_table by value, for host and device
+struct Table {
+    uint32_t table_block, bitmap_block, total_inodes, check_bitmap;
+};
+// What steps 1 and 2 decide for inode `ino` from its bitmap byte and the byte's read status: the verdict, whether the
+// bit was read at all, and the status piece_status slot 0 reports (ST_UNUSED when it was not).  A byte that was not
+// delivered is not looked at.
+struct BitmapStep {
+    uint32_t verdict, bitmap_status;
+    bool bit_read;
+};
+PPFS_HD inline BitmapStep bitmap_step(const Table& t, uint32_t ino, uint32_t byte, uint32_t read_status)
+{
+    const bool bit_read = ino < t.total_inodes && t.check_bitmap;
+    const bool seen = bit_read && (read_status == ST_OK || read_status == ST_CORRECTED);
+    return BitmapStep { bitmap_verdict(ino, t.total_inodes, t.check_bitmap != 0, read_status, seen ? byte : 0u, 0x80u >> (ino % 8u)),
+        bit_read ? read_status : ST_UNUSED, bit_read };
+}
+// The epilogue of one inode: its final status, and into `row` (may be null) its 1 + K bytes of piece_status: the
+// bitmap status, then the statuses of its pieces, ST_UNUSED behind the last one and throughout when the table was
+// not read.  piece_status(k): the status of piece k < pieces(ino, ds).
+template <class PieceStatus>
+PPFS_HD inline uint32_t inode_status(const BitmapStep& b, uint32_t ino, uint64_t ds, uint32_t K, PieceStatus piece_status, uint8_t* row)
+{
+    const uint32_t np = b.verdict == 0u ? pieces(ino, ds) : 0u;
+    const uint32_t st = b.verdict ? b.verdict : table_status(b.bit_read ? b.bitmap_status : 0u, np, piece_status);
+    if (row) {
+        row[0] = (uint8_t)b.bitmap_status;
+        for (uint32_t k = 0; k < K; ++k)
+            row[1u + k] = (uint8_t)(k < np ? piece_status(k) : ST_UNUSED);
+    }
+    return st;
+}
+
+// What slot k < K of an inode does: it TAKES PART when the verdict is 0, k < pieces(ino, ds) and its block is below
+// NO_BLOCK, and then `length` bytes at `offset` of `block` are bytes [pos, pos + length) of the 81
+struct Slot {
+    bool takes_part;
+    uint32_t block, offset, length, pos;
+};
+PPFS_HD inline Slot slot_of(uint32_t table_block, uint32_t ino, uint32_t k, uint32_t verdict, uint64_t ds)
+{
+    Slot s { false, NO_BLOCK, 0, 0, 0 };
+    if (verdict != 0u || k >= pieces(ino, ds))
+        return s;
+    const Piece p = piece(table_block, ino, k, ds);
+    if (p.block >= NO_BLOCK)
+        return s;
+    return Slot { true, (uint32_t)p.block, p.offset, p.length, p.pos };
+}
+// the read's extent of slot s of inode j of a piece (Extent: ppfs_ecc_extent's fields in its order): the slot's bytes
+// land at 81 j + pos of the rows; a slot that does not take part gives the invalid extent
+template <class Extent>
+PPFS_HD inline Extent slot_extent(const Slot& s, uint64_t j)
+{
+    return s.takes_part ? Extent { (uint64_t)INODE_BYTES * j + s.pos, s.block, (uint16_t)s.offset, (uint16_t)s.length }
+                        : Extent { 0, NO_BLOCK, 0, 0 };
 }
 
 // where a status lands in ppfs_ecc_inode_counts taken as eight 64-bit words: ok, corrected, failed, out_of_range,

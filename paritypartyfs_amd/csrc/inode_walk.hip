@@ -4,17 +4,16 @@
 // InodeManager::get (lib/inode_manager/src/inode_manager.cpp:127-138) is one byte of the inode bitmap, then the 81
 // bytes of the packed Inode out of the inode table, cut at block boundaries.  For a piece of a batch of inode
 // numbers that is two extent reads with three small kernels around them, all queued, nothing read back:
-//   inode_bitmap_extents_kernel  the lane's inode number out of the caller's strided source (byte loads when the
-//                                source is not 4-aligned) into the scratch; the extent of its bitmap byte, invalid
-//                                when the number is out of range or the bitmap is not checked
-//   inode_table_extents_kernel   the bit and its read status decide (inode_plan.hpp bitmap_verdict); K extents,
-//                                those of the inode's pieces valid when the table is read, pos = 81 j + the bytes
-//                                before piece k
-//   inode_merge_kernel           the status rule (inode_plan.hpp), the 81-byte row split into the ppfs_ecc_file
-//                                record and the metadata or both zero-filled, status, piece_status, the tally
+//   inode_bitmap_extents_kernel      the lane's inode number out of the caller's strided source (byte loads when the
+//                                    source is not 4-aligned) into the scratch; the extent of its bitmap byte, invalid
+//                                    when the number is out of range or the bitmap is not checked
+//   inode_table_extents_kernel       the bit and its read status decide (inode_plan.hpp bitmap_step); K extents, those
+//                                    of the slots that take part valid (slot_of, slot_extent)
+//   inode_status_kernel<ReadPieces>  the epilogue (inode_plan.hpp inode_status): status, piece_status, the tally; the
+//                                    81-byte row split into the ppfs_ecc_file record and the metadata or both zero-filled
 // One lane per inode, 256 lanes a workgroup, a grid-stride loop; consecutive lanes store consecutive elements.
 // The kernels are latency-bound and small: the codec work is in the extent calls between them.  Every index is
-// checked against its array's extent before use; all arithmetic is inode_plan.hpp's.
+// checked against its array's extent before use; all arithmetic and the whole per-inode rule are inode_plan.hpp's.
 #include <hip/hip_runtime.h>
 
 #include "dbg.hpp"
@@ -28,10 +27,6 @@ namespace ppfs {
 
 using namespace inodeplan;
 
-struct InodeTable {
-    uint32_t table_block, bitmap_block, total_inodes, check_bitmap;
-};
-
 __device__ inline void invalid_extent(ppfs_ecc_extent& e)
 {
     e.pos = 0;
@@ -41,7 +36,7 @@ __device__ inline void invalid_extent(ppfs_ecc_extent& e)
 
 // src: n numbers `stride` bytes apart, src_bytes = (n - 1) * stride + 4 in all; ino_out[j] and ext[j] for j < n
 __global__ __launch_bounds__(256) void inode_bitmap_extents_kernel(const uint8_t* __restrict__ src, uint64_t stride,
-    uint64_t src_bytes, uint64_t n, InodeTable t, uint64_t ds, uint32_t* __restrict__ ino_out, ppfs_ecc_extent* __restrict__ ext)
+    uint64_t src_bytes, uint64_t n, Table t, uint64_t ds, uint32_t* __restrict__ ino_out, ppfs_ecc_extent* __restrict__ ext)
 {
     const bool aligned = ((((uintptr_t)src) | stride) & 3u) == 0;
     for (uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x; j < n; j += (uint64_t)gridDim.x * 256u) {
@@ -71,97 +66,101 @@ __global__ __launch_bounds__(256) void inode_bitmap_extents_kernel(const uint8_t
     }
 }
 
-// what steps 1 and 2 decide for inode j of the piece, from the scratch
-__device__ inline uint32_t verdict_of(const InodeTable& t, uint32_t ino, const uint8_t* __restrict__ bm, const uint8_t* __restrict__ bst,
-    uint64_t j, uint64_t n, uint32_t mask, uint32_t* read_status)
+// A piece of a batch as the bitmap steps left it in the scratch: ino[j], bm[j], bst[j] for j < n; K = max_pieces(ds).
+// What every kernel below starts from.
+struct PieceIn {
+    const uint32_t* ino;
+    const uint8_t *bm, *bst;
+    uint64_t n;
+    Table t;
+    uint64_t ds;
+    uint32_t K;
+};
+
+// the number of inode j and what steps 1 and 2 decided for it; false when there is no such inode
+__device__ inline bool inode_at(const PieceIn& p, uint64_t j, uint32_t* ino, BitmapStep* b)
 {
+    if (j >= p.n || !PPFS_DBG_OK(p.ino + j, 4, p.ino, p.n * 4))
+        return false;
+    *ino = p.ino[j];
     uint32_t st = ST_OUT, byte = 0;
-    if (ino < t.total_inodes && t.check_bitmap && PPFS_DBG_OK(bst + j, 1, bst, n) && PPFS_DBG_OK(bm + j, 1, bm, n)) {
-        st = bst[j];
-        if (st == ST_OK || st == ST_CORRECTED) // a byte that was not delivered is not looked at
-            byte = bm[j];
+    if (PPFS_DBG_OK(p.bst + j, 1, p.bst, p.n) && PPFS_DBG_OK(p.bm + j, 1, p.bm, p.n)) {
+        st = p.bst[j];
+        byte = p.bm[j];
     }
-    *read_status = st;
-    return bitmap_verdict(ino, t.total_inodes, t.check_bitmap != 0, st, byte, mask);
+    *b = bitmap_step(p.t, *ino, byte, st);
+    return true;
 }
 
 // ext[j * K + k], k < K, for j < n
-__global__ __launch_bounds__(256) void inode_table_extents_kernel(const uint32_t* __restrict__ ino_in, const uint8_t* __restrict__ bm,
-    const uint8_t* __restrict__ bst, uint64_t n, InodeTable t, uint64_t ds, uint32_t K, ppfs_ecc_extent* __restrict__ ext)
+__global__ __launch_bounds__(256) void inode_table_extents_kernel(PieceIn p, ppfs_ecc_extent* __restrict__ ext)
 {
-    for (uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x; j < n; j += (uint64_t)gridDim.x * 256u) {
-        if (!PPFS_DBG_OK(ino_in + j, 4, ino_in, n * 4))
+    for (uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x; j < p.n; j += (uint64_t)gridDim.x * 256u) {
+        uint32_t ino = 0;
+        BitmapStep b {};
+        if (!inode_at(p, j, &ino, &b))
             continue;
-        const uint32_t ino = ino_in[j];
-        uint32_t bitmap_status;
-        const uint32_t verdict = verdict_of(t, ino, bm, bst, j, n, 0x80u >> (ino % 8u), &bitmap_status);
-        const uint32_t np = verdict == 0u ? pieces(ino, ds) : 0u;
-        for (uint32_t k = 0; k < K; ++k) {
-            ppfs_ecc_extent e;
-            invalid_extent(e);
-            if (k < np) {
-                const Piece p = piece(t.table_block, ino, k, ds);
-                if (p.block < NO_BLOCK) {
-                    e.pos = (uint64_t)INODE_BYTES * j + p.pos;
-                    e.block = (uint32_t)p.block;
-                    e.offset = (uint16_t)p.offset;
-                    e.length = (uint16_t)p.length;
-                }
-            }
-            if (PPFS_DBG_OK(ext + j * K + k, 16, ext, n * K * 16))
-                ext[j * K + k] = e;
-        }
+        for (uint32_t k = 0; k < p.K; ++k)
+            if (PPFS_DBG_OK(ext + j * p.K + k, 16, ext, p.n * p.K * 16))
+                ext[j * p.K + k] = slot_extent<ppfs_ecc_extent>(slot_of(p.t.table_block, ino, k, b.verdict, p.ds), j);
     }
 }
 
-// rows: 81 n bytes, row j at 81 j (any alignment); pst[j * K + k]: the read status of piece k of inode j.
-// files (4-byte aligned), meta (8-byte aligned), status, piece_status (n * (1 + K) bytes), counts: each may be null
-__global__ __launch_bounds__(256) void inode_merge_kernel(const uint32_t* __restrict__ ino_in, const uint8_t* __restrict__ bm,
-    const uint8_t* __restrict__ bst, const uint8_t* __restrict__ rows, const uint8_t* __restrict__ pst, uint64_t n, InodeTable t,
-    uint64_t ds, uint32_t K, uint32_t* __restrict__ files, unsigned long long* __restrict__ meta, uint8_t* __restrict__ status,
+// Where the read's piece statuses come from: pst[j * K + k], the read status of piece k of inode j.  Its inodes have
+// a row to split: rows, 81 n bytes, row j at 81 j (any alignment), into files (4-byte aligned) and meta (8-byte
+// aligned), each may be null
+struct ReadPieces {
+    const uint8_t *rows, *pst;
+    uint32_t* files;
+    unsigned long long* meta;
+
+    __device__ uint32_t status(const PieceIn& p, uint64_t j, uint32_t, uint32_t, uint32_t k) const
+    {
+        const uint8_t* my = pst + j * p.K + k;
+        return k < p.K && PPFS_DBG_OK(my, 1, pst, p.n * p.K) ? *my : (uint32_t)ST_OUT;
+    }
+    __device__ void finish(const PieceIn& p, uint64_t j, uint32_t st) const
+    {
+        const bool good = st == ST_OK || st == ST_CORRECTED;
+        const uint8_t* row = rows + (uint64_t)INODE_BYTES * j;
+        auto at = [&](uint32_t i) -> uint32_t {
+            return good && i < INODE_BYTES && PPFS_DBG_OK(row + i, 1, rows, (uint64_t)INODE_BYTES * p.n) ? row[i] : 0u;
+        };
+        if (files && PPFS_DBG_OK(files + j * 16u, 64, files, p.n * 64)) {
+            for (uint32_t w = 0; w < FILE_BYTES / 4u; ++w)
+                files[j * 16u + w] = le32(at, FILE_OFF + 4u * w);
+        }
+        if (meta && PPFS_DBG_OK(meta + j * 3u, 24, meta, p.n * 24)) {
+            meta[j * 3u] = le64(at, 0);
+            meta[j * 3u + 1u] = le64(at, 8);
+            meta[j * 3u + 2u] = at(TYPE_OFF);
+        }
+    }
+};
+
+// The epilogue of a piece, for the reads and the writes: Pieces::status(p, j, ino, verdict, k) is the status of piece
+// k of inode j, Pieces::finish(p, j, st) what else the call stores for an inode of final status st.
+// status, piece_status (n * (1 + K) bytes), counts: each may be null
+template <class Pieces>
+__global__ __launch_bounds__(256) void inode_status_kernel(PieceIn p, Pieces src, uint8_t* __restrict__ status,
     uint8_t* __restrict__ piece_status, unsigned long long* __restrict__ counts)
 {
     uint32_t c[4] = { 0, 0, 0, 0 }, free_c[4] = { 0, 0, 0, 0 };
-    const uint64_t W = 1u + K;
-    for (uint64_t w0 = (uint64_t)blockIdx.x * 256u; w0 < n; w0 += (uint64_t)gridDim.x * 256u) {
+    const uint64_t W = 1u + p.K;
+    for (uint64_t w0 = (uint64_t)blockIdx.x * 256u; w0 < p.n; w0 += (uint64_t)gridDim.x * 256u) {
         const uint64_t j = w0 + threadIdx.x;
         int slot = -1;
-        if (j < n && PPFS_DBG_OK(ino_in + j, 4, ino_in, n * 4)) {
-            const uint32_t ino = ino_in[j];
-            uint32_t bitmap_status;
-            const uint32_t verdict = verdict_of(t, ino, bm, bst, j, n, 0x80u >> (ino % 8u), &bitmap_status);
-            const bool bit_read = ino < t.total_inodes && t.check_bitmap;
-            const uint32_t np = verdict == 0u ? pieces(ino, ds) : 0u;
-            const uint8_t* my = pst + j * K;
-            auto piece_st = [&](uint32_t k) -> uint32_t {
-                return k < K && PPFS_DBG_OK(my + k, 1, pst, n * K) ? my[k] : (uint32_t)ST_OUT;
-            };
-            const uint32_t st = verdict ? verdict : table_status(bit_read ? bitmap_status : 0u, np, piece_st);
+        uint32_t ino = 0;
+        BitmapStep b {};
+        if (inode_at(p, j, &ino, &b)) {
+            uint8_t* ps = piece_status ? piece_status + j * W : nullptr;
+            if (ps && !PPFS_DBG_OK(ps, W, piece_status, p.n * W))
+                ps = nullptr;
+            const uint32_t st = inode_status(b, ino, p.ds, p.K, [&](uint32_t k) { return src.status(p, j, ino, b.verdict, k); }, ps);
             slot = count_slot(st);
-            if (status && PPFS_DBG_OK(status + j, 1, status, n))
+            if (status && PPFS_DBG_OK(status + j, 1, status, p.n))
                 status[j] = (uint8_t)st;
-            if (piece_status) {
-                uint8_t* ps = piece_status + j * W;
-                if (PPFS_DBG_OK(ps, W, piece_status, n * W)) {
-                    ps[0] = (uint8_t)(bit_read ? bitmap_status : ST_UNUSED);
-                    for (uint32_t k = 0; k < K; ++k)
-                        ps[1u + k] = (uint8_t)(k < np ? piece_st(k) : ST_UNUSED);
-                }
-            }
-            const bool good = st == ST_OK || st == ST_CORRECTED;
-            const uint8_t* row = rows + (uint64_t)INODE_BYTES * j;
-            auto at = [&](uint32_t i) -> uint32_t {
-                return good && i < INODE_BYTES && PPFS_DBG_OK(row + i, 1, rows, (uint64_t)INODE_BYTES * n) ? row[i] : 0u;
-            };
-            if (files && PPFS_DBG_OK(files + j * 16u, 64, files, n * 64)) {
-                for (uint32_t w = 0; w < FILE_BYTES / 4u; ++w)
-                    files[j * 16u + w] = le32(at, FILE_OFF + 4u * w);
-            }
-            if (meta && PPFS_DBG_OK(meta + j * 3u, 24, meta, n * 24)) {
-                meta[j * 3u] = le64(at, 0);
-                meta[j * 3u + 1u] = le64(at, 8);
-                meta[j * 3u + 2u] = at(TYPE_OFF);
-            }
+            src.finish(p, j, st);
         }
         tally_add(c, slot);
         tally_add(free_c, slot == SLOT_NOT_ALLOCATED ? 0 : -1);
@@ -172,15 +171,15 @@ __global__ __launch_bounds__(256) void inode_merge_kernel(const uint32_t* __rest
 }
 
 // ---- the inode writes (inode_path.cpp ppfs_ecc_write_inodes_device; the grouping step of inode_wplan.hpp) ----
-//   inode_elect_kernel          one lane per slot (entry j, piece k): a slot that takes part claims its block's key and
-//                               lowers the block's owner to its slot index; piece 0 claims the inode number's key and
-//                               raises its winner to j
-//   inode_owner_extents_kernel  the owner slot of each block emits {pos 0, block, 0, 0}, every other slot the invalid
-//                               extent
-//   inode_overlay_kernel        inside the extent write, after the old payloads: the slots of winning entries store
-//                               their bytes of the composed row into their block's owner row of P
-//   inode_write_status_kernel   one lane per inode: the pieces' write statuses under the first toucher rule, the status
-//                               rule, status, piece_status, the tally
+//   inode_elect_kernel                one lane per slot (entry j, piece k): a slot that takes part claims its block's
+//                                     key and lowers the block's owner to its slot index; piece 0 claims the inode
+//                                     number's key and raises its winner to j
+//   inode_owner_extents_kernel        the owner slot of each block emits {pos 0, block, 0, 0}, every other slot the
+//                                     invalid extent
+//   inode_overlay_kernel              inside the extent write, after the old payloads: the slots of winning entries
+//                                     store their bytes of the composed row into their block's owner row of P
+//   inode_status_kernel<WritePieces>  one lane per inode: the pieces' write statuses under the first toucher rule, then
+//                                     the reads' epilogue
 // The tables were cleared to 0xFF on the stream before the elect kernel.  No lane waits for another: claim() and
 // find() end after at most cap probes.
 using namespace inodewplan;
@@ -207,68 +206,56 @@ struct DeviceOps {
     }
 };
 
-// what slot `slot` < n * K of the piece does, from the scratch; *ino_out and *entry: its inode number and entry
-__device__ inline Slot slot_from_scratch(const uint32_t* __restrict__ ino_in, const uint8_t* __restrict__ bm,
-    const uint8_t* __restrict__ bst, uint64_t n, const InodeTable& t, uint64_t ds, uint32_t K, uint64_t slot, uint32_t* ino_out,
-    uint32_t* entry)
+// what slot `slot` < n * K of the piece does; *ino and *entry: its inode number and entry
+__device__ inline Slot slot_from_scratch(const PieceIn& p, uint64_t slot, uint32_t* ino, uint32_t* entry)
 {
-    const uint64_t j = slot / K;
+    const uint64_t j = slot / p.K;
     *entry = (uint32_t)j;
-    *ino_out = 0;
-    if (j >= n || !PPFS_DBG_OK(ino_in + j, 4, ino_in, n * 4))
+    *ino = 0;
+    BitmapStep b {};
+    if (!inode_at(p, j, ino, &b))
         return Slot { false, NO_BLOCK, 0, 0, 0 };
-    const uint32_t ino = ino_in[j];
-    *ino_out = ino;
-    uint32_t bitmap_status;
-    const uint32_t verdict = verdict_of(t, ino, bm, bst, j, n, 0x80u >> (ino % 8u), &bitmap_status);
-    return slot_of(t.table_block, ino, (uint32_t)(slot - j * K), verdict, ds);
+    return slot_of(p.t.table_block, *ino, (uint32_t)(slot - j * p.K), b.verdict, p.ds);
 }
 
-// tab: the two tables, table_bytes(cap) bytes, cleared
-__global__ __launch_bounds__(256) void inode_elect_kernel(const uint32_t* __restrict__ ino_in, const uint8_t* __restrict__ bm,
-    const uint8_t* __restrict__ bst, uint64_t n, InodeTable t, uint64_t ds, uint32_t K, uint32_t* tab, uint32_t cap)
+// T: the two tables, cleared
+__global__ __launch_bounds__(256) void inode_elect_kernel(PieceIn p, Tables T)
 {
-    const Tables T = tables_at(tab, cap);
-    for (uint64_t s = (uint64_t)blockIdx.x * 256u + threadIdx.x; s < n * K; s += (uint64_t)gridDim.x * 256u) {
+    for (uint64_t s = (uint64_t)blockIdx.x * 256u + threadIdx.x; s < p.n * p.K; s += (uint64_t)gridDim.x * 256u) {
         uint32_t ino, j;
-        const Slot sl = slot_from_scratch(ino_in, bm, bst, n, t, ds, K, s, &ino, &j);
-        elect<DeviceOps>(T, sl, ino, j, (uint32_t)(s - (uint64_t)j * K), (uint32_t)s);
+        const Slot sl = slot_from_scratch(p, s, &ino, &j);
+        elect<DeviceOps>(T, sl, ino, j, (uint32_t)(s - (uint64_t)j * p.K), (uint32_t)s);
     }
 }
 
 // ext[s] for s < n * K
-__global__ __launch_bounds__(256) void inode_owner_extents_kernel(const uint32_t* __restrict__ ino_in, const uint8_t* __restrict__ bm,
-    const uint8_t* __restrict__ bst, uint64_t n, InodeTable t, uint64_t ds, uint32_t K, uint32_t* tab, uint32_t cap,
-    ppfs_ecc_extent* __restrict__ ext)
+__global__ __launch_bounds__(256) void inode_owner_extents_kernel(PieceIn p, Tables T, ppfs_ecc_extent* __restrict__ ext)
 {
-    const Tables T = tables_at(tab, cap);
-    for (uint64_t s = (uint64_t)blockIdx.x * 256u + threadIdx.x; s < n * K; s += (uint64_t)gridDim.x * 256u) {
+    for (uint64_t s = (uint64_t)blockIdx.x * 256u + threadIdx.x; s < p.n * p.K; s += (uint64_t)gridDim.x * 256u) {
         uint32_t ino, j;
-        const Slot sl = slot_from_scratch(ino_in, bm, bst, n, t, ds, K, s, &ino, &j);
+        const Slot sl = slot_from_scratch(p, s, &ino, &j);
         ppfs_ecc_extent e;
         invalid_extent(e);
         if (sl.takes_part && owner_of<DeviceOps>(T, sl.block) == (uint32_t)s)
             e.block = sl.block; // pos, offset and length 0: the block is checked and encoded again
-        if (PPFS_DBG_OK(ext + s, 16, ext, n * K * 16))
+        if (PPFS_DBG_OK(ext + s, 16, ext, p.n * p.K * 16))
             ext[s] = e;
     }
 }
 
 // files: 64 n bytes, meta: 3 n 64-bit words; idx[r], r < n * K: the staged index of extent r, whose payload is row r
 // of P (stride ds, P_cap bytes)
-__global__ __launch_bounds__(256) void inode_overlay_kernel(const uint32_t* __restrict__ ino_in, const uint8_t* __restrict__ bm,
-    const uint8_t* __restrict__ bst, uint64_t n, InodeTable t, uint64_t ds, uint32_t K, uint32_t* tab, uint32_t cap,
-    const uint8_t* __restrict__ files, const unsigned long long* __restrict__ meta, const uint32_t* __restrict__ idx, uint8_t* P,
-    uint64_t P_cap)
+__global__ __launch_bounds__(256) void inode_overlay_kernel(PieceIn p, Tables T, const uint8_t* __restrict__ files,
+    const unsigned long long* __restrict__ meta, const uint32_t* __restrict__ idx, uint8_t* P, uint64_t P_cap)
 {
-    const Tables T = tables_at(tab, cap);
-    for (uint64_t s = (uint64_t)blockIdx.x * 256u + threadIdx.x; s < n * K; s += (uint64_t)gridDim.x * 256u) {
+    const uint64_t n = p.n, ds = p.ds;
+    for (uint64_t s = (uint64_t)blockIdx.x * 256u + threadIdx.x; s < n * p.K; s += (uint64_t)gridDim.x * 256u) {
         uint32_t ino, j;
-        const Slot sl = slot_from_scratch(ino_in, bm, bst, n, t, ds, K, s, &ino, &j);
+        const Slot sl = slot_from_scratch(p, s, &ino, &j);
         if (!sl.takes_part || winner_of<DeviceOps>(T, ino) != j)
             continue;
         const uint32_t row = owner_of<DeviceOps>(T, sl.block);
-        if (row >= n * K || !PPFS_DBG_OK(idx + row, 4, idx, n * K * 4) || idx[row] != sl.block)
+        if (row >= n * p.K || !PPFS_DBG_OK(idx + row, 4, idx, n * p.K * 4) || idx[row] != sl.block)
             continue; // the block is not in the image: nothing is written
         const uint64_t at = (uint64_t)row * ds + sl.offset;
         if (sl.offset + (uint64_t)sl.length > ds || at + sl.length > P_cap || sl.pos + sl.length > INODE_BYTES
@@ -283,52 +270,24 @@ __global__ __launch_bounds__(256) void inode_overlay_kernel(const uint32_t* __re
     }
 }
 
-// wst[r], r < n * K: the write status of extent r.  status, piece_status (n * (1 + K) bytes), counts: each may be null
-__global__ __launch_bounds__(256) void inode_write_status_kernel(const uint32_t* __restrict__ ino_in, const uint8_t* __restrict__ bm,
-    const uint8_t* __restrict__ bst, const uint8_t* __restrict__ wst, uint64_t n, InodeTable t, uint64_t ds, uint32_t K, uint32_t* tab,
-    uint32_t cap, uint8_t* __restrict__ status, uint8_t* __restrict__ piece_status, unsigned long long* __restrict__ counts)
-{
-    const Tables T = tables_at(tab, cap);
-    uint32_t c[4] = { 0, 0, 0, 0 }, free_c[4] = { 0, 0, 0, 0 };
-    const uint64_t W = 1u + K;
-    for (uint64_t w0 = (uint64_t)blockIdx.x * 256u; w0 < n; w0 += (uint64_t)gridDim.x * 256u) {
-        const uint64_t j = w0 + threadIdx.x;
-        int slot = -1;
-        if (j < n && PPFS_DBG_OK(ino_in + j, 4, ino_in, n * 4)) {
-            const uint32_t ino = ino_in[j];
-            uint32_t bitmap_status;
-            const uint32_t verdict = verdict_of(t, ino, bm, bst, j, n, 0x80u >> (ino % 8u), &bitmap_status);
-            const bool bit_read = ino < t.total_inodes && t.check_bitmap;
-            const uint32_t np = verdict == 0u ? pieces(ino, ds) : 0u;
-            auto piece_st = [&](uint32_t k) -> uint32_t {
-                const Slot sl = slot_of(t.table_block, ino, k, verdict, ds);
-                if (!sl.takes_part)
-                    return ST_OUT;
-                const uint32_t row = owner_of<DeviceOps>(T, sl.block);
-                if (row >= n * K || !PPFS_DBG_OK(wst + row, 1, wst, n * K))
-                    return ST_OUT;
-                return seen_status(wst[row], (uint32_t)(j * K + k), row);
-            };
-            const uint32_t st = verdict ? verdict : table_status(bit_read ? bitmap_status : 0u, np, piece_st);
-            slot = count_slot(st);
-            if (status && PPFS_DBG_OK(status + j, 1, status, n))
-                status[j] = (uint8_t)st;
-            if (piece_status) {
-                uint8_t* ps = piece_status + j * W;
-                if (PPFS_DBG_OK(ps, W, piece_status, n * W)) {
-                    ps[0] = (uint8_t)(bit_read ? bitmap_status : ST_UNUSED);
-                    for (uint32_t k = 0; k < K; ++k)
-                        ps[1u + k] = (uint8_t)(k < np ? piece_st(k) : ST_UNUSED);
-                }
-            }
-        }
-        tally_add(c, slot);
-        tally_add(free_c, slot == SLOT_NOT_ALLOCATED ? 0 : -1);
+// Where the write's piece statuses come from: wst[r], r < n * K, the write status of extent r; a piece's is that of
+// its block's owner row, found through the tables, under the first toucher rule.  Nothing else to store
+struct WritePieces {
+    const uint8_t* wst;
+    Tables T;
+
+    __device__ uint32_t status(const PieceIn& p, uint64_t j, uint32_t ino, uint32_t verdict, uint32_t k) const
+    {
+        const Slot sl = slot_of(p.t.table_block, ino, k, verdict, p.ds);
+        if (!sl.takes_part)
+            return ST_OUT;
+        const uint32_t row = owner_of<DeviceOps>(T, sl.block);
+        if (row >= p.n * p.K || !PPFS_DBG_OK(wst + row, 1, wst, p.n * p.K))
+            return ST_OUT;
+        return seen_status(wst[row], (uint32_t)(j * p.K + k), row);
     }
-    tally_flush(c, counts, 0, 4);
-    __syncthreads(); // the two flushes share their LDS words
-    tally_flush(free_c, counts, SLOT_NOT_ALLOCATED, 1);
-}
+    __device__ void finish(const PieceIn&, uint64_t, uint32_t) const { }
+};
 
 // grid-stride, at most 2,048 workgroups
 static uint32_t grid_of(uint64_t n)
@@ -337,6 +296,23 @@ static uint32_t grid_of(uint64_t n)
     return (uint32_t)(want < 2048u ? want : 2048u);
 }
 static bool shape_ok(uint64_t n, uint64_t ds) { return ds > 0 && ds <= 0xFFFFu && n <= 2u * PIECE_INODES; }
+static Table table_of(const ppfs_ecc_inode_table& t) { return Table { t.table_block, t.bitmap_block, t.total_inodes, t.check_bitmap }; }
+
+// what every launcher behind the bitmap step checks of the scratch and the table, and the piece the kernels take
+static bool piece_in(const uint32_t* ino, const uint8_t* bm, const uint8_t* bst, uint64_t n, const ppfs_ecc_inode_table* table,
+    uint64_t ds, PieceIn* p)
+{
+    if (!ino || !bm || !bst || !table || ((uintptr_t)ino & 3u) || !shape_ok(n, ds))
+        return false;
+    *p = PieceIn { ino, bm, bst, n, table_of(*table), ds, max_pieces(ds) };
+    return true;
+}
+// the inode writes: n inodes of K slots each, n * K <= 2 * PIECE_INODES; tab: 4-byte aligned, table_bytes(cap) bytes
+static bool wshape_ok(uint64_t n, uint64_t ds, const void* tab, uint32_t cap)
+{
+    return n * max_pieces(ds) <= 2u * PIECE_INODES && tab && !((uintptr_t)tab & 3u) && cap >= 2u && (cap & (cap - 1u)) == 0u
+        && (uint64_t)cap >= 2u * n * max_pieces(ds);
+}
 
 } // namespace ppfs
 
@@ -349,21 +325,20 @@ extern "C" hipError_t ppfs_inode_bitmap_extents_launch(const void* src, uint64_t
         return hipSuccess;
     if (!src || stride < 4 || !table || !ino_out || !ext || ((uintptr_t)ino_out & 3u) || ((uintptr_t)ext & 7u) || !shape_ok(n, ds))
         return hipErrorInvalidValue;
-    const InodeTable t { table->table_block, table->bitmap_block, table->total_inodes, table->check_bitmap };
     hipLaunchKernelGGL(inode_bitmap_extents_kernel, dim3(grid_of(n)), dim3(256), 0, s, (const uint8_t*)src, stride, (n - 1) * stride + 4u,
-        n, t, ds, ino_out, ext);
+        n, table_of(*table), ds, ino_out, ext);
     return hipGetLastError();
 }
 
 extern "C" hipError_t ppfs_inode_table_extents_launch(const uint32_t* ino, const uint8_t* bm, const uint8_t* bst, uint64_t n,
     const ppfs_ecc_inode_table* table, uint64_t ds, ppfs_ecc_extent* ext, hipStream_t s)
 {
+    PieceIn p;
     if (n == 0)
         return hipSuccess;
-    if (!ino || !bm || !bst || !table || !ext || ((uintptr_t)ino & 3u) || ((uintptr_t)ext & 7u) || !shape_ok(n, ds))
+    if (!piece_in(ino, bm, bst, n, table, ds, &p) || !ext || ((uintptr_t)ext & 7u))
         return hipErrorInvalidValue;
-    const InodeTable t { table->table_block, table->bitmap_block, table->total_inodes, table->check_bitmap };
-    hipLaunchKernelGGL(inode_table_extents_kernel, dim3(grid_of(n)), dim3(256), 0, s, ino, bm, bst, n, t, ds, max_pieces(ds), ext);
+    hipLaunchKernelGGL(inode_table_extents_kernel, dim3(grid_of(n)), dim3(256), 0, s, p, ext);
     return hipGetLastError();
 }
 
@@ -371,38 +346,30 @@ extern "C" hipError_t ppfs_inode_merge_launch(const uint32_t* ino, const uint8_t
     const uint8_t* pst, uint64_t n, const ppfs_ecc_inode_table* table, uint64_t ds, ppfs_ecc_file* files, ppfs_ecc_inode_meta* meta,
     uint8_t* status, uint8_t* piece_status, unsigned long long* counts, hipStream_t s)
 {
+    PieceIn p;
     if (n == 0 || (!files && !meta && !status && !piece_status && !counts))
         return hipSuccess;
-    if (!ino || !bm || !bst || !rows || !pst || !table || ((uintptr_t)ino & 3u) || ((uintptr_t)files & 3u)
-        || (((uintptr_t)meta | (uintptr_t)counts) & 7u) || !shape_ok(n, ds))
+    if (!piece_in(ino, bm, bst, n, table, ds, &p) || !rows || !pst || ((uintptr_t)files & 3u)
+        || (((uintptr_t)meta | (uintptr_t)counts) & 7u))
         return hipErrorInvalidValue;
-    const InodeTable t { table->table_block, table->bitmap_block, table->total_inodes, table->check_bitmap };
-    hipLaunchKernelGGL(inode_merge_kernel, dim3(grid_of(n)), dim3(256), 0, s, ino, bm, bst, rows, pst, n, t, ds, max_pieces(ds),
-        (uint32_t*)files, (unsigned long long*)meta, status, piece_status, counts);
+    hipLaunchKernelGGL(inode_status_kernel<ReadPieces>, dim3(grid_of(n)), dim3(256), 0, s, p,
+        ReadPieces { rows, pst, (uint32_t*)files, (unsigned long long*)meta }, status, piece_status, counts);
     return hipGetLastError();
-}
-
-// the inode writes: n inodes of K slots each, n * K <= 2 * PIECE_INODES; tab: 4-byte aligned, table_bytes(cap) bytes
-static bool wshape_ok(uint64_t n, uint64_t ds, const void* tab, uint32_t cap)
-{
-    return shape_ok(n, ds) && n * max_pieces(ds) <= 2u * PIECE_INODES && tab && !((uintptr_t)tab & 3u) && cap >= 2u
-        && (cap & (cap - 1u)) == 0u && (uint64_t)cap >= 2u * n * max_pieces(ds);
 }
 
 extern "C" hipError_t ppfs_inode_elect_launch(const uint32_t* ino, const uint8_t* bm, const uint8_t* bst, uint64_t n,
     const ppfs_ecc_inode_table* table, uint64_t ds, uint32_t* tab, uint32_t cap, ppfs_ecc_extent* ext, hipStream_t s)
 {
+    PieceIn p;
     if (n == 0)
         return hipSuccess;
-    if (!ino || !bm || !bst || !table || !ext || ((uintptr_t)ino & 3u) || ((uintptr_t)ext & 7u) || !wshape_ok(n, ds, tab, cap))
+    if (!piece_in(ino, bm, bst, n, table, ds, &p) || !ext || ((uintptr_t)ext & 7u) || !wshape_ok(n, ds, tab, cap))
         return hipErrorInvalidValue;
-    const InodeTable t { table->table_block, table->bitmap_block, table->total_inodes, table->check_bitmap };
-    const uint32_t K = max_pieces(ds);
-    hipLaunchKernelGGL(inode_elect_kernel, dim3(grid_of(n * K)), dim3(256), 0, s, ino, bm, bst, n, t, ds, K, tab, cap);
+    hipLaunchKernelGGL(inode_elect_kernel, dim3(grid_of(n * p.K)), dim3(256), 0, s, p, tables_at(tab, cap));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         return e;
-    hipLaunchKernelGGL(inode_owner_extents_kernel, dim3(grid_of(n * K)), dim3(256), 0, s, ino, bm, bst, n, t, ds, K, tab, cap, ext);
+    hipLaunchKernelGGL(inode_owner_extents_kernel, dim3(grid_of(n * p.K)), dim3(256), 0, s, p, tables_at(tab, cap), ext);
     return hipGetLastError();
 }
 
@@ -410,15 +377,14 @@ extern "C" hipError_t ppfs_inode_overlay_launch(const uint32_t* ino, const uint8
     const ppfs_ecc_inode_table* table, uint64_t ds, uint32_t* tab, uint32_t cap, const ppfs_ecc_file* files,
     const ppfs_ecc_inode_meta* meta, const uint32_t* idx, uint8_t* P, uint64_t P_cap, hipStream_t s)
 {
+    PieceIn p;
     if (n == 0)
         return hipSuccess;
-    if (!ino || !bm || !bst || !table || !files || !meta || !idx || !P || ((uintptr_t)ino & 3u) || ((uintptr_t)idx & 3u)
-        || ((uintptr_t)meta & 7u) || !wshape_ok(n, ds, tab, cap))
+    if (!piece_in(ino, bm, bst, n, table, ds, &p) || !files || !meta || !idx || !P || ((uintptr_t)idx & 3u) || ((uintptr_t)meta & 7u)
+        || !wshape_ok(n, ds, tab, cap))
         return hipErrorInvalidValue;
-    const InodeTable t { table->table_block, table->bitmap_block, table->total_inodes, table->check_bitmap };
-    const uint32_t K = max_pieces(ds);
-    hipLaunchKernelGGL(inode_overlay_kernel, dim3(grid_of(n * K)), dim3(256), 0, s, ino, bm, bst, n, t, ds, K, tab, cap,
-        (const uint8_t*)files, (const unsigned long long*)meta, idx, P, P_cap);
+    hipLaunchKernelGGL(inode_overlay_kernel, dim3(grid_of(n * p.K)), dim3(256), 0, s, p, tables_at(tab, cap), (const uint8_t*)files,
+        (const unsigned long long*)meta, idx, P, P_cap);
     return hipGetLastError();
 }
 
@@ -426,13 +392,13 @@ extern "C" hipError_t ppfs_inode_write_status_launch(const uint32_t* ino, const 
     uint64_t n, const ppfs_ecc_inode_table* table, uint64_t ds, uint32_t* tab, uint32_t cap, uint8_t* status, uint8_t* piece_status,
     unsigned long long* counts, hipStream_t s)
 {
+    PieceIn p;
     if (n == 0 || (!status && !piece_status && !counts))
         return hipSuccess;
-    if (!ino || !bm || !bst || !wst || !table || ((uintptr_t)ino & 3u) || ((uintptr_t)counts & 7u) || !wshape_ok(n, ds, tab, cap))
+    if (!piece_in(ino, bm, bst, n, table, ds, &p) || !wst || ((uintptr_t)counts & 7u) || !wshape_ok(n, ds, tab, cap))
         return hipErrorInvalidValue;
-    const InodeTable t { table->table_block, table->bitmap_block, table->total_inodes, table->check_bitmap };
-    hipLaunchKernelGGL(inode_write_status_kernel, dim3(grid_of(n)), dim3(256), 0, s, ino, bm, bst, wst, n, t, ds, max_pieces(ds), tab,
-        cap, status, piece_status, counts);
+    hipLaunchKernelGGL(inode_status_kernel<WritePieces>, dim3(grid_of(n)), dim3(256), 0, s, p, WritePieces { wst, tables_at(tab, cap) },
+        status, piece_status, counts);
     return hipGetLastError();
 }
 

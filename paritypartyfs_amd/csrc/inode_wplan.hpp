@@ -6,8 +6,8 @@
 //
 // InodeManager::update (lib/inode_manager/src/inode_manager.cpp:142-159) is Bitmap::getBit and _writeInode (:20-54),
 // one writeBlock per piece of the 81 bytes (inode_plan.hpp piece()).  A piece of a batch is m inodes of K = K(ds)
-// slots each, slot = j * K + k for piece k of entry j; a slot TAKES PART when its inode's verdict (inode_plan.hpp
-// bitmap_verdict) is 0, k < pieces(ino) and its block is below NO_BLOCK.
+// slots each, slot = j * K + k for piece k of entry j; a slot TAKES PART as inode_plan.hpp slot_of says, which the
+// reads' table extents use too.  This file is the election only.
 //   elect    two open-addressing tables of `cap` = capacity(m * K) entries, keys and values 32-bit, all 0xFF when
 //            cleared.  blocks: key = block number, value = the LOWEST slot that touches it (unsigned minimum): the
 //            block's owner, whose slot index is the block's row in the extent staging.  inodes: key = inode number,
@@ -117,23 +117,7 @@ struct Tables {
 };
 PPFS_HD inline Tables tables_at(uint32_t* base, uint32_t cap) { return Tables { base, base + cap, base + 2ull * cap, base + 3ull * cap, cap }; }
 
-// What slot k of an entry does: takes part (see above), and then where its bytes go
-struct Slot {
-    bool takes_part;
-    uint32_t block, offset, length, pos;
-};
-PPFS_HD inline Slot slot_of(uint32_t table_block, uint32_t ino, uint32_t k, uint32_t verdict, uint64_t ds)
-{
-    Slot s { false, NO_BLOCK, 0, 0, 0 };
-    if (verdict != 0u || k >= pieces(ino, ds))
-        return s;
-    const Piece p = piece(table_block, ino, k, ds);
-    if (p.block >= NO_BLOCK)
-        return s;
-    return Slot { true, (uint32_t)p.block, p.offset, p.length, p.pos };
-}
-
-// elect: slot `slot` = entry j, piece k
+// elect: slot `slot` = entry j, piece k; s: inode_plan.hpp slot_of
 template <class Ops>
 PPFS_HD inline void elect(const Tables& t, const Slot& s, uint32_t ino, uint32_t j, uint32_t k, uint32_t slot)
 {

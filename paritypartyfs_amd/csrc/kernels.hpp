@@ -2,7 +2,7 @@
 // rs_kernels.hip (Reed-Solomon and its servers), bit_kernels.hip (CRC, Hamming, parity and the bit
 // server) vote.hip (vote, copy, gather, patch list, inject, flag, block lists), alloc_scan.hip (bitmap
 // expansion, scrub tally), files_walk.hip (the file walk's expansion, extents and merges),
-// inode_walk.hip (the inode reads' extents and merge, the inode writes' election, overlay and statuses) and
+// inode_walk.hip (the inode reads' extents, the inode writes' election and overlay, their one status kernel) and
 // dir_walk.hip (the directory lookups' match and finish).
 // The three table-sizing functions are in host_tables.hpp, beside the builders that use them.
 #pragma once
@@ -137,7 +137,7 @@ hipError_t ppfs_files_write_merge_launch(const ppfs_files_owner* owner, const ui
 // table_extents: bm[j] / bst[j], the bitmap bytes and their read statuses -> ext[j * K + k], the pieces of the inodes
 // whose table is read with pos = 81 j + the bytes before piece k, every other one invalid.
 // merge: rows (81 n bytes) and pst[j * K + k], the pieces' read statuses -> files, meta, status, piece_status
-// (n * (1 + K) bytes) and the counts (five categories), each may be null.
+// (n * (1 + K) bytes) and the counts (five categories), each may be null.  The status kernel on the read's pieces.
 hipError_t ppfs_inode_bitmap_extents_launch(const void* src, uint64_t stride, uint64_t n, const ppfs_ecc_inode_table* table,
     uint64_t ds, uint32_t* ino, ppfs_ecc_extent* ext, hipStream_t s);
 hipError_t ppfs_inode_table_extents_launch(const uint32_t* ino, const uint8_t* bm, const uint8_t* bst, uint64_t n,
@@ -153,7 +153,7 @@ hipError_t ppfs_inode_merge_launch(const uint32_t* ino, const uint8_t* bm, const
 // overlay: the bytes of the winning entries' rows (files: 64 n bytes, meta: 24 n bytes, 8-byte aligned) into their
 // blocks' owner rows of P (stride ds, P_cap bytes); idx: the staged indices of the n * K extents.
 // write_status: wst[slot], the extents' write statuses -> status, piece_status (n * (1 + K) bytes) and the counts, each
-// may be null.
+// may be null.  The same status kernel on the write's pieces.
 hipError_t ppfs_inode_elect_launch(const uint32_t* ino, const uint8_t* bm, const uint8_t* bst, uint64_t n,
     const ppfs_ecc_inode_table* table, uint64_t ds, uint32_t* tab, uint32_t cap, ppfs_ecc_extent* ext, hipStream_t s);
 hipError_t ppfs_inode_overlay_launch(const uint32_t* ino, const uint8_t* bm, const uint8_t* bst, uint64_t n,

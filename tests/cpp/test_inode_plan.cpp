@@ -4,8 +4,10 @@
 // rs_block_device.cpp:28-48), Bitmap::_getByteLocation / getBit (lib/bitmap/src/bitmap.cpp:8-14, 87-101) and
 // InodeManager::get's order of evaluation (:127-138).  Every inode of a table for ds in {1, 2, 3, 27, 31, 79, 80, 81,
 // 82, 162, 249, 4091, 4095, 65535}, inode numbers near 2^32, the piece size of the device call, the status rule over
-// every combination of statuses of a short inode and random ones of a long one, and the row split over a heap buffer
-// of exactly 81 bytes.  No HIP: built with the host compiler (tests/test_inodes_cpu.py, with the address and
+// every combination of statuses of a short inode and random ones of a long one, the shared epilogue (bitmap_step,
+// inode_status) against a restatement of its former copies with the piece_status row in a heap buffer of exactly 1 + K
+// bytes, slot_of and the read's extents against piece(), and the row split over a heap buffer of exactly 81 bytes.
+// No HIP: built with the host compiler (tests/test_inodes_cpu.py, with the address and
 // undefined-behaviour sanitizers).
 #include "../../paritypartyfs_amd/csrc/inode_plan.hpp"
 
@@ -101,6 +103,29 @@ static void check_inode(uint32_t table, uint32_t bitmap, uint64_t ino, uint64_t 
     for (unsigned byte = 0; byte < 256; byte += 51) // 0x00, 0x33, 0x66, 0x99, 0xCC, 0xFF
         CHECK(((byte & b.mask) != 0) == getBit((uint8_t)byte, ino));
     CHECK(b.mask == (0x80u >> (ino % 8)));
+    // slot_of and the read's extent of a slot against piece(): entry j = 5 of a piece
+    struct Ext {
+        uint64_t pos;
+        uint32_t block;
+        uint16_t offset, length;
+    };
+    for (uint32_t k = 0; k < K; ++k) {
+        const Slot s = slot_of(table, (uint32_t)ino, k, 0, ds);
+        const Piece p = piece(table, ino, k, ds);
+        CHECK(s.takes_part == (k < np && p.block < NO_BLOCK));
+        const Ext e = slot_extent<Ext>(s, 5);
+        if (s.takes_part) {
+            CHECK(s.block == p.block && s.offset == p.offset && s.length == p.length && s.pos == p.pos);
+            CHECK(e.pos == 81u * 5u + p.pos && e.block == p.block && e.offset == p.offset && e.length == p.length);
+        } else {
+            CHECK(e.pos == 0 && e.block == NO_BLOCK && e.offset == 0 && e.length == 0);
+        }
+        for (uint32_t verdict : { 5u, 9u, 255u }) {
+            const Slot out = slot_of(table, (uint32_t)ino, k, verdict, ds);
+            const Ext none = slot_extent<Ext>(out, 5);
+            CHECK(!out.takes_part && none.pos == 0 && none.block == NO_BLOCK && none.offset == 0 && none.length == 0);
+        }
+    }
 }
 
 // InodeManager::get over per-read statuses, stopping at the first error: what the status rule restates
@@ -164,6 +189,85 @@ static void check_status_rule()
         && count_slot(2) == -1);
 }
 
+// The epilogue as each of its four copies spelt it out (the merge and write-status kernels, the two host forms) before
+// bitmap_step and inode_status held it once; pst: K piece statuses, ps: 1 + K bytes
+static uint32_t old_epilogue(uint32_t ino, uint32_t total, bool check, uint32_t bst, uint32_t bm, uint64_t ds, uint32_t K,
+    const std::vector<uint32_t>& pst, uint8_t* ps)
+{
+    const bool seen = check && ino < total && (bst == ST_OK || bst == ST_CORRECTED);
+    const uint32_t v = bitmap_verdict(ino, total, check, bst, seen ? bm : 0u, 0x80u >> (ino % 8u));
+    const bool bit_read = check && ino < total;
+    const uint32_t np = v == 0u ? pieces(ino, ds) : 0u;
+    const uint32_t st = v ? v : table_status(bit_read ? bst : 0u, np, [&](uint32_t k) { return pst[k]; });
+    ps[0] = bit_read ? (uint8_t)bst : (uint8_t)ST_UNUSED;
+    for (uint32_t k = 0; k < K; ++k)
+        ps[1u + k] = k < np ? (uint8_t)pst[k] : (uint8_t)ST_UNUSED;
+    return st;
+}
+
+static void check_one_epilogue(uint32_t ino, uint64_t ds, const std::vector<uint32_t>& pst)
+{
+    const uint32_t codes[4] = { 0, 1, 5, 9 }, K = max_pieces(ds), np = pieces(ino, ds);
+    std::vector<uint8_t> want(1 + K);
+    uint8_t* row = (uint8_t*)std::malloc(1 + K); // exactly 1 + K bytes: a store past it is the sanitizer's
+    for (uint32_t total : { ino, ino + 1u })        // out of range, the last inode
+        for (uint32_t check = 0; check < 2; ++check) // in the states that do not read the bit, its bytes are anything
+            for (uint32_t bst : codes)
+                for (int bit = 0; bit < 2; ++bit) {
+                    const uint32_t mask = 0x80u >> (ino % 8), byte = bit ? 0xFFu : (0xFFu & ~mask);
+                    const uint32_t old = old_epilogue(ino, total, check != 0, bst, byte, ds, K, pst, want.data());
+                    auto piece_st = [&](uint32_t k) {
+                        CHECK(k < np);
+                        return pst[k];
+                    };
+                    const BitmapStep b = bitmap_step(Table { 7, 3, total, check }, ino, byte, bst);
+                    std::memset(row, 0xAA, 1 + K);
+                    CHECK(inode_status(b, ino, ds, K, piece_st, row) == old);
+                    CHECK(std::memcmp(row, want.data(), 1 + K) == 0);
+                    CHECK(inode_status(b, ino, ds, K, piece_st, nullptr) == old);
+                    CHECK(b.bit_read == (ino < total && check) && b.bitmap_status == want[0]);
+                    CHECK(old == loop_status(ino, total, check != 0, bst, bit != 0, std::vector<uint32_t>(pst.begin(), pst.begin() + np)));
+                }
+    std::free(row);
+}
+
+// K in {2, 3, 4, 81}: every bitmap state with every combination of piece statuses of the inodes of one to four
+// pieces, and with random ones of the inode of 81
+static void check_epilogue()
+{
+    const uint32_t codes[4] = { 0, 1, 5, 9 };
+    uint32_t rng = 777;
+    auto next = [&]() { return rng = rng * 1664525u + 1013904223u, rng >> 16; };
+    for (uint64_t ds : { 249ull, 79ull, 31ull, 1ull }) {
+        const uint32_t K = max_pieces(ds);
+        CHECK(K == (ds == 249 ? 2u : ds == 79 ? 3u : ds == 31 ? 4u : 81u));
+        uint32_t seen_np = 0; // a bit per piece count met
+        for (uint32_t ino = 0; ino < 400; ++ino) {
+            const uint32_t np = pieces(ino, ds);
+            if (seen_np >> (np % 32u) & 1u)
+                continue;
+            seen_np |= 1u << (np % 32u);
+            std::vector<uint32_t> pst(K, 9); // the slots behind the inode's pieces: never looked at
+            if (np <= 4) {
+                for (uint32_t combo = 0; combo < (1u << (2 * np)); ++combo) {
+                    for (uint32_t k = 0; k < np; ++k)
+                        pst[k] = codes[(combo >> (2 * k)) & 3];
+                    check_one_epilogue(ino, ds, pst);
+                }
+            } else {
+                for (int round = 0; round < 500; ++round) {
+                    for (uint32_t k = 0; k < np; ++k)
+                        pst[k] = next() % 23 == 0 ? codes[next() % 4] : 0u;
+                    check_one_epilogue(ino, ds, pst);
+                }
+            }
+        }
+        CHECK(seen_np >> (K % 32u) & 1u); // an inode of K pieces was among them
+        if (ds == 249)
+            CHECK(seen_np == 0x6u); // one and two pieces
+    }
+}
+
 static void check_fields()
 {
     uint8_t* row = (uint8_t*)std::malloc(kInode); // exactly 81 bytes: a read past it is the sanitizer's
@@ -215,6 +319,7 @@ int main()
     CHECK(max_pieces(31) == 4 && max_pieces(1) == 81 && max_pieces(80) == 2 && max_pieces(79) == 3);
     CHECK(pieces(3, 249) == 2 && pieces(0, 249) == 1); // 243 + 80 = 323: every fourth inode straddles
     check_status_rule();
+    check_epilogue();
     check_fields();
     if (g_fail) {
         std::printf("%d FAILED\n", g_fail);

@@ -513,6 +513,45 @@ def test_write_then_read_on_one_stream_and_on_two(images):
     same(runs[1](), expect(im, reads2), disk2, "stream 1")
 
 
+@pytest.mark.parametrize("name", ["rs255_t3", "parity32"])  # K = 2 on the direct list path; ds = 31, K = 4, staged
+def test_reads_and_writes_alternate_on_one_stream(images, name):
+    """read, write, read, write, read queued on one stream of one context with nothing in between, every batch one
+    piece of its call plus 3 inodes: the two calls share their frame and the scratch's layout, and the second piece of
+    each starts in what the piece before left there.  Every output, the counts and the final image equal those of the
+    same five calls through the host forms, which the tests above hold to the loop."""
+    im = images(name)
+    K, eng = im.K, im.eng
+    staged = max(1024, min(eng.host_chunk_blocks() & ~1023, max(1024, ((1 << 31) // im.raw) & ~1023)))  # list_plan.hpp piece_blocks
+    piece = dict(read=2 * PIECE // K, write=min(2 * PIECE // K, max(staged // K, 1)))
+    assert (K, eng.list_kernel_name()) == dict(rs255_t3=(2, "rs255-wg-list-lds"), parity32=(4, "gather-stage-scatter"))[name]
+    calls = []
+    for step, kind in enumerate(["read", "write", "read", "write", "read"]):
+        n = piece[kind] + 3
+        nums = rng_for("alternate", name, step).integers(0, im.total, n).astype(np.uint32)
+        nums[[5, n - 1]] = nums[2]  # a number in both pieces
+        nums[[7, n - 2]] = im.total, 0xFFFFFFFF
+        assert im.free[nums[nums < im.total]].any()
+        calls.append((kind, nums, records(n, "alternate", name, step)))
+    image, want = im.clean, []
+    for kind, nums, recs in calls:
+        want.append(im.run("host", image, nums) if kind == "read" else run(im, "host", image, nums, recs))
+        image = want[-1]["image"]
+    assert not np.array_equal(image, im.clean)
+    s, g = torch.cuda.Stream(), Guarded(im.clean)
+    torch.cuda.synchronize()  # the image was copied on the default stream
+    got = [im.run("device", im.clean, nums, stream=s, guarded=g) if kind == "read"
+           else run(im, "device", im.clean, nums, recs, stream=s, guarded=g) for kind, nums, recs in calls]
+    torch.cuda.synchronize()
+    for step, ((kind, nums, _), finish, w) in enumerate(zip(calls, got, want)):
+        a = finish()
+        for k in ("files", "meta") if kind == "read" else ():
+            assert np.array_equal(a[k], w[k]), (k, step)
+        assert np.array_equal(a["status"], w["status"]) and np.array_equal(a["piece_status"], w["piece_status"]), step
+        assert a["counts"] == w["counts"] and sum(a["counts"][:5]) == len(nums), step
+        assert a["counts"].out_of_range == 2 and a["counts"].not_allocated > 0 and a["counts"].ok > 0, step
+        assert np.array_equal(a["image"], image), step  # the image after all five
+
+
 def test_extent_write_before_and_after_an_inode_write(images):
     """ppfs_ecc_write_extents_device on the same context gives what it gives on a context that never wrote an inode."""
     im = images("rs255_t3")

@@ -15,7 +15,7 @@ from tests.test_kernel_resources import kernel_descriptors
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "paritypartyfs_amd", "_lib", "libppfs_ecc.so")
 NAMES = ("ppfs_ecc_write_inodes_device", "ppfs_ecc_write_inodes_host")
-KERNELS = ("inode_elect_kernel", "inode_owner_extents_kernel", "inode_overlay_kernel", "inode_write_status_kernel")
+KERNELS = ("inode_elect_kernel", "inode_owner_extents_kernel", "inode_overlay_kernel", "inode_status_kernelINS_11WritePiecesE")
 
 
 @pytest.fixture(scope="module")
@@ -88,3 +88,4 @@ def test_inode_write_kernels_use_no_scratch(tmp_path):
         assert len(found) == 1, (frag, sorted(found))
         for n, d in found.items():
             assert d["private_segment_fixed_size"] == 0 and d["vgpr_spill_count"] == 0 and d["sgpr_spill_count"] == 0, (n, d)
+            assert 0 < d["vgpr_count"] <= 64, (n, d)  # at most 64 VGPRs: 8 waves per SIMD

@@ -16,7 +16,7 @@ from tests.test_kernel_resources import kernel_descriptors
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "paritypartyfs_amd", "_lib", "libppfs_ecc.so")
 NAMES = ("ppfs_ecc_inode_span", "ppfs_ecc_read_inodes_device", "ppfs_ecc_read_inodes_host")
-KERNELS = ("inode_bitmap_extents_kernel", "inode_table_extents_kernel", "inode_merge_kernel")
+KERNELS = ("inode_bitmap_extents_kernel", "inode_table_extents_kernel", "inode_status_kernelINS_10ReadPiecesE")
 
 
 @pytest.fixture(scope="module")
@@ -34,7 +34,10 @@ def test_inode_plan(plan_exe):
     against a literal restatement of _getInodeLocation, _readInode's two-branch loop over a clamping readBlock and
     Bitmap::_getByteLocation / getBit; pieces <= K(ds), with equality where gcd(81, ds) = 1; the device call's piece;
     the status rule against InodeManager::get's order of evaluation over all status combinations of inodes of one to
-    three pieces and random ones of an inode of 81; the row split over a heap buffer of exactly 81 bytes."""
+    three pieces and random ones of an inode of 81; the shared epilogue (bitmap_step, inode_status) for K in {2, 3, 4,
+    81} against a restatement of its four former copies, final status and the piece_status row in a heap buffer of
+    exactly 1 + K bytes, over every bitmap state and the same piece statuses; slot_of and the read's extents against
+    piece(); the row split over a heap buffer of exactly 81 bytes."""
     r = subprocess.run([plan_exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "ALL PASSED" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
 
@@ -109,3 +112,4 @@ def test_inode_kernels_use_no_scratch(tmp_path):
         assert len(found) == 1, (frag, sorted(found))
         for n, d in found.items():
             assert d["private_segment_fixed_size"] == 0 and d["vgpr_spill_count"] == 0 and d["sgpr_spill_count"] == 0, (n, d)
+            assert 0 < d["vgpr_count"] <= 64, (n, d)  # at most 64 VGPRs: 8 waves per SIMD
